@@ -15,17 +15,23 @@ left pad, no data-path collective; the one exchange is an all-gather of the pitc
 (8 B/frame), overlapped with the next step.  Rank 0 prints ONE JSON line.
 
 `value` is the contract's own region and nothing else: W untimed warm-up steps, then K timed steps between
-barrier + synchronize pairs, the first thing the process does with the device after its setup.  Everything
-else in the line is a labelled secondary measured afterwards (`value_conditioned`, `noise_input_secondary`,
-`pcm_gather_secondary`, `pv_shard_secondary`, the supplementary figures, `cpu_baseline`).  Under WORLD_SIZE > 1 the line
-carries `ranks` — every rank's own kernel times, package power, shader clock and PCI address — and `pv_shard_secondary`:
-the build-defined phase vocoder sharded over the ranks, whose two small all-gathers (phase maps, overlap-add seams) are the
+barrier + synchronize pairs, the first thing the process does with the device after its setup.  A plain run does only
+that: set-up, the W + K steps, the outputs (`--dump-outputs DIR`) and the line.  With `--full` the line also carries the
+check of the step's outputs (`outputs_ok`) and the labelled secondaries measured afterwards (`value_conditioned`,
+`noise_input_secondary`, `pcm_gather_secondary`, `pv_shard_secondary`, the supplementary figures, `roofline.limiter`,
+`cpu_baseline`; each `--no-*` option still drops its own).  Under WORLD_SIZE > 1 the line carries `ranks` — every rank's
+own kernel times, package power, shader clock and PCI address — and, with `--full`, `pv_shard_secondary`: the
+build-defined phase vocoder sharded over the ranks, whose two small all-gathers (phase maps, overlap-add seams) are the
 seam exchange BASELINE.json's north_star names; per-rank stage and all-gather times, output checked against
 the single call.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files (fixed, seeded samples of the large
+arrays, with their float64 indices), so that two builds can be compared output for output: see dump_outputs().
 """
 from __future__ import annotations
 
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -215,8 +221,6 @@ class PowerSampler:
 
 def kernel_source_hash() -> str:
     """sha1 over the STFT kernel's sources: ties a PMC traffic figure under profiles/ to the kernel it was measured on."""
-    import hashlib
-
     h = hashlib.sha1()
     for f in ("stft_kernels.hip", "stft_kernel_impl.h", "stft_core.h", "pk_math.h", "stft_tables.h", "stft_consts.inc"):
         with open(os.path.join(ROOT, "melonix_amd", "csrc", f), "rb") as fh:
@@ -316,6 +320,43 @@ def cpu_baseline(N: int, hop: int):
     }
 
 
+DUMP_ROWS_BYTES = 8 << 20   # magnitude rows written by dump_outputs (whole rows, a seeded sample of them)
+DUMP_FRAMES = 1 << 20        # pitch records written whole up to this many frames, a seeded sample beyond
+DUMP_PCM_SAMPLES = 1 << 20   # int16 PCM samples written (a seeded sample)
+
+
+def seeded_sample(n: int, k: int, seed: int):
+    """Sorted indices of k of range(n) drawn without replacement by a fixed seed (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(torch, out_dir: str, mags_t, pitch_t, pcm_t) -> None:
+    """What the last timed step handed its caller, as DIR/<name>.npy: the pitch records (`pitch_bin`, `pitch_mag`), rows of
+    the magnitude spectrogram (`mags_rows`, F x N/2 in HBM: 5.5 GB at the default size) and the int16 PCM (`pcm`, as
+    float32: exact).  Each array beyond its share (the DUMP_* sizes: under 40 MB in all) is a seeded sample, with its indices
+    in `<name>_index` (float64, exact); the seeds are fixed, so the same arguments give the same files on every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    dev = pitch_t.device
+
+    def take(t, idx):
+        return t.index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy()
+
+    F = pitch_t.shape[0]
+    fi = seeded_sample(F, DUMP_FRAMES, 1)
+    rec = take(pitch_t, fi)  # {bin int32, magnitude float32 bits}
+    out = {"pitch_bin": rec[:, 0].astype(np.float32), "pitch_mag": rec[:, 1].view(np.float32), "pitch_index": fi}
+    if mags_t is not None:
+        ri = seeded_sample(F, max(1, DUMP_ROWS_BYTES // (4 * mags_t.shape[1])), 2)
+        out.update(mags_rows=take(mags_t, ri), mags_rows_index=ri)
+    if pcm_t is not None:
+        si = seeded_sample(pcm_t.shape[0], DUMP_PCM_SAMPLES, 3)
+        out.update(pcm=take(pcm_t, si).astype(np.float32), pcm_index=si)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if name.endswith("index") else np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -351,7 +392,17 @@ def main() -> None:
     ap.add_argument("--init-timeout", type=float, default=180.0,
                     help="seconds the process-group start-up and the first collective may take before the rank prints a "
                          "one-line JSON error and exits 5 instead of hanging")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the step's outputs and measure every secondary, supplementary and CPU-baseline figure "
+                         "(--conditioning and the --no-* options above shape them); off: the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, seeded samples of "
+                         "the large arrays)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the outputs, the line — nothing else
+        args.conditioning = 0
+        args.no_cpu_baseline = args.no_supplementary = args.no_noise_secondary = args.no_limiter_probe = True
+        args.no_pcm_gather = args.no_pv_shard = True
 
     import torch
 
@@ -460,11 +511,13 @@ def main() -> None:
         t0 = time.perf_counter()
         gs, gl, gf = ctx.grain_table_dev(audio)
         t_gr = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        gs, gl, gf = ctx.grain_table_dev(audio)  # second call: work buffers exist, kernels loaded
-        t_gr2 = time.perf_counter() - t0
+        t_gr2 = None
         mk = [(1, 0, 0, 3.0), (n - 1, 0, 0, 3.0)]
-        mx.schedule_build_table(n, SR, gs, gl, gf, mk)
+        if args.full:  # (the warm set-up timings of `resynth_setup`: each call once more)
+            t0 = time.perf_counter()
+            gs, gl, gf = ctx.grain_table_dev(audio)  # second call: work buffers exist, kernels loaded
+            t_gr2 = time.perf_counter() - t0
+            mx.schedule_build_table(n, SR, gs, gl, gf, mk)
         t0 = time.perf_counter()
         steps_arr, total, _ = mx.schedule_build_table(n, SR, gs, gl, gf, mk)
         t_sc = time.perf_counter() - t0
@@ -522,6 +575,8 @@ def main() -> None:
     # (1) THE CONTRACT, with nothing added: W untimed warm-up steps, then K timed steps between barrier + synchronize
     # pairs -> `value`, `ms_per_step`, `roofline` (the first thing this process does with the device after its setup)
     elapsed, kern_ms, res_ms, my_kern_ms, my_res_ms = timed_region(args.steps, args.warmup, rs)
+    if args.dump_outputs and rank == 0:  # (before any secondary overwrites the buffers)
+        dump_outputs(torch, args.dump_outputs, mags_t, pitch_t[(args.steps - 1) & 1], rs["pcm"] if rs is not None else None)
 
     # (2) labelled secondary `value_conditioned`: the same W + K region again after `--conditioning` more untimed steps.
     # A fresh box needs some tens of milliseconds of the actual load before its memory / fabric clocks and the power
@@ -540,50 +595,50 @@ def main() -> None:
                 "resynth_kernel_ms": r_c, "conditioning_steps": args.conditioning,
                 "note": "the same W + K region after this many more untimed steps (clock / power settling); never `value`"}
 
-    # The outputs of the last timed step, checked against what the workload is (the parity tests are the correctness
-    # proof; this guards the bench run itself against a skipped or mis-launched kernel): every pitch bin in the band, and —
-    # the signal is a linear sweep — within two bins of the sweep's instantaneous frequency at the frame's newest samples.
-    bins = pitch_t[(args.steps - 1) & 1][:, 0].clone()
-    ok = bool(((bins >= band[0]) & (bins <= band[1])).all().item())
-    h = torch.arange(F, device=dev, dtype=torch.float64)
-    newest = (rank * n + (h + 1.0) * hop - 0.5 * hop).clamp_(min=0.0)   # global sample index at the middle of the newest hop
-    f_inst = 110.0 + (1760.0 - 110.0) * newest / float(world * n)
-    want_bin = f_inst * N / SR
-    settled = h >= (N // hop)                                           # (frames that still reach before the signal's start aside)
-    bin_err = (bins.to(torch.float64) - want_bin).abs()[settled]
-    pitch_err = float(bin_err.max().item()) if bin_err.numel() else 0.0
-    ok = ok and pitch_err <= 2.5
-    import hashlib
-
-    # sha1 of this rank's pitch track after the last timed step (a sharded run's gathered track carries its own below:
-    # N ranks over one signal must reproduce the single-rank track of that signal bit for bit)
-    local_track_sha1 = hashlib.sha1(pitch_t[(args.steps - 1) & 1].cpu().numpy().tobytes()).hexdigest()
     exchange = None
-    if use_dist:  # the gathered whole-signal track must contain this rank's shard, bit for bit
-        g = gathered[(args.steps - 1) & 1]
-        g_ok = bool(torch.equal(g[rank * F:(rank + 1) * F], pitch_t[(args.steps - 1) & 1]))
-        ok = ok and g_ok
-        okt = torch.tensor([1 if ok else 0, 1 if g_ok else 0], device=dev)
-        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-        ok, g_ok = bool(okt[0].item()), bool(okt[1].item())
-        track_sha1 = hashlib.sha1(g.cpu().numpy().tobytes()).hexdigest()
-        exchange = {"backend": dist.get_backend(), "collective": "all_gather_into_tensor", "async_op": True,
-                    "gathered_track_sha1": track_sha1,
-                    "bytes_per_rank": int(pitch_t[0].numel() * 4), "world_size": world,
-                    "gathered_equals_local": g_ok,
-                    "note": "per-rank pitch tracks (8 B/frame) stitched into the whole-signal track on RCCL's stream, "
-                            "double-buffered against the next step's kernels"}
+    if args.full:
+        # The outputs of the last timed step, checked against what the workload is (the parity tests are the correctness
+        # proof; this guards the bench run itself against a skipped or mis-launched kernel): every pitch bin in the band, and —
+        # the signal is a linear sweep — within two bins of the sweep's instantaneous frequency at the frame's newest samples.
+        bins = pitch_t[(args.steps - 1) & 1][:, 0].clone()
+        ok = bool(((bins >= band[0]) & (bins <= band[1])).all().item())
+        h = torch.arange(F, device=dev, dtype=torch.float64)
+        newest = (rank * n + (h + 1.0) * hop - 0.5 * hop).clamp_(min=0.0)   # global sample index at the middle of the newest hop
+        f_inst = 110.0 + (1760.0 - 110.0) * newest / float(world * n)
+        want_bin = f_inst * N / SR
+        settled = h >= (N // hop)                                           # (frames that still reach before the signal's start aside)
+        bin_err = (bins.to(torch.float64) - want_bin).abs()[settled]
+        pitch_err = float(bin_err.max().item()) if bin_err.numel() else 0.0
+        ok = ok and pitch_err <= 2.5
 
-    pcm_rms = None
-    if rs is not None:  # the resynthesis leg: the terminating zeros, and a sweep of amplitude 0.5 has an rms of 0.5 / sqrt(2)
-        tail_ok = not bool(rs["pcm"][-1500:].any().item())
-        body = rs["pcm"][: rs["total"] - 1500]
-        pcm_rms = float(body.to(torch.float32).pow(2).mean().sqrt().item() / 32767.0)
-        ok = ok and tail_ok and 0.33 <= pcm_rms <= 0.375
-    if use_dist:  # the line's outputs_ok is every rank's
-        okf = torch.tensor([1 if ok else 0], device=dev)
-        dist.all_reduce(okf, op=dist.ReduceOp.MIN)
-        ok = bool(okf.item())
+        # sha1 of this rank's pitch track after the last timed step (a sharded run's gathered track carries its own below:
+        # N ranks over one signal must reproduce the single-rank track of that signal bit for bit)
+        local_track_sha1 = hashlib.sha1(pitch_t[(args.steps - 1) & 1].cpu().numpy().tobytes()).hexdigest()
+        if use_dist:  # the gathered whole-signal track must contain this rank's shard, bit for bit
+            g = gathered[(args.steps - 1) & 1]
+            g_ok = bool(torch.equal(g[rank * F:(rank + 1) * F], pitch_t[(args.steps - 1) & 1]))
+            ok = ok and g_ok
+            okt = torch.tensor([1 if ok else 0, 1 if g_ok else 0], device=dev)
+            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+            ok, g_ok = bool(okt[0].item()), bool(okt[1].item())
+            track_sha1 = hashlib.sha1(g.cpu().numpy().tobytes()).hexdigest()
+            exchange = {"backend": dist.get_backend(), "collective": "all_gather_into_tensor", "async_op": True,
+                        "gathered_track_sha1": track_sha1,
+                        "bytes_per_rank": int(pitch_t[0].numel() * 4), "world_size": world,
+                        "gathered_equals_local": g_ok,
+                        "note": "per-rank pitch tracks (8 B/frame) stitched into the whole-signal track on RCCL's stream, "
+                                "double-buffered against the next step's kernels"}
+
+        pcm_rms = None
+        if rs is not None:  # the resynthesis leg: the terminating zeros, and a sweep of amplitude 0.5 has an rms of 0.5 / sqrt(2)
+            tail_ok = not bool(rs["pcm"][-1500:].any().item())
+            body = rs["pcm"][: rs["total"] - 1500]
+            pcm_rms = float(body.to(torch.float32).pow(2).mean().sqrt().item() / 32767.0)
+            ok = ok and tail_ok and 0.33 <= pcm_rms <= 0.375
+        if use_dist:  # the line's outputs_ok is every rank's
+            okf = torch.tensor([1 if ok else 0], device=dev)
+            dist.all_reduce(okf, op=dist.ReduceOp.MIN)
+            ok = bool(okf.item())
     supplementary = rank == 0 and world == 1 and not args.no_resynth and not args.no_supplementary
     host = audio_t[pad:pad + n].cpu().numpy() if supplementary else None
     # supplementary (SURVEY 8d timing protocol, second figure): end to end from a host buffer — H2D of the audio
@@ -964,18 +1019,19 @@ def main() -> None:
             "kernels": kernels,
             # labelled secondary: BASELINE configs[1] alone (what round 1 quoted as `value`)
             "stft_pitch_only": {"frames_per_s": world * F / (kern_ms * 1e-3), "kernel_ms": kern_ms},
-            "pitch_track_sha1": local_track_sha1,
             # which build ran: the digits mx_version() carries = sha1 over the library's sources and flags (melonix_amd/build.py);
             # the loader refuses a library whose digits differ from the tree's
             "library_version": mx._capi.lib().mx_version().decode(),
             "library_src_sha": mx._capi.library_src_sha(mx._capi.lib().mx_version().decode()),
-            "outputs_ok": ok,
-            "outputs_check": {"pitch_max_abs_bin_error_vs_sweep": pitch_err, "pcm_rms_full_scale": pcm_rms,
-                              "note": "every pitch bin in band and within 2.5 bins of the sweep's instantaneous frequency at the "
-                                      "frame's newest hop; int16 PCM rms within 0.33 .. 0.375 of full scale (0.5 / sqrt 2 = 0.354), "
-                                      "terminating zeros in place; MIN over ranks"},
         }
-        if rs is not None:
+        if args.full:
+            line["pitch_track_sha1"] = local_track_sha1
+            line["outputs_ok"] = ok
+            line["outputs_check"] = {"pitch_max_abs_bin_error_vs_sweep": pitch_err, "pcm_rms_full_scale": pcm_rms,
+                                     "note": "every pitch bin in band and within 2.5 bins of the sweep's instantaneous frequency at the "
+                                             "frame's newest hop; int16 PCM rms within 0.33 .. 0.375 of full scale (0.5 / sqrt 2 = 0.354), "
+                                             "terminating zeros in place; MIN over ranks"}
+        if args.full and rs is not None:
             line["resynth_setup"] = {"grain_scan_s": rs["grain_scan_s"], "grain_scan_warm_s": rs["grain_scan_warm_s"],
                                      "schedule_host_s": rs["schedule_host_s"],
                                      "note": "once per (audio, markers), before the timed region"}

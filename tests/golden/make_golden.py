@@ -64,7 +64,36 @@ def main():
         pvg[f"st_{st:+.0f}"] = {"samples": y[::997].tolist(), "rms": float(np.sqrt((y ** 2).mean())), "len": len(y)}
     with open(os.path.join(HERE, "pv_sweep2.json"), "w") as f:
         json.dump(pvg, f)
+    if O.ref_lib() is not None:
+        ref_savewav()
     print("wrote", os.listdir(HERE))
+
+
+SAVEWAV_LENGTHS = (0, 1, 2, 3, 1000, 70001)
+SAVEWAV_RATES = (48000, 44100, 8000)
+
+
+def savewav_pcm(m):
+    """test_oracle.py's saveWav input of m samples."""
+    return np.random.default_rng(m).integers(-32768, 32767, m, dtype=np.int16)
+
+
+def ref_savewav():
+    """ref_savewav.json: length and sha256 of the bytes the reference's own save-wav.cpp (oracle/_ref, built by
+    `make -C oracle ref` from the reference tree) writes for each test input — the saveWav parity test's answer wherever
+    that build is absent."""
+    import tempfile
+
+    g = {"what": "reference save-wav.cpp output for savewav_pcm(m) at each sample rate", "pcm": {}, "wav": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for m in SAVEWAV_LENGTHS:
+            pcm = savewav_pcm(m)
+            g["pcm"][str(m)] = hashlib.sha256(pcm.tobytes()).hexdigest()
+            for sr in SAVEWAV_RATES:
+                b = O.ref_wav_bytes(pcm, sr, os.path.join(tmp, "r.wav"))
+                g["wav"][f"{m}@{sr}"] = {"bytes": len(b), "sha256": hashlib.sha256(b).hexdigest()}
+    with open(os.path.join(HERE, "ref_savewav.json"), "w") as f:
+        json.dump(g, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -32,7 +32,7 @@ def _bench(args, launcher):
     if launcher:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port())]
-    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args
+    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full"] + args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -126,7 +126,7 @@ def _bench_ranks_one_device(args, world=2):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
-           "--single-device"] + args
+           "--single-device", "--full"] + args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -193,7 +193,7 @@ def _bench_ranks_by_hand(args, world, mask_devices, timeout=600):
         env.update({"RANK": str(r), "LOCAL_RANK": str(r), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": port})
         if mask_devices:
             env["HIP_VISIBLE_DEVICES"] = "0"  # (the box has one GPU: every rank's "own" device is that one)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + args, cwd=ROOT, env=env,
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full"] + args, cwd=ROOT, env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p_ in procs:

@@ -2,8 +2,8 @@
 
  * grains / process / export / time maps: the known-answer facts the survey recorded from the
    compiled reference.
- * saveWav: byte-compared with the reference's own save-wav.cpp (oracle/_ref, built from
-   /root/reference in the build container; travels prebuilt to the GPU box).
+ * saveWav: byte-compared with the reference's own save-wav.cpp: with its build (oracle/_ref) where
+   there is one, and always with the digests of its output stored in golden/ref_savewav.json.
  * the double DFT that stands where FFTW stands: against an independent f64 FFT (numpy
    pocketfft) and analytic DFT pairs — the reference holds no golden vectors for it.
 """
@@ -70,13 +70,17 @@ def test_memo_equals_pure_on_export(oracle, sweep10):
 # ---- saveWav against the reference's own code -----------------------------------------------
 @pytest.mark.parametrize("m", [0, 1, 2, 3, 1000, 70001])
 def test_savewav_matches_reference_build(oracle, tmp_path, m):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here and no prebuilt .so)")
+    with open(os.path.join(GOLD, "ref_savewav.json")) as f:
+        gold = json.load(f)  # recorded from the reference build by golden/make_golden.py
     rng = np.random.default_rng(m)
     pcm = rng.integers(-32768, 32767, m, dtype=np.int16)
+    assert hashlib.sha256(pcm.tobytes()).hexdigest() == gold["pcm"][str(m)]  # the input the digests were taken of
     for sr in (48000, 44100, 8000):
-        ref = oracle.ref_wav_bytes(pcm, sr, tmp_path / "r.wav")
-        assert oracle.wav_bytes(pcm, sr) == ref
+        got = oracle.wav_bytes(pcm, sr)
+        ref = gold["wav"][f"{m}@{sr}"]
+        assert len(got) == ref["bytes"] and hashlib.sha256(got).hexdigest() == ref["sha256"]
+        if oracle.ref_lib() is not None:
+            assert got == oracle.ref_wav_bytes(pcm, sr, tmp_path / "r.wav")
 
 
 # ---- the DFT that stands where FFTW stands ---------------------------------------------------

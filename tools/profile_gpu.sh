@@ -11,7 +11,7 @@ OUT=gpurun_out
 # supplementary extras.  PROF_KERNEL=<substring> picks the kernel whose PMC rows are summarised (default stft_kernel;
 # PROF_RESYNTH=1 = resynth_kernel_v).
 NORES="--no-supplementary --no-noise-secondary --no-limiter-probe"; [ "${PROF_RESYNTH:-0}" = "1" ] && export PROF_KERNEL=${PROF_KERNEL:-resynth_kernel_v}
-BENCH="python bench.py --steps 50 --warmup 10 --no-cpu-baseline $NORES $*"
+BENCH="python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline $NORES $*"
 mkdir -p $OUT
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o stft -- $BENCH > $OUT/prof_${TAG}_bench.log 2>&1
 PASSES=(
@@ -24,7 +24,7 @@ PASSES=(
 i=0
 for P in "${PASSES[@]}"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --output-format csv --pmc $P -d $OUT/pmc_${TAG}_$i -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline $NORES $* > $OUT/pmc_${TAG}_$i.log 2>&1 || echo "pass $i failed" >> $OUT/pmc_${TAG}_fail.log
+  rocprofv3 --kernel-trace --output-format csv --pmc $P -d $OUT/pmc_${TAG}_$i -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline $NORES $* > $OUT/pmc_${TAG}_$i.log 2>&1 || echo "pass $i failed" >> $OUT/pmc_${TAG}_fail.log
 done
 python tools/summarize_prof.py $TAG > $OUT/prof_${TAG}_summary.txt 2>&1
 find $OUT -name "*.db" -delete; find $OUT -name "*agent_info*" -delete

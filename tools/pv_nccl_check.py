@@ -1,7 +1,7 @@
 """tools/pv_nccl_check.py [seconds] — the sharded phase vocoder over RCCL, stand-alone (run under torch.distributed.run, one rank
 per GPU: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/pv_nccl_check.py 600`):
 shard.pv_pitch_shift_rank_dev (three device stages, two small all-gathers: 12 KiB of phase maps and 30 KiB of overlap-add seams
-per rank) against the single call on the same signal, per-rank stage and all-gather times.  bench.py --gpus N carries the same
+per rank) against the single call on the same signal, per-rank stage and all-gather times.  bench.py --gpus N --full carries the same
 check as `pv_shard_secondary`; this is the 30-second version for a first multi-GPU box."""
 import os
 import sys
