@@ -379,6 +379,61 @@ int mx_minmax_pyramid_dev(mx_ctx *ctx, const mx_audio *a, float *d_picks, int64_
 void mx_minmax_range(const float *host_wav, int64_t n, const float *picks, const int64_t *counts, int nlevels,
                      int start, int end, float *mn, float *mx);
 
+/* ---- YIN f0 tracking, notes, pitch-correction markers (BUILD-DEFINED) ---------------------------------
+ * The reference has no f0 estimator (Marker::note comes from the mouse, app.cpp:923,937); the build defines one, and
+ * parity is against that definition (restated in f64 by tests/yin_ref.py).  N = 4096, W = N/2.  Frame h is centred on
+ * sample h*hop and reads x_j = audio[h*hop - W + j], j < N (zeros outside the file).  Per frame:
+ *   d(tau) = sum_{j<W} (x_j - x_{j+tau})^2 (tau <= W, >= 0), d'(tau) = d(tau) * tau / sum_{j=1..tau} d(j) (1 where 0);
+ *   search range tau_min = max(2, floor(sr/fmax)) .. tau_max = min(W-1, ceil(sr/fmin));
+ *   tau* = the first tau in range with d' < threshold, then forward while d'(tau+1) < d'(tau) (tau+1 <= tau_max);
+ *   none under threshold: the argmin of d' over the range (lowest tau on ties);
+ *   period = tau* + parabolic offset on d at tau*-1, tau*, tau*+1 (clamped to +-1/2, 0 if the curvature is <= 0).
+ * Defaults fmin = 55, fmax = 1760 Hz (notes 24..84), threshold 0.15.  Note law (mx_bin_note's):
+ * note = 24 + 12*log2(sr / period / 55). */
+typedef struct mx_f0 {
+  int32_t tau;        /* tau* (0: silent frame) */
+  float period;       /* tau* + parabolic offset, samples (0: silent) */
+  float aperiodicity; /* d'(tau*) (1: silent) */
+  float rms;          /* sqrt(sum x_j^2 / N) over the frame (0: silent) */
+} mx_f0;
+
+/* Frames [first_frame, first_frame + count) of the bulk indexing (first_frame + count <= mx_frame_count(n, hop)).
+ * Host output, blocks.  MX_ERR_INVALID for sr <= 0, hop outside [1, 16384], fmin <= 0, fmax <= 0, an empty search range
+ * or frames outside the file. */
+int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                float fmin, float fmax, float threshold, mx_f0 *out);
+/* Same, the records stay in HBM (count x 16 bytes).  Asynchronous on the context's stream. */
+int mx_f0_track_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                    float fmin, float fmax, float threshold, mx_f0 *d_out);
+
+/* Notes (host, double).  A frame is voiced when tau > 0, aperiodicity < threshold and rms >= rms_floor.  A note is a
+ * maximal run of voiced frames; a new run starts before frame f when |m_f - m_{f-1}| > max_jump or
+ * |m_f - median(m over the run so far)| > max_dev (m = the frame's note; the median of an even count is the mean of the
+ * two middle values).  Runs shorter than min_frames (>= 2) are dropped. */
+typedef struct mx_note_params {
+  float threshold, rms_floor;
+  double max_jump, max_dev;
+  int32_t min_frames;
+} mx_note_params;
+typedef struct mx_note {
+  int32_t start_sample, end_sample; /* centres of the run's first and last frames */
+  int32_t first_frame, frames;      /* frame index of the run's first frame (track[0] is frame first_frame), run length */
+  double note;                      /* the run's median note */
+  float aperiodicity;               /* the run's mean */
+  float spread;                     /* max |m_f - note| */
+} mx_note;
+/* {0.15, 1e-3, 0.5, 0.75, 8} */
+void mx_note_params_default(mx_note_params *p);
+/* track: count records of frames first_frame .. first_frame+count-1 (hop samples apart).  *notes is library-allocated
+ * (free with mx_free; NULL when there are none). */
+int mx_detect_notes(const mx_f0 *track, int64_t count, int sampleRate, int hop, int64_t first_frame,
+                    const mx_note_params *params, mx_note **notes, int64_t *nnotes);
+/* Correction markers: each note moves to T, the nearest integer note whose pitch class T mod 12 (A = 0) is set in
+ * scale_mask (bits 0..11; 0 = all twelve), ties to the lower note; bend b = strength * (T - note), strength in [0, 1].
+ * out (2*count markers): {start_sample, note, 0, b}, {end_sample, note, 0, b} per note — strictly increasing samples,
+ * dTime 0 (the time map stays the identity).  The notes must be in order and not overlap. */
+int mx_correction_markers(const mx_note *notes, int64_t count, double strength, int scale_mask, mx_marker *out);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

@@ -14,10 +14,11 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import MX_AUDIO_PAD, PITCH_DTYPE, STEP_DTYPE, MxError  # noqa: F401
+from ._capi import F0_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, PITCH_DTYPE, STEP_DTYPE, MxError  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
-           "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration"]
+           "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
+           "F0_DTYPE", "NOTE_DTYPE", "MARKER_DTYPE", "note_params_default", "detect_notes", "correction_markers"]
 
 
 def _ptr(a):
@@ -231,6 +232,23 @@ class Context:
         _capi.check(_capi.lib().mx_stft_ranges_dev(self.handle, audio.handle, N, C.c_void_p(d_ranges), count,
                                                    band[0], band[1], C.c_void_p(d_mags or 0),
                                                    C.c_void_p(d_pitch or 0)))
+
+    # ---- YIN f0 tracking (build-defined; include/melonix_amd.h) ----
+    def f0_track(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, fmin: float = 55.0,
+                 fmax: float = 1760.0, threshold: float = 0.15):
+        """-> F0_DTYPE records of frames [first, first + count) (frame h centred on sample h*hop)."""
+        if count is None:
+            count = frame_count(audio.n, hop) - first
+        out = np.empty(max(count, 0), dtype=F0_DTYPE)
+        _capi.check(_capi.lib().mx_f0_track(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
+                                            _ptr(out)))
+        return out
+
+    def f0_track_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_out: int, fmin: float = 55.0,
+                     fmax: float = 1760.0, threshold: float = 0.15):
+        """The records stay in HBM at d_out (count x 16 bytes); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_f0_track_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
+                                                C.c_void_p(d_out or 0)))
 
     # ---- grains / resynthesis ----
     def grains_dev(self, audio: Audio):
@@ -473,3 +491,41 @@ def column_range(markers, sr, time, width, range_time):
     _capi.lib().mx_column_range(_capi.markers_array(markers), len(markers), sr, float(time), int(width),
                                 float(range_time), C.byref(k), C.byref(s), C.byref(e))
     return k.value, s.value, e.value
+
+
+# ---- notes and correction markers (host; build-defined) ----
+def note_params_default() -> dict:
+    p = _capi.NoteParams()
+    _capi.lib().mx_note_params_default(C.byref(p))
+    return {k: getattr(p, k) for k, _ in _capi.NoteParams._fields_}
+
+
+def detect_notes(track, sr: int, hop: int, first: int = 0, **params):
+    """Notes of an F0_DTYPE track (track[0] = frame `first`) -> NOTE_DTYPE array.  params: threshold, rms_floor, max_jump,
+    max_dev, min_frames (defaults: note_params_default())."""
+    track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+    p = _capi.NoteParams()
+    _capi.lib().mx_note_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(_capi.NoteParams._fields_):
+            raise TypeError(f"unknown note parameter {k!r}")
+        setattr(p, k, v)
+    out, cnt = C.POINTER(_capi.Note)(), C.c_int64()
+    _capi.check(_capi.lib().mx_detect_notes(_ptr(track) if len(track) else None, len(track), sr, hop, first, C.byref(p),
+                                            C.byref(out), C.byref(cnt)))
+    if not cnt.value:
+        _capi.lib().mx_free(out)
+        return np.zeros(0, NOTE_DTYPE)
+    buf = (C.c_char * (cnt.value * NOTE_DTYPE.itemsize)).from_address(C.addressof(out.contents))
+    notes = np.frombuffer(bytes(buf), dtype=NOTE_DTYPE).copy()
+    _capi.lib().mx_free(out)
+    return notes
+
+
+def correction_markers(notes, strength: float = 1.0, scale_mask: int = 0):
+    """Two markers per note (MARKER_DTYPE): {start, note, 0, b}, {end, note, 0, b}, b = strength * (target - note)."""
+    notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    out = np.zeros(2 * len(notes), dtype=MARKER_DTYPE)
+    _capi.check(_capi.lib().mx_correction_markers(_ptr(notes) if len(notes) else None, len(notes), float(strength),
+                                                  int(scale_mask), _ptr(out) if len(out) else None))
+    return out

@@ -35,18 +35,22 @@ UNITS = [
     ("grain_chain.hip", "hip", []),
     # build-defined phase vocoder: shares the FFT passes of stft_core.h (explicit FMAs)
     ("pv_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # build-defined YIN f0 tracker: three transforms per frame on the same FFT passes
+    ("f0_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
     ("capi_pv.cpp", "hip", []),
     ("capi_resynth.cpp", "hip", []),
     ("capi_pyramid.cpp", "hip", []),
+    ("capi_f0.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 HEADERS = ["kernels.h", "colormap_core.h", "stft_kernel_impl.h", "stft_core.h", "pk_math.h", "stft_tables.h", "stft_consts.inc",
-           "host_logic.h", "capi_internal.h",
+           "host_logic.h", "capi_internal.h", "f0_notes.h",
            os.path.join("..", "..", "include", "melonix_amd.h")]
 
 

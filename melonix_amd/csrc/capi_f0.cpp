@@ -1,0 +1,142 @@
+// capi_f0.cpp — the YIN f0 tracker (f0_kernels.hip), notes and correction markers (f0_notes.cpp): BUILD-DEFINED, the
+// reference has no detector.  One unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).
+#include "capi_internal.h"
+#include "f0_notes.h"
+
+using namespace mx;
+
+namespace {
+
+constexpr int kF0W = 2048;
+
+// the search range of (sr, fmin, fmax), or a failed status
+int f0_range(int sampleRate, float fmin, float fmax, int &tmin, int &tmax) {
+  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  if (!(fmin > 0.f) || !(fmax > 0.f) || !std::isfinite(fmin) || !std::isfinite(fmax))
+    return fail(MX_ERR_INVALID, "f0 band [%g, %g] Hz: both ends must be positive and finite", (double)fmin, (double)fmax);
+  const double lo = std::floor((double)sampleRate / (double)fmax), hi = std::ceil((double)sampleRate / (double)fmin);
+  tmin = (int)std::max(2.0, std::min(lo, 1e9));
+  tmax = (int)std::min((double)(kF0W - 1), hi);
+  if (tmin > tmax)
+    return fail(MX_ERR_INVALID, "empty lag range [%d, %d] for %g..%g Hz at %d Hz", tmin, tmax, (double)fmin, (double)fmax,
+                sampleRate);
+  return MX_OK;
+}
+
+int f0_check(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
+             float fmax, float threshold, int &tmin, int &tmax) {
+  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+  if (!std::isfinite(threshold)) return fail(MX_ERR_INVALID, "threshold is not finite");
+  if (first_frame < 0 || count < 0) return fail(MX_ERR_INVALID, "negative frame range");
+  const int64_t frames = (a->n + hop - 1) / hop;
+  if (first_frame > frames || count > frames - first_frame)
+    return fail(MX_ERR_INVALID, "frames [%lld, %lld) outside the %lld frames of the file", (long long)first_frame,
+                (long long)(first_frame + count), (long long)frames);
+  return f0_range(sampleRate, fmin, fmax, tmin, tmax);
+}
+
+int f0_launch(mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_frame, int64_t count, int tmin, int tmax,
+              float threshold, mx_f0 *d_out) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  NTables t;
+  if (const int rc = get_tables(ctx, 4096, t)) return rc;
+  F0Args g{};
+  g.audio = a->d_padded;
+  g.hop = hop;
+  g.first_frame = first_frame;
+  g.count = count;
+  g.tau_min = tmin;
+  g.tau_max = tmax;
+  g.threshold = threshold;
+  g.tw2 = t.tw2;
+  g.tw3 = t.tw3;
+  g.ubase = t.ubase;
+  g.out = d_out;
+  HIP_TRY(launch_f0(g, ctx->stream));
+  return MX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mx_f0_track_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                    float fmin, float fmax, float threshold, mx_f0 *d_out) {
+  return mx_guard([&]() -> int {
+    int tmin = 0, tmax = 0;
+    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
+    if (count > 0 && !d_out) return fail(MX_ERR_INVALID, "null output");
+    return f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_out);
+  });
+}
+
+int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
+                float fmax, float threshold, mx_f0 *out) {
+  return mx_guard([&]() -> int {
+    int tmin = 0, tmax = 0;
+    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
+    if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
+    if (count == 0) return MX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)count * sizeof(mx_f0);
+    std::lock_guard<std::mutex> lk(ctx->stage_mu);
+    void *d = nullptr;
+    HIP_TRY(stage_get(ctx, 0, bytes, &d));
+    int rc = f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, static_cast<mx_f0 *>(d));
+    if (rc == MX_OK) {
+      hipError_t e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "f0 download: %s", hipGetErrorString(e));
+    }
+    stage_trim(ctx);
+    return rc;
+  });
+}
+
+void mx_note_params_default(mx_note_params *p) {
+  mx_guard_void([&] {
+    if (p) *p = mx_note_params{0.15f, 1e-3f, 0.5, 0.75, 8};
+  });
+}
+
+int mx_detect_notes(const mx_f0 *track, int64_t count, int sampleRate, int hop, int64_t first_frame,
+                    const mx_note_params *params, mx_note **notes, int64_t *nnotes) {
+  return mx_guard([&]() -> int {
+    if (!params || !notes || !nnotes || (count > 0 && !track)) return fail(MX_ERR_INVALID, "null argument");
+    if (count < 0 || first_frame < 0) return fail(MX_ERR_INVALID, "negative frame range");
+    if (sampleRate <= 0 || hop < 1) return fail(MX_ERR_INVALID, "sample rate %d / hop %d", sampleRate, hop);
+    if ((first_frame + count) * (int64_t)hop > INT32_MAX) return fail(MX_ERR_INVALID, "frame centres beyond int32 samples");
+    const mx_note_params &p = *params;
+    if (p.min_frames < 2) return fail(MX_ERR_INVALID, "min_frames %d < 2", p.min_frames);
+    if (!std::isfinite(p.threshold) || !std::isfinite(p.rms_floor) || !(p.max_jump >= 0.0) || !(p.max_dev >= 0.0))
+      return fail(MX_ERR_INVALID, "note parameters must be finite, the deviations >= 0");
+    const std::vector<mx_note> v = detect_notes(track, count, sampleRate, hop, first_frame, p);
+    mx_note *buf = nullptr;
+    if (!v.empty()) {
+      buf = static_cast<mx_note *>(std::malloc(v.size() * sizeof(mx_note)));
+      if (!buf) return fail(MX_ERR_NOMEM, "out of host memory");
+      std::memcpy(buf, v.data(), v.size() * sizeof(mx_note));
+    }
+    *notes = buf;
+    *nnotes = (int64_t)v.size();
+    return MX_OK;
+  });
+}
+
+int mx_correction_markers(const mx_note *notes, int64_t count, double strength, int scale_mask, mx_marker *out) {
+  return mx_guard([&]() -> int {
+    if (count < 0 || (count > 0 && (!notes || !out))) return fail(MX_ERR_INVALID, "null argument");
+    if (!(strength >= 0.0 && strength <= 1.0)) return fail(MX_ERR_INVALID, "strength %g outside [0, 1]", strength);
+    if (scale_mask < 0 || scale_mask > 0xFFF) return fail(MX_ERR_INVALID, "scale mask 0x%x beyond the twelve classes", scale_mask);
+    for (int64_t i = 0; i < count; ++i) {
+      if (!std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
+      if (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample))
+        return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
+    }
+    correction_markers(notes, count, strength, scale_mask, out);
+    return MX_OK;
+  });
+}
+
+}  // extern "C"

@@ -141,6 +141,20 @@ hipError_t launch_pv_edge_sum(float *dst, const float *x, const float *y, int n,
 hipError_t launch_pv_plan_const(int64_t *apos, uint32_t *hop, double *hratio, int64_t rows, int64_t fbase, double r,
                                 hipStream_t s);
 
+// Build-defined YIN f0 tracker (f0_kernels.hip; the reference has no detector).  Frame first_frame + f (f < count) is
+// centred on sample (first_frame + f) * hop; out[f] its record.  tau_min / tau_max: the search range, checked by the caller.
+struct F0Args {
+  const float *audio;  // padded image (zeros in the pads)
+  int hop;
+  int64_t first_frame;
+  int64_t count;
+  int tau_min, tau_max;
+  float threshold;
+  const float2 *tw2, *tw3, *ubase;  // Plan<4096,16> tables
+  mx_f0 *out;
+  int frames_per_block;  // 0: the default
+};
+hipError_t launch_f0(const F0Args &a, hipStream_t s);
 // spec-cache.cpp:77-96 colormap: nbins_total magnitudes -> 3*nbins_total bytes (both device).
 hipError_t launch_colormap(const float *mags, uint8_t *rgb, int64_t nbins_total, float k, hipStream_t s);
 

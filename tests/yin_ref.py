@@ -1,0 +1,184 @@
+"""Float64 restatement of the build-defined YIN f0 tracker, notes and correction markers (definition:
+include/melonix_amd.h, f0_kernels.hip).  Test-side only: the product never imports it.
+
+track()          d through float64 FFTs and prefix sums (cross-checked against the literal double sum of step 1 by the
+                 CPU suite); also returns d' so that the GPU tests can tell near-ties from disagreements
+detect_notes()   the same loop as f0_notes.cpp, in the same order of float64 operations (math.log2 = the C library's
+                 log2): notes come out with equal doubles
+correction_markers()
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+N, W = 4096, 2048
+SILENT = (0, 0.0, 1.0, 0.0)
+
+
+def frames_of(w, hop, first, count):
+    """x[f] = audio[(first+f)*hop - W + j], j < N, zeros outside the file (float64)."""
+    w = np.asarray(w, dtype=np.float64)
+    pad = np.concatenate([np.zeros(W), w, np.zeros(N + hop)])
+    idx = (np.arange(first, first + count, dtype=np.int64) * hop)[:, None] + np.arange(N)[None, :]
+    return pad[idx]
+
+
+def tau_range(sr, fmin=55.0, fmax=1760.0):
+    fmin, fmax = float(np.float32(fmin)), float(np.float32(fmax))
+    return max(2, math.floor(sr / fmax)), min(W - 1, math.ceil(sr / fmin))
+
+
+def diff_fft(x):
+    """d(tau), tau = 0..W, per row of x (F x N): e0 + e_tau - 2 r(tau), clamped to >= 0."""
+    a = np.zeros_like(x)
+    a[:, :W] = x[:, :W]
+    r = np.fft.irfft(np.conj(np.fft.rfft(a, axis=1)) * np.fft.rfft(x, axis=1), n=N, axis=1)[:, :W + 1]
+    S = np.concatenate([np.zeros((x.shape[0], 1)), np.cumsum(x * x, axis=1)], axis=1)
+    tau = np.arange(W + 1)
+    e = S[:, tau + W] - S[:, tau]
+    return np.maximum(S[:, W:W + 1] + e - 2 * r, 0.0)
+
+
+def diff_direct(x):
+    """Step 1 literally: sum_{j<W} (x_j - x_{j+tau})^2 in double (one row)."""
+    return np.array([float(np.sum((x[:W] - x[t:t + W]) ** 2)) for t in range(W + 1)])
+
+
+def cmnd(d):
+    """d'(tau): d(0)' = 1, d(tau) tau / sum_{j=1..tau} d(j), 1 where that sum is 0."""
+    cs = np.cumsum(d[:, 1:], axis=1)
+    tau = np.arange(1, W + 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dp = np.where(cs == 0, 1.0, d[:, 1:] * tau / np.where(cs == 0, 1.0, cs))
+    return np.concatenate([np.ones((d.shape[0], 1)), dp], axis=1)
+
+
+def pick(dp_row, tmin, tmax, theta):
+    under = np.nonzero(dp_row[tmin:tmax + 1] < theta)[0]
+    if len(under):
+        t = tmin + int(under[0])
+        while t + 1 <= tmax and dp_row[t + 1] < dp_row[t]:
+            t += 1
+        return t
+    return tmin + int(np.argmin(dp_row[tmin:tmax + 1]))
+
+
+def track(w, sr, hop=256, first=0, count=None, fmin=55.0, fmax=1760.0, threshold=0.15, chunk=2048):
+    """-> (records: list of (tau, period, aperiodicity, rms), dp: F x (W+1) d' rows, or None when not kept)."""
+    n = len(w)
+    if count is None:
+        count = -(-n // hop) - first
+    tmin, tmax = tau_range(sr, fmin, fmax)
+    theta = float(np.float32(threshold))
+    recs, dps = [], []
+    for c0 in range(0, count, chunk):
+        x = frames_of(w, hop, first + c0, min(chunk, count - c0))
+        d = diff_fft(x)
+        dp = cmnd(d)
+        dps.append(dp)
+        rms = np.sqrt(np.sum(x * x, axis=1) / N)
+        for i in range(x.shape[0]):
+            if rms[i] == 0:
+                recs.append(SILENT)
+                continue
+            t = pick(dp[i], tmin, tmax, theta)
+            dm, d0, dq = d[i, t - 1], d[i, t], d[i, t + 1]
+            den = 2 * (dm - 2 * d0 + dq)
+            delta = (dm - dq) / den if den > 0 else 0.0
+            delta = min(0.5, max(-0.5, delta))
+            recs.append((t, t + delta, dp[i, t], rms[i]))
+    return recs, np.concatenate(dps) if dps else np.zeros((0, W + 1))
+
+
+def near_ties(dp, taus, tmin, tmax, theta, eps_theta=1e-4, eps_cmp=1e-4):
+    """Frames whose decision a perturbation of d' could change: d' within eps_theta of theta at some tau <= tau*, or within
+    eps_cmp of d'(tau*) at a competing candidate — tau*'s neighbours (the end of the descent) or, where nothing is under
+    theta, any tau of the range (the argmin)."""
+    out = np.zeros(len(taus), dtype=bool)
+    for i, t in enumerate(taus):
+        row = dp[i]
+        if t <= 0:
+            continue
+        seg = row[tmin:t + 1]
+        if np.any(np.abs(seg - theta) < eps_theta):
+            out[i] = True
+            continue
+        if row[t] < theta:
+            nb = [row[t - 1]] if t - 1 >= tmin else []
+            if t + 1 <= tmax:
+                nb.append(row[t + 1])
+            out[i] = any(abs(v - row[t]) < eps_cmp for v in nb)
+        else:
+            others = np.delete(row[tmin:tmax + 1], t - tmin)
+            out[i] = bool(np.any(np.abs(others - row[t]) < eps_cmp))
+    return out
+
+
+# ---- notes and markers (host definitions, same float64 operations as f0_notes.cpp) ----
+def period_note(period, sr):
+    return 24.0 + 12.0 * math.log2(float(sr) / float(period) / 55.0)
+
+
+def _median(vals):
+    s = sorted(vals)
+    k = len(s)
+    return s[k // 2] if k % 2 else (s[k // 2 - 1] + s[k // 2]) / 2.0
+
+
+DEFAULT_PARAMS = dict(threshold=0.15, rms_floor=1e-3, max_jump=0.5, max_dev=0.75, min_frames=8)
+
+
+def detect_notes(track, sr, hop, first=0, **params):
+    """track: records with fields tau, period, aperiodicity, rms (float32 values).  -> list of tuples
+    (start_sample, end_sample, first_frame, frames, note, aperiodicity (f32), spread (f32))."""
+    p = dict(DEFAULT_PARAMS, **params)
+    thr, floor = float(np.float32(p["threshold"])), float(np.float32(p["rms_floor"]))
+    out, run, m = [], [], {}
+
+    def close():
+        if len(run) >= p["min_frames"]:
+            note = _median([m[f] for f in run])
+            ap, spread = 0.0, 0.0
+            for f in run:
+                ap += float(track[f]["aperiodicity"])
+                spread = max(spread, abs(m[f] - note))
+            s, e = run[0], run[-1]
+            out.append(((first + s) * hop, (first + e) * hop, first + s, len(run), note,
+                        float(np.float32(ap / len(run))), float(np.float32(spread))))
+        run.clear()
+
+    for f in range(len(track)):
+        r = track[f]
+        if not (int(r["tau"]) > 0 and float(r["aperiodicity"]) < thr and float(r["rms"]) >= floor):
+            close()
+            continue
+        m[f] = period_note(float(r["period"]), sr)
+        if run and (abs(m[f] - m[f - 1]) > p["max_jump"] or abs(m[f] - _median([m[g] for g in run])) > p["max_dev"]):
+            close()
+        run.append(f)
+    close()
+    return out
+
+
+def snap(note, mask):
+    base = math.floor(note)
+    best, bestd = None, math.inf
+    for k in range(-12, 14):
+        c = base + k
+        if mask and not (mask >> (c % 12)) & 1:
+            continue
+        d = abs(c - note)
+        if d < bestd:
+            best, bestd = float(c), d
+    return best
+
+
+def correction_markers(notes, strength=1.0, scale_mask=0):
+    out = []
+    for n in notes:
+        start, end, note = int(n[0]), int(n[1]), float(n[4])
+        b = strength * (snap(note, scale_mask) - note)
+        out += [(start, note, 0.0, b), (end, note, 0.0, b)]
+    return out
