@@ -388,6 +388,9 @@ void mx_minmax_range(const float *host_wav, int64_t n, const float *picks, const
  *   tau* = the first tau in range with d' < threshold, then forward while d'(tau+1) < d'(tau) (tau+1 <= tau_max);
  *   none under threshold: the argmin of d' over the range (lowest tau on ties);
  *   period = tau* + parabolic offset on d at tau*-1, tau*, tau*+1 (clamped to +-1/2, 0 if the curvature is <= 0).
+ * A frame is silent exactly when its samples are all zero.  The level does not change tau, period or aperiodicity: the
+ * kernel scales each frame by a power of two to a fixed binade first (records are bit for bit the same for 2^k x
+ * wherever 2^k x is exact in f32, subnormal samples included), and rms scales with it.
  * Defaults fmin = 55, fmax = 1760 Hz (notes 24..84), threshold 0.15.  Note law (mx_bin_note's):
  * note = 24 + 12*log2(sr / period / 55). */
 typedef struct mx_f0 {

@@ -11,9 +11,16 @@
 //      d'(tau+1) < d'(tau); none under theta: argmin of d' over the range, ties to the smallest tau
 //   5. parabolic refinement on d at tau*-1, tau*, tau*+1: delta = (d- - d+) / (2 (d- - 2 d0 + d+)) clamped to
 //      [-1/2, 1/2], 0 where the denominator is <= 0
-//   6. mx_f0 {tau*, tau* + delta, d'(tau*), sqrt(sum_{j<N} x_j^2 / N)}; rms == 0: {0, 0, 1, 0}
+//   6. mx_f0 {tau*, tau* + delta, d'(tau*), sqrt(sum_{j<N} x_j^2 / N)}; rms == 0 (every x_j == 0): {0, 0, 1, 0}
 //
 // One workgroup (Plan<4096,16>: 128 threads, two wavefronts) walks a run of consecutive frames; per frame:
+//   the level: x is scaled by 2^-s so that max_j |x_j| lands in [1, 2) (s from the block maximum of the magnitude bits;
+//   s = 0 for a frame of zeros or one holding Inf / NaN).  Scaling by a power of two is exact and commutes with every
+//   f32 operation below barring under- and overflow, which the fixed binade keeps away: the sum of x^2 lies in
+//   [1, 2^14), so a frame's level alone no longer squares its samples to 0 or subnormals (a quiet frame reported
+//   silent, d without precision) nor overflows its sums.  A frame is silent exactly when its samples are all zero;
+//   tau, period and d' do not depend on the level (2^k x gives the same bits while it is exact in f32); rms is
+//   ldexp(rms of the scaled frame, s).  The maximum is reduced at the end of the previous frame, under its last barrier;
 //   forward transform of a = x[0:W] zero-padded and of x (stft_core.h's three passes + the real-FFT split, post_cplx),
 //   P = conj(A) X in registers, P to LDS in bin order, the inverse split (E + i O from P[c], P[M-c]), the same three
 //   passes on its conjugate = the N-point real inverse: r(2m) + i r(2m+1) = conj(out[m]) / (8M) (the split leaves
@@ -58,6 +65,25 @@ __device__ __forceinline__ float wave_scan_addf(float x) {
   MX_SCAN_STEP(0x143, 0xc)
 #undef MX_SCAN_STEP
   return x;
+}
+
+// max |x| over the thread's 32 samples and then the wavefront, as float bits (|x| orders as its bits; NaN above Inf)
+__device__ __forceinline__ unsigned wave_absmax_bits(const cpx (&xr)[FP::E]) {
+  unsigned m = 0;
+#pragma unroll
+  for (int e = 0; e < FP::E; ++e) {
+    const unsigned a = __float_as_uint(xr[e].x) & 0x7fffffffu, b = __float_as_uint(xr[e].y) & 0x7fffffffu;
+    m = m > a ? m : a;
+    m = m > b ? m : b;
+  }
+  return wave_reduce_u32<true>(m);
+}
+
+// s with 2^s <= |x| < 2^(s+1) for the magnitude bits m of a finite non-zero |x|; 0 for 0, Inf and NaN
+__device__ __forceinline__ int level_exp(unsigned m) {
+  if (m == 0 || m >= 0x7f800000u) return 0;
+  if (m >= 0x00800000u) return (int)(m >> 23) - 127;
+  return -118 - __builtin_clz(m);  // subnormal: m 2^-149, top bit 31 - clz(m)
 }
 
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k) {
@@ -132,6 +158,7 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
   __shared__ float sq[kSqLen];                                    // x^2, then its exclusive prefix sums; then d'
   __shared__ float wtot[2];                                       // a scan's first-wavefront total
   __shared__ float s_tot;                                         // sum_{j<N} x_j^2
+  __shared__ unsigned s_max[2];                                   // the next frame's max |x| bits, per wavefront
   __shared__ unsigned long long red[3][2];
   float *const dd = reinterpret_cast<float *>(img);
   const int t_ = threadIdx.x;
@@ -163,12 +190,24 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
   const float *const base = a.audio + MX_AUDIO_PAD - kF0W;
   cpx xr[P::E];
   load_raw<P, false>(t_, xr, base + (a.first_frame + f0) * (int64_t)a.hop);
+  {
+    const unsigned m = wave_absmax_bits(xr);
+    if (lane == 0) s_max[t_ >> 6] = m;
+  }
+  __syncthreads();
   const float theta = a.threshold;
   const int tmin = a.tau_min, tmax = a.tau_max;
 
   for (int64_t f = f0; f < f1; ++f) {
     int t = t_;
     asm volatile("" : "+v"(t));
+    // the level: max |x| in [1, 2) (exact)
+    const int lv = __builtin_amdgcn_readfirstlane(level_exp(s_max[0] > s_max[1] ? s_max[0] : s_max[1]));
+#pragma unroll
+    for (int e = 0; e < P::E; ++e) {
+      xr[e].x = __builtin_ldexpf(xr[e].x, -lv);
+      xr[e].y = __builtin_ldexpf(xr[e].y, -lv);
+    }
     // x^2 in sample order (the prefix sums read them after the first transform's barriers)
 #pragma unroll
     for (int e = 0; e < P::E; ++e) {
@@ -311,11 +350,15 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
         r.tau = tau_s;
         r.period = (float)tau_s + delta;
         r.aperiodicity = sq[dd_idx(tau_s)];
-        r.rms = __builtin_sqrtf(etot * (1.0f / kF0N));
+        r.rms = __builtin_ldexpf(__builtin_sqrtf(etot * (1.0f / kF0N)), lv);
       }
       a.out[f] = r;
     }
-    __syncthreads();  // the images are read: the next frame may write them
+    if (f + 1 < f1) {  // the next frame's level (its samples have long arrived)
+      const unsigned m = wave_absmax_bits(xr);
+      if (lane == 0) s_max[t >> 6] = m;
+    }
+    __syncthreads();  // the images are read: the next frame may write them; s_max is written
   }
 }
 

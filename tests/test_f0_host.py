@@ -1,6 +1,7 @@
 """The YIN tracker's host side (no GPU): notes and correction markers against their Python restatement (tests/yin_ref.py),
 marker properties, argument errors, the f64 reference itself, and the kernel's resources / hand-issued LDS reads."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -220,3 +221,20 @@ def test_f0_kernel_lds_reads_are_covered_by_their_waits(tmp_path):
     assert aud.returncode == 0, aud.stdout[-3000:]
     m = re.fullmatch(r"(\d+) kernel\(s\) audited, 0 finding\(s\)", aud.stdout.splitlines()[-1])
     assert m and int(m.group(1)) >= 1, aud.stdout[-500:]
+
+
+def test_reference_is_scale_invariant():
+    """The scale property the GPU suite pins bit for bit belongs to the definition: 2^k x gives the same tau, period and
+    aperiodicity and 2^k times the rms, for every k with 2^k x exact in f32."""
+    i = np.arange(6000)
+    w = Y.pcm16(0.45 * np.sin(2 * np.pi * 196.0 * i / SR) + 0.1 * np.sin(2 * np.pi * 392.0 * i / SR)
+                + 1e-3 * np.random.default_rng(5).uniform(-1, 1, len(i)))
+    ks = Y.exact_scales(w)
+    assert ks[0] <= -130 and ks[-1] >= 120 and ks == list(range(ks[0], ks[-1] + 1))
+    ref, _ = Y.track(w, SR)
+    assert all(r[0] > 0 for r in ref)
+    for k in ks:
+        got, _ = Y.track(np.ldexp(w, k), SR)
+        assert [r[0] for r in got] == [r[0] for r in ref], k
+        for g, r in zip(got, ref):
+            assert g[1] == r[1] and g[2] == r[2] and g[3] == math.ldexp(r[3], k), k

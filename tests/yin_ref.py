@@ -3,6 +3,8 @@ include/melonix_amd.h, f0_kernels.hip).  Test-side only: the product never impor
 
 track()          d through float64 FFTs and prefix sums (cross-checked against the literal double sum of step 1 by the
                  CPU suite); also returns d' so that the GPU tests can tell near-ties from disagreements
+check_parity()   the GPU tests' comparison of a kernel track with track()'s
+pcm16(), exact_scales()  test signals for the scale property (2^k x exact in f32)
 detect_notes()   the same loop as f0_notes.cpp, in the same order of float64 operations (math.log2 = the C library's
                  log2): notes come out with equal doubles
 correction_markers()
@@ -114,6 +116,69 @@ def near_ties(dp, taus, tmin, tmax, theta, eps_theta=1e-4, eps_cmp=1e-4):
             others = np.delete(row[tmin:tmax + 1], t - tmin)
             out[i] = bool(np.any(np.abs(others - row[t]) < eps_cmp))
     return out
+
+
+def pcm16(w):
+    """w rounded to 16-bit PCM values m / 32768 (f32)."""
+    return (np.round(np.asarray(w, np.float64) * 32768.0) / 32768.0).astype(np.float32)
+
+
+def exact_scales(w, lo=-160, hi=140):
+    """The k in [lo, hi) for which 2^k w is exact in f32 (finite, and scales back to w)."""
+    ks = []
+    with np.errstate(over="ignore", under="ignore"):
+        for k in range(lo, hi):
+            y = np.ldexp(w, k)
+            if np.isfinite(y).all() and (np.ldexp(y, -k) == w).all():
+                ks.append(k)
+    return ks
+
+
+REC_DTYPE = [("tau", "<i4"), ("period", "<f8"), ("aperiodicity", "<f8"), ("rms", "<f8")]
+FLT_MIN = 2.0 ** -126
+
+
+def check_parity(got, recs, dp, tmin, tmax, theta, label, eps=1e-4, cents=1.0, ap_abs=1e-4, ap_rel=1e-3, rms_rel=1e-5,
+                 rms_floor=1e-30, rms_sub_abs=0.0, check_excused=False):
+    """Asserts a kernel track (F0_DTYPE) against track()'s (recs, dp) and prints one summary line.  Silent frames are
+    the reference's (rms == 0) and no others; tau is equal except on near-ties (eps: near_ties' eps_theta and eps_cmp);
+    where it is equal the period is within `cents` and the aperiodicity within ap_abs + ap_rel * ref; rms is within
+    rms_rel relative to max(ref, rms_floor), plus rms_sub_abs absolute where the reference's rms is below FLT_MIN (the f32
+    field cannot hold more there).  check_excused: a frame excused as a near-tie must be one the reference's own d'
+    nearly supports: the kernel's tau lies in range and its d' is within eps of the reference's d'(tau*), or d' is within
+    eps of theta at some tau up to the later of the two.  -> (frames, frames whose tau differs on an excused near-tie)."""
+    ref = np.array(recs, dtype=REC_DTYPE)
+    assert len(got) == len(ref), label
+    silent = ref["rms"] == 0
+    loud = ~silent
+    assert (got["tau"][silent] == 0).all() and (got["period"][silent] == 0).all(), label
+    assert (got["aperiodicity"][silent] == 1).all() and (got["rms"][silent] == 0).all(), label
+    assert (got["tau"][loud] > 0).all(), f"{label}: frames reported silent {np.nonzero(loud & (got['tau'] == 0))[0][:10]}"
+    ties = near_ties(dp, ref["tau"], tmin, tmax, theta, eps_theta=eps, eps_cmp=eps)
+    same = got["tau"] == ref["tau"]
+    bad = ~same & ~ties
+    excused = ~same & ties
+    ap_err = np.abs(got["aperiodicity"] - ref["aperiodicity"])[same & loud]
+    rms_err = np.abs(got["rms"] - ref["rms"])[loud]
+    rms_den = np.maximum(ref["rms"], rms_floor)[loud]
+    rms_rel_err = rms_err / rms_den
+    c = np.abs(1200 * np.log2(got["period"][same & loud] / ref["period"][same & loud]))
+    print(f"f0 parity {label}: {len(got)} frames, tau differs on {int((~same).sum())} "
+          f"(near-tie frames {int(ties.sum())}), "
+          f"period max {c.max() if len(c) else 0:.3g} cents, aperiodicity max err {ap_err.max() if len(ap_err) else 0:.2e}, "
+          f"rms max rel {rms_rel_err.max() if len(rms_rel_err) else 0:.2e}")
+    assert not bad.any(), f"{label}: tau differs outside near-ties at frames {np.nonzero(bad)[0][:10]}"
+    if check_excused:
+        for i in np.nonzero(excused)[0]:
+            g, t, row = int(got["tau"][i]), int(ref["tau"][i]), dp[i]
+            assert tmin <= g <= tmax and (abs(row[g] - row[t]) < eps
+                                          or np.any(np.abs(row[tmin:max(g, t) + 1] - theta) < eps)), \
+                f"{label}: frame {i} tau {g} (d' {row[g]:.6g}) against the reference's {t} (d' {row[t]:.6g})"
+    assert (c <= cents).all(), label
+    assert (ap_err <= ap_abs + ap_rel * ref["aperiodicity"][same & loud]).all(), label
+    slack = np.where(ref["rms"] < FLT_MIN, rms_sub_abs, 0.0)[loud]
+    assert (rms_rel_err <= rms_rel + slack / rms_den).all(), label
+    return len(got), int(excused.sum())
 
 
 # ---- notes and markers (host definitions, same float64 operations as f0_notes.cpp) ----
