@@ -40,7 +40,9 @@ UNITS = [
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
+    ("capi_pv_arena.cpp", "hip", []),
     ("capi_pv.cpp", "hip", []),
+    ("capi_pv_shard.cpp", "hip", []),
     ("capi_resynth.cpp", "hip", []),
     ("capi_pyramid.cpp", "hip", []),
     ("capi_f0.cpp", "hip", []),
@@ -50,7 +52,7 @@ UNITS = [
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 HEADERS = ["kernels.h", "colormap_core.h", "stft_kernel_impl.h", "stft_core.h", "pk_math.h", "stft_tables.h", "stft_consts.inc",
-           "host_logic.h", "capi_internal.h", "f0_notes.h",
+           "host_logic.h", "capi_internal.h", "pv_pipe.h", "f0_notes.h",
            os.path.join("..", "..", "include", "melonix_amd.h")]
 
 

@@ -84,7 +84,34 @@ struct NTables {
   std::vector<float> wext_host;
 };
 
-struct PvPipe;  // capi_pv.cpp: the phase vocoder's bounded work arena, streams and events
+// Device memory a call (or a staged rank job) owns: n elements, freed on every path, and only once `stream` has drained — nothing
+// of ours may still be in flight when it goes.
+template <class T>
+struct DeviceArray {
+  T *p = nullptr;
+  size_t n = 0;
+  hipStream_t stream = nullptr;
+  DeviceArray() = default;
+  DeviceArray(const DeviceArray &) = delete;
+  DeviceArray &operator=(const DeviceArray &) = delete;
+  ~DeviceArray() { reset(); }
+  void reset() {
+    if (!p) return;
+    hipStreamSynchronize(stream);
+    hipFree(p);
+    p = nullptr;
+  }
+  hipError_t alloc(hipStream_t s, size_t count) {  // (count 0: no buffer)
+    reset();
+    stream = s;
+    n = count;
+    return count ? hipMalloc(&p, count * sizeof(T)) : hipSuccess;
+  }
+  // into host memory (may be null: nothing), queued on the stream behind what wrote it
+  hipError_t download(T *host) const { return p && host ? hipMemcpyAsync(host, p, n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess; }
+};
+
+struct PvPipe;  // pv_pipe.h: the phase vocoder's work arena, streams and events
 
 }  // namespace mx
 
@@ -111,7 +138,7 @@ struct mx_ctx {
   // device work buffers of the grain chain (mx_grains_dev): the two predicate bitmaps, the rank tables, the lifting
   // tables — kept between calls like the staging buffers (guarded by zc_mu)
   Stage chain[4];
-  // the phase vocoder's bounded work arena, second stream and events (capi_pv.cpp): built on first use, kept for the next
+  // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;
   mx::PvPipe *pv = nullptr;
@@ -145,8 +172,26 @@ int64_t chunk_frames(int N);
 hipError_t stage_get(mx_ctx *ctx, int i, size_t bytes, void **out);
 // Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.
 void stage_trim(mx_ctx *ctx);
-// gives the phase vocoder's arena, stream and events back (capi_pv.cpp); the caller holds ctx->pv_mu or owns the context
+// gives the phase vocoder's arena, stream and events back (capi_pv_arena.cpp); the caller holds ctx->pv_mu or owns the context
 // outright (mx_ctx_destroy)
 void pv_release(mx_ctx *ctx);
+
+// The host-pointer form of a PCM entry point: `to_device(d_f32, d_i16)`, its device form, fills device buffers of n samples in the
+// formats the caller asked for; they reach the caller's buffers only if it succeeded.
+template <class F>
+int pcm_to_host(mx_ctx *ctx, int64_t n, float *f_out, int16_t *i_out, F &&to_device) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  DeviceArray<float> f;
+  DeviceArray<int16_t> i;
+  hipError_t e = f.alloc(ctx->stream, f_out ? (size_t)n : 0);
+  if (e == hipSuccess) e = i.alloc(ctx->stream, i_out ? (size_t)n : 0);
+  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device PCM buffers: %s", hipGetErrorString(e));
+  const int rc = to_device(f.p, i.p);
+  if (rc) return rc;
+  e = f.download(f_out);
+  if (e == hipSuccess) e = i.download(i_out);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "PCM download: %s", hipGetErrorString(e));
+}
 
 }  // namespace mx

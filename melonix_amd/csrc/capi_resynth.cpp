@@ -265,40 +265,35 @@ int mx_resynth_dev(mx_ctx *ctx, const mx_audio *a, const mx_step *d_steps, int64
 }  // extern "C"
 
 namespace {
-// The device half of mx_resynth: checks the schedule's invariants, uploads it, allocates the requested PCM buffers and
-// runs the kernel (asynchronously on the context's stream).  The caller downloads and frees.
-struct ResynthBuffers {
-  mx_step *d_steps = nullptr;
-  float *d_f = nullptr;
-  int16_t *d_i = nullptr;
-  ~ResynthBuffers() { hipFree(d_steps); hipFree(d_f); hipFree(d_i); }
-};
-int resynth_to_device(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int64_t nsteps, int64_t nsamples, bool want_f,
-                      bool want_i, ResynthBuffers &b) {
+// Checks a schedule's invariants against the audio; *covered: the samples its steps emit.
+int resynth_check(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int64_t nsteps, int64_t nsamples, int64_t *covered) {
   if (!ctx || !a || nsteps < 0 || nsamples < 0 || (nsteps > 0 && !steps)) return fail(MX_ERR_INVALID, "bad argument");
-  int64_t covered = 0;
+  *covered = 0;
   for (int64_t i = 0; i < nsteps; ++i) {
     const mx_step &s = steps[i];
-    if (s.out_offset != covered || s.sz < 0 || s.grain_start < 0 || s.grain_len <= 0 ||
+    if (s.out_offset != *covered || s.sz < 0 || s.grain_start < 0 || s.grain_len <= 0 ||
         (int64_t)s.grain_start + s.grain_len > a->n)
       return fail(MX_ERR_INVALID, "step %lld is inconsistent with the schedule invariants", (long long)i);
-    covered += s.sz;
+    *covered += s.sz;
   }
-  if (covered > nsamples) return fail(MX_ERR_INVALID, "steps emit %lld samples, nsamples is %lld", (long long)covered,
-                                      (long long)nsamples);
+  if (*covered > nsamples) return fail(MX_ERR_INVALID, "steps emit %lld samples, nsamples is %lld", (long long)*covered,
+                                       (long long)nsamples);
+  return MX_OK;
+}
+// The device half of mx_resynth / mx_resynth_to_wav behind resynth_check: uploads the schedule into d_steps and runs the kernel
+// into the device PCM (either may be null), asynchronously on the context's stream.
+int resynth_to_device(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int64_t nsteps, int64_t nsamples, int64_t covered,
+                      DeviceArray<mx_step> &d_steps, float *d_f, int16_t *d_i) {
   HIP_TRY(hipSetDevice(ctx->device));
-  hipError_t e = hipSuccess;
-  if (nsteps) e = hipMalloc(&b.d_steps, (size_t)nsteps * sizeof(mx_step));
-  if (e == hipSuccess && want_f && nsamples) e = hipMalloc(&b.d_f, (size_t)nsamples * sizeof(float));
-  if (e == hipSuccess && want_i && nsamples) e = hipMalloc(&b.d_i, (size_t)nsamples * sizeof(int16_t));
+  hipError_t e = d_steps.alloc(ctx->stream, (size_t)nsteps);
   if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device buffers: %s", hipGetErrorString(e));
   if (nsteps)
-    if ((e = hipMemcpyAsync(b.d_steps, steps, (size_t)nsteps * sizeof(mx_step), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(d_steps.p, steps, (size_t)nsteps * sizeof(mx_step), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
       return fail(MX_ERR_DEVICE, "schedule upload: %s", hipGetErrorString(e));
   // anything between the covered run and the tail is zero by definition
-  if (b.d_f) hipMemsetAsync(b.d_f + covered, 0, (size_t)(nsamples - covered) * sizeof(float), ctx->stream);
-  if (b.d_i) hipMemsetAsync(b.d_i + covered, 0, (size_t)(nsamples - covered) * sizeof(int16_t), ctx->stream);
-  return mx_resynth_dev(ctx, a, b.d_steps, nsteps, nsamples, b.d_f, b.d_i);
+  if (d_f) hipMemsetAsync(d_f + covered, 0, (size_t)(nsamples - covered) * sizeof(float), ctx->stream);
+  if (d_i) hipMemsetAsync(d_i + covered, 0, (size_t)(nsamples - covered) * sizeof(int16_t), ctx->stream);
+  return mx_resynth_dev(ctx, a, d_steps.p, nsteps, nsamples, d_f, d_i);
 }
 }  // namespace
 
@@ -307,19 +302,12 @@ extern "C" {
 int mx_resynth(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int64_t nsteps, int64_t nsamples,
                float *pcm_f32_out, int16_t *pcm_i16_out) {
   return mx_guard([&]() -> int {
-    ResynthBuffers b;
-    int rc = resynth_to_device(ctx, a, steps, nsteps, nsamples, pcm_f32_out != nullptr, pcm_i16_out != nullptr, b);
-    if (rc == MX_OK) {
-      hipError_t e = hipSuccess;
-      if (b.d_f) e = hipMemcpyAsync(pcm_f32_out, b.d_f, (size_t)nsamples * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess && b.d_i)
-        e = hipMemcpyAsync(pcm_i16_out, b.d_i, (size_t)nsamples * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "PCM download: %s", hipGetErrorString(e));
-    } else if (ctx) {
-      hipStreamSynchronize(ctx->stream);  // nothing of ours may still be in flight when the buffers go
-    }
-    return rc;
+    int64_t covered = 0;
+    if (const int rc = resynth_check(ctx, a, steps, nsteps, nsamples, &covered)) return rc;
+    DeviceArray<mx_step> d_steps;
+    return pcm_to_host(ctx, nsamples, pcm_f32_out, pcm_i16_out, [&](float *d_f, int16_t *d_i) {
+      return resynth_to_device(ctx, a, steps, nsteps, nsamples, covered, d_steps, d_f, d_i);
+    });
   });
 }
 
@@ -327,21 +315,24 @@ int mx_resynth_to_wav(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int6
                       const char *path, int sampleRate, int strict_reference_header) {
   return mx_guard([&]() -> int {
     if (!ctx || !a || !path) return fail(MX_ERR_INVALID, "bad argument");
+    int64_t covered = 0;
+    int rc = resynth_check(ctx, a, steps, nsteps, nsamples, &covered);
+    if (rc) return rc;
     // The PCM never exists as one host buffer: it leaves the device in 16 MiB pieces through two pinned landing
     // buffers, and each piece goes into the file while the next one is in flight.
-    ResynthBuffers b;
-    int rc = resynth_to_device(ctx, a, steps, nsteps, nsamples, false, true, b);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DeviceArray<mx_step> d_steps;
+    DeviceArray<int16_t> pcm;
+    hipError_t e = pcm.alloc(ctx->stream, (size_t)nsamples);
+    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device buffers: %s", hipGetErrorString(e));
+    rc = resynth_to_device(ctx, a, steps, nsteps, nsamples, covered, d_steps, nullptr, pcm.p);
     WavStream ws;
     if (rc == MX_OK && wav_begin(ws, path, nsamples, sampleRate, strict_reference_header != 0) != MX_OK)
       rc = fail(MX_ERR_IO, "cannot write %s", path);
-    if (rc != MX_OK) {
-      hipStreamSynchronize(ctx->stream);  // nothing of ours may still be in flight when the buffers go
-      return rc;
-    }
+    if (rc != MX_OK) return rc;
     constexpr int64_t kPiece = 8 << 20;  // samples
     int16_t *land[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
-    hipError_t e = hipSuccess;
     const int64_t pieces = (nsamples + kPiece - 1) / kPiece;
     for (int i = 0; i < 2 && e == hipSuccess && i < pieces; ++i) {
       e = hipHostMalloc((void **)&land[i], (size_t)std::min<int64_t>(kPiece, nsamples) * sizeof(int16_t), hipHostMallocDefault);
@@ -350,7 +341,7 @@ int mx_resynth_to_wav(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int6
     auto piece_len = [&](int64_t k) { return std::min<int64_t>(kPiece, nsamples - k * kPiece); };
     for (int64_t k = 0; k <= pieces && e == hipSuccess; ++k) {
       if (k < pieces) {
-        e = hipMemcpyAsync(land[k & 1], b.d_i + k * kPiece, (size_t)piece_len(k) * sizeof(int16_t), hipMemcpyDeviceToHost,
+        e = hipMemcpyAsync(land[k & 1], pcm.p + k * kPiece, (size_t)piece_len(k) * sizeof(int16_t), hipMemcpyDeviceToHost,
                            ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(ev[k & 1], ctx->stream);
       }
