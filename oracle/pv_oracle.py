@@ -70,19 +70,30 @@ def window():
     return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(N) / N)
 
 
+# The frame centres the product accepts: a_f in [-AUDIO_PAD/2, n + AUDIO_PAD/2] (include/melonix_amd.h MX_AUDIO_PAD; a marker
+# plan reaching further is refused with "outside the audio").  Constant-ratio plans stay inside [0, n + Hs).
+AUDIO_PAD = 32768
+
+
 def analysis(x, a, chunk=256):
-    """-> mags (F, N/2) f64 = |X|/N, phases (F, N/2) uint32 turns."""
+    """-> mags (F, N/2) f64 = |X|/N, phases (F, N/2) uint32 turns.  Frames centred anywhere in [-AUDIO_PAD/2, n + AUDIO_PAD/2]
+    read zeros outside the file; a centre outside that range raises ValueError."""
     x = np.asarray(x, dtype=np.float64)
     n = len(x)
     w = window()
+    a = np.asarray(a, dtype=np.int64)
     F = len(a)
+    lo, hi = -(AUDIO_PAD // 2), n + AUDIO_PAD // 2
+    if F and (a.min() < lo or a.max() > hi):
+        raise ValueError(f"frame centres [{int(a.min())}, {int(a.max())}] leave the accepted range [{lo}, {hi}]")
     mags = np.empty((F, N // 2))
     ph = np.empty((F, N // 2), dtype=np.uint32)
-    xp = np.concatenate([np.zeros(N), x, np.zeros(N + HS)])  # zeros outside the file
+    lead = AUDIO_PAD // 2 + N // 2  # zeros outside the file: index a_f - N/2 + j + lead lies in [0, n + 2 lead)
+    xp = np.concatenate([np.zeros(lead), x, np.zeros(lead)])
     j = np.arange(N)
     for f0 in range(0, F, chunk):
         af = a[f0:f0 + chunk]
-        idx = af[:, None] - N // 2 + j[None, :] + N  # a frame never leaves [-N/2, n + Hs + N/2)
+        idx = af[:, None] - N // 2 + j[None, :] + lead
         fr = xp[idx] * w[None, :]
         X = np.fft.rfft(fr, axis=1)[:, : N // 2] / N
         mags[f0:f0 + chunk] = np.abs(X)

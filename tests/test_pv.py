@@ -755,6 +755,93 @@ def test_marker_plan_equals_oracle(mxlib, pv, mk):
     assert i0[-1] == n_out and (np.diff(i0) >= 0).all() and tf[-1] >= (n_out - 1) / SR
 
 
+def test_oracle_reads_zeros_around_the_file_and_refuses_beyond(mxlib, pv):
+    """The oracle's analysis covers every frame centre the product accepts, a_f in [-MX_AUDIO_PAD/2, n + MX_AUDIO_PAD/2]: a
+    frame there that does not reach the file is exactly zero (a negative index must not wrap around into the end of the file),
+    a frame that does reach it sees it, and a centre one sample outside the range raises."""
+    n = 3 * SR
+    x = accum_sweep(n).astype(np.float64)
+    lo, hi = -mxlib.MX_AUDIO_PAD // 2, n + mxlib.MX_AUDIO_PAD // 2
+    mags, _ = pv.analysis(x, np.array([-10000]))
+    assert not mags.any(), float(mags.max())
+    mags, ph = pv.analysis(x, np.array([lo, hi, -6401, -5000, n + 2048]))
+    assert not mags.any() and not ph.any()
+    assert pv.AUDIO_PAD == mxlib.MX_AUDIO_PAD
+    seen, _ = pv.analysis(x, np.array([0, n - 1, 100]))
+    assert (seen.max(axis=1) > 1e-3).all()
+    for bad in ([lo - 1], [hi + 1], [0, lo - 1, 5]):
+        with pytest.raises(ValueError):
+            pv.analysis(x, np.array(bad))
+    # a plan whose first segment runs backward to -12000: 52 frames below -6400, all silent in the oracle's render
+    mk = [(-12000, 0, 0.6, 0.0), (n - 1, 0, 0, 0)]
+    _, apos, _, _, _ = pv.marker_plan(n, SR, mk)
+    assert (apos < -6400).sum() == 52 and apos.min() >= lo
+    m, _ = pv.analysis(x, apos[apos < -6400])
+    assert not m.any()
+
+
+def _same_plan(got, ref, what):
+    n_out, apos, tf, rf, i0 = got
+    on, oa, otf, orf, oi0 = ref
+    assert n_out == on and np.array_equal(apos, oa) and np.array_equal(i0, oi0), what
+    assert np.array_equal(tf, otf) and np.array_equal(rf, orf), what
+    assert i0[-1] == n_out and (np.diff(i0) >= 0).all() and len(i0) == len(apos) + 1, what
+
+
+def test_marker_plan_equals_oracle_random_warps(mxlib, pv):
+    """240 seeded marker sets (tests/pv_markers.py): markers before 0 and beyond n, backward segments, stalls and 20-100x
+    stretches, bends anywhere in [-48, 48] incl. -48 -> +48 at one sample, last markers before n - 1, files of 1 sample to 3 s.
+    The host plan equals the oracle's field for field, exactly; the sets must reach every one of those shapes."""
+    import collections
+    import pv_markers
+    seen = collections.Counter()
+    for i, (n, mk) in enumerate(pv_markers.marker_sets(20261016, 240, (1, 3 * SR))):
+        got = mxlib.pv_plan(n, SR, mk)
+        _same_plan(got, pv.marker_plan(n, SR, mk), (i, n, mk))
+        n_out, apos, tf, rf, i0 = got
+        assert mxlib._capi.lib().mx_pv_render_length(n, SR, mxlib._capi.markers_array(mk), len(mk)) == n_out
+        h = np.diff(apos)
+        seen["n_out = 0"] += n_out == 0
+        seen["one frame"] += len(apos) == 1
+        seen["marker < 0"] += any(m[0] < 0 for m in mk)
+        seen["marker > n"] += any(m[0] > n for m in mk)
+        seen["last marker < n - 1"] += bool(mk) and mk[-1][0] < n - 1
+        seen["a_f < -6400"] += bool((apos < -6400).any())
+        seen["a_f < -PAD/2"] += bool((apos < -pv.AUDIO_PAD // 2).any())
+        seen["a_f >= n"] += bool((apos >= n).any())
+        seen["stall"] += bool((h == 0).any())
+        seen["backward"] += bool((h < 0).any())
+        seen["h > N"] += bool((h > pv.N).any())
+        seen["r = 16"] += bool((rf == 16.0).any())
+        seen["r = 1/16"] += bool((rf == 1.0 / 16.0).any())
+        seen["-48 -> +48"] += any(a[0] == b[0] and a[3] == -48 and b[3] == 48 for a, b in zip(mk, mk[1:]))
+    assert min(seen.values()) >= 2 and len(seen) == 14, dict(seen)
+
+
+def test_marker_plan_refuses_what_it_cannot_render(mxlib):
+    """Bends outside [-48, 48] where a frame reads them, non-finite dTime or bend, unsorted markers, a bad rate: MX_ERR_INVALID
+    from the plan and from the render's length, no crash.  (The constant-ratio range: mx_pv_shard_frames, which needs no device.)"""
+    from melonix_amd import _capi
+    n = SR
+    nan, inf = float("nan"), float("inf")
+    bad = [([(1000, 0, 0, 48.5), (40000, 0, 0, 48.5)], SR), ([(1000, 0, 0, -60.0), (2000, 0, 0, 0)], SR),
+           ([(20000, 0, 0, 48.0001), (30000, 0, 0, 48.0001)], SR),
+           ([(1000, 0, nan, 0)], SR), ([(1000, 0, 0, nan)], SR), ([(1000, 0, inf, 0)], SR), ([(1000, 0, -inf, 0)], SR),
+           ([(1000, 0, 0, inf)], SR), ([(1000, 0, 0, 0), (2000, 0, 0, -inf)], SR),
+           ([(2000, 0, 0, 0), (1000, 0, 0, 0)], SR), ([(1000, 0, 0, 0)], 0), ([(1000, 0, 0, 0)], -SR)]
+    for mk, sr in bad:
+        with pytest.raises(mxlib.MxError) as err:
+            mxlib.pv_plan(n, sr, mk)
+        assert err.value.code == _capi.MX_ERR_INVALID, (mk, sr)
+        assert _capi.lib().mx_pv_render_length(n, sr, _capi.markers_array(mk), len(mk)) == _capi.MX_ERR_INVALID, (mk, sr)
+    mxlib.pv_plan(n, SR, [(1000, 0, 0, 48.0), (40000, 0, 0, -48.0)])  # the ends of the range themselves are fine
+    for st in (48.0001, -48.0001, nan, inf, -inf, 1e308):
+        with pytest.raises(mxlib.MxError):
+            mxlib.pv_shard_frames(10 * SR, st, 0, 1)
+    for st in (48.0, -48.0):
+        assert mxlib.pv_shard_frames(10 * SR, st, 0, 1)[:2] == (0, int(np.ceil(10 * SR * 2.0 ** (st / 12) / 256)) + 1)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mk", MARKER_SETS)
 def test_gpu_marker_render_matches_oracle(gpu_ctx, pv, mk):
