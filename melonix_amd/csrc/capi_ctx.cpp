@@ -150,28 +150,10 @@ int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_
 // frames per host-staging chunk: keep the device staging buffer <= ~1 GiB
 int64_t chunk_frames(int N) { return std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)(N / 2) * 4)); }
 
-// Staging slot `i` with room for `bytes` (contents undefined).  Caller holds ctx->stage_mu.
-hipError_t stage_get(mx_ctx *ctx, int i, size_t bytes, void **out) {
-  mx_ctx::Stage &st = ctx->stage[i];
-  if (st.cap < bytes) {
-    if (st.p) hipFree(st.p);
-    st.p = nullptr;
-    st.cap = 0;
-    const hipError_t e = hipMalloc(&st.p, bytes);
-    if (e != hipSuccess) return e;
-    st.cap = bytes;
-  }
-  *out = st.p;
-  return hipSuccess;
-}
 // Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.
 void stage_trim(mx_ctx *ctx) {
   for (auto &st : ctx->stage)
-    if (st.cap > ((size_t)256 << 20)) {
-      hipFree(st.p);
-      st.p = nullptr;
-      st.cap = 0;
-    }
+    if (st.cap > ((size_t)256 << 20)) st.drop();
 }
 
 }  // namespace mx
@@ -227,8 +209,8 @@ void mx_ctx_destroy(mx_ctx *ctx) {
       hipFree(kv.second.wext);
     }
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
-    for (auto &st : ctx->stage) hipFree(st.p);
-    for (auto &st : ctx->chain) hipFree(st.p);
+    for (auto &st : ctx->stage) st.drop();
+    for (auto &st : ctx->chain) st.drop();
     pv_release(ctx);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -265,24 +247,18 @@ int mx_ctx_release_scratch(mx_ctx *ctx) {
     HIP_TRY(hipSetDevice(ctx->device));
     {
       std::lock_guard<std::mutex> lk(ctx->stage_mu);
-      for (auto &st : ctx->stage) {
-        hipFree(st.p);
-        st = {};
-      }
+      for (auto &st : ctx->stage) st.drop();
     }
     {
       std::lock_guard<std::mutex> lk(ctx->pv_mu);
       pv_release(ctx);  // (a staged multi-GPU job lives in that arena: it ends here)
       ctx->pv_budget_auto = 0;  // (the automatic budget is taken again from what is free at the next first use)
-    ctx->pv_rec_full = false;
+      ctx->pv_rec_full = false;
     }
     {
       std::lock_guard<std::mutex> lk(ctx->zc_mu);
       ctx->zc_scratch = ZcBitmaps{};
-      for (auto &st : ctx->chain) {
-        hipFree(st.p);
-        st = {};
-      }
+      for (auto &st : ctx->chain) st.drop();
     }
     return MX_OK;
   });

@@ -81,9 +81,9 @@ int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)count * sizeof(mx_f0);
     std::lock_guard<std::mutex> lk(ctx->stage_mu);
-    void *d = nullptr;
-    HIP_TRY(stage_get(ctx, 0, bytes, &d));
-    int rc = f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, static_cast<mx_f0 *>(d));
+    mx_f0 *d = nullptr;
+    HIP_TRY(ctx->stage[kStageMags].get(bytes, &d));  // (no magnitude rows in this call: their buffer holds the records)
+    int rc = f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d);
     if (rc == MX_OK) {
       hipError_t e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -112,13 +112,10 @@ int mx_detect_notes(const mx_f0 *track, int64_t count, int sampleRate, int hop, 
     if (!std::isfinite(p.threshold) || !std::isfinite(p.rms_floor) || !(p.max_jump >= 0.0) || !(p.max_dev >= 0.0))
       return fail(MX_ERR_INVALID, "note parameters must be finite, the deviations >= 0");
     const std::vector<mx_note> v = detect_notes(track, count, sampleRate, hop, first_frame, p);
-    mx_note *buf = nullptr;
-    if (!v.empty()) {
-      buf = static_cast<mx_note *>(std::malloc(v.size() * sizeof(mx_note)));
-      if (!buf) return fail(MX_ERR_NOMEM, "out of host memory");
-      std::memcpy(buf, v.data(), v.size() * sizeof(mx_note));
-    }
-    *notes = buf;
+    HandOver h;
+    if (v.empty()) *notes = nullptr;  // (no notes: no array)
+    else h.add(notes, v.data(), v.size());
+    if (const int rc = h.give()) return rc;
     *nnotes = (int64_t)v.size();
     return MX_OK;
   });

@@ -1,5 +1,8 @@
 // capi_internal.h — what the units of the C-ABI implementation (capi_*.cpp) share: the context and audio handle
-// types, the error slot behind mx_last_error, the per-N table cache.  Not installed; include/melonix_amd.h is the boundary.
+// types, the error slot behind mx_last_error, the per-N table cache, and the sequences written once: the owners of device
+// memory (DeviceArray for a call, GrowBuf for a context), the chunked host-staged loop (staged_batch), the PCM download
+// (pcm_to_host), the arrays handed out for mx_free (HandOver), the MELONIX_TIMING phase clock (PhaseClock).
+// Not installed; include/melonix_amd.h is the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +10,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <chrono>
 #include <map>
@@ -107,8 +111,87 @@ struct DeviceArray {
     n = count;
     return count ? hipMalloc(&p, count * sizeof(T)) : hipSuccess;
   }
-  // into host memory (may be null: nothing), queued on the stream behind what wrote it
-  hipError_t download(T *host) const { return p && host ? hipMemcpyAsync(host, p, n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess; }
+  // the first `count` elements (default: all) into host memory (may be null: nothing), queued on the stream behind what wrote them
+  hipError_t download(T *host, size_t count = SIZE_MAX) const {
+    return p && host ? hipMemcpyAsync(host, p, std::min(count, n) * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess;
+  }
+};
+
+// Device memory a context keeps between calls: grows to the largest request, never shrinks until dropped — a screen-sized
+// batch otherwise spends more time in hipMalloc/hipFree than in the kernel.  The mutex of its array guards it.
+struct GrowBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  void drop() {
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  hipError_t get(size_t bytes, T **out) {  // room for `bytes`, contents undefined
+    if (cap < bytes) {
+      drop();
+      const hipError_t e = hipMalloc(&p, bytes);
+      if (e != hipSuccess) return e;
+      cap = bytes;
+    }
+    *out = static_cast<T *>(p);
+    return hipSuccess;
+  }
+};
+// staging of the host-pointer entry points (mx_ctx::stage, under stage_mu) and work buffers of the grain chain (mx_ctx::chain,
+// under zc_mu): the two predicate bitmaps, the rank tables, the lifting tables
+enum StageSlot { kStageMags, kStagePitch, kStageRanges, kStageTexels, kStageSlots };
+enum ChainSlot { kChainBitmap7, kChainBitmap3, kChainRanks, kChainTables, kChainSlots };
+
+// Arrays handed to the caller, who frees them with mx_free.  add(): a fresh malloc block of n elements (at least one, so an
+// empty result is not a null pointer), copied from src or, src null, left for a download.  give(): every block is there and
+// the caller's pointers are set, or MX_ERR_NOMEM; whatever was not given is freed on every path out.
+class HandOver {
+  void *blk_[4] = {}, *out_[4] = {};
+  int n_ = 0;
+  bool ok_ = true;
+
+ public:
+  HandOver() = default;
+  HandOver(const HandOver &) = delete;
+  HandOver &operator=(const HandOver &) = delete;
+  ~HandOver() {
+    for (int i = 0; i < n_; ++i) free(blk_[i]);
+  }
+  template <class T>
+  T *add(T **out, const T *src, size_t n) {
+    T *p = static_cast<T *>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
+    if (p && src && n) memcpy(p, src, n * sizeof(T));
+    ok_ = ok_ && p;
+    blk_[n_] = p;
+    out_[n_++] = out;
+    return p;
+  }
+  bool ok() const { return ok_; }
+  int give() {
+    if (!ok_) return fail(MX_ERR_NOMEM, "out of host memory");
+    for (int i = 0; i < n_; ++i) memcpy(out_[i], &blk_[i], sizeof(void *));
+    n_ = 0;
+    return MX_OK;
+  }
+};
+
+// MELONIX_TIMING: the phases of one call, for the one line it prints on stderr.  mark() ends a phase; ms(i) is the length of
+// phase i — up to now for the one still running, 0 for one the call never reached.
+class PhaseClock {
+  using clk = std::chrono::steady_clock;
+  clk::time_point t_[6];
+  int n_ = 1;
+
+ public:
+  const bool on = getenv("MELONIX_TIMING") != nullptr;
+  PhaseClock() { t_[0] = clk::now(); }
+  void mark() { t_[n_++] = clk::now(); }
+  double ms(int i) const {
+    if (i >= n_) return 0.;
+    return std::chrono::duration<double, std::milli>((i + 1 < n_ ? t_[i + 1] : clk::now()) - t_[i]).count();
+  }
 };
 
 struct PvPipe;  // pv_pipe.h: the phase vocoder's work arena, streams and events
@@ -127,17 +210,12 @@ struct mx_ctx {
   // pages that are already mapped runs at PCIe rate, a fresh 2 x n/8-byte buffer pays ~3 ms of faults
   std::mutex zc_mu;
   mx::ZcBitmaps zc_scratch;
-  // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*):
-  // grow-only buffers kept between calls — a screen-sized batch otherwise spends more time in
-  // hipMalloc/hipFree than in the kernel.  One host-staged call per context at a time.
+  // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
+  // mx_f0_track), kept between calls.  One host-staged call per context at a time.
   std::mutex stage_mu;
-  struct Stage {
-    void *p = nullptr;
-    size_t cap = 0;
-  } stage[4];
-  // device work buffers of the grain chain (mx_grains_dev): the two predicate bitmaps, the rank tables, the lifting
-  // tables — kept between calls like the staging buffers (guarded by zc_mu)
-  Stage chain[4];
+  mx::GrowBuf stage[mx::kStageSlots];
+  // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)
+  mx::GrowBuf chain[mx::kChainSlots];
   // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;
@@ -168,13 +246,63 @@ int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_
                 int run_length = 0);
 // frames per host-staging chunk: keep the device staging buffer <= ~1 GiB
 int64_t chunk_frames(int N);
-// Staging slot `i` with room for `bytes` (contents undefined).  Caller holds ctx->stage_mu.
-hipError_t stage_get(mx_ctx *ctx, int i, size_t bytes, void **out);
-// Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.
+// Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.  Caller holds ctx->stage_mu.
 void stage_trim(mx_ctx *ctx);
 // gives the phase vocoder's arena, stream and events back (capi_pv_arena.cpp); the caller holds ctx->pv_mu or owns the context
 // outright (mx_ctx_destroy)
 void pv_release(mx_ctx *ctx);
+
+// One host-staged batch: `count` rows of N/2 bins, walked in chunks of chunk_frames(N) rows through the context's staging
+// buffers.  Callers fill it in this order: {N, count, ranges, mags_out, pitch_out, rgb_out, d_rows}, trailing nulls left out.
+struct StagedBatch {
+  int N = 0;
+  int64_t count = 0;
+  const int32_t *ranges = nullptr;  // host (start, end) pairs, uploaded chunk by chunk; null: the call has none
+  float *mags_out = nullptr;        // host outputs, each or null
+  mx_pitch *pitch_out = nullptr;
+  uint8_t *rgb_out = nullptr;
+  float *d_rows = nullptr;  // device rows that stay resident: chunk `done` lands at d_rows + done*N/2, not in a staging buffer
+};
+// The host-pointer form of a row entry point: `run(done, c, d_ranges, d_mags, d_pitch, d_rgb) -> status` queues rows
+// [done, done + c) on the context's stream; a device pointer is null where the batch has no such output.  Each chunk's rows
+// reach the caller's buffers before the next chunk overwrites the staging buffers.
+template <class F>
+int staged_batch(mx_ctx *ctx, const StagedBatch &b, F &&run) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t row = (size_t)(b.N / 2);
+  const int64_t chunk = std::min<int64_t>(b.count, chunk_frames(b.N));
+  float *d_mags = nullptr;
+  mx_pitch *d_pitch = nullptr;
+  int32_t *d_ranges = nullptr;
+  uint8_t *d_rgb = nullptr;
+  std::lock_guard<std::mutex> slk(ctx->stage_mu);
+  hipError_t e = hipSuccess;
+  if (b.mags_out && !b.d_rows) e = ctx->stage[kStageMags].get((size_t)chunk * row * sizeof(float), &d_mags);
+  if (e == hipSuccess && b.pitch_out) e = ctx->stage[kStagePitch].get((size_t)chunk * sizeof(mx_pitch), &d_pitch);
+  if (e == hipSuccess && b.ranges) e = ctx->stage[kStageRanges].get((size_t)chunk * 2 * sizeof(int32_t), &d_ranges);
+  if (e == hipSuccess && b.rgb_out) e = ctx->stage[kStageTexels].get((size_t)chunk * row * 3, &d_rgb);
+  int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
+  for (int64_t done = 0; done < b.count && rc == MX_OK; done += chunk) {
+    const int64_t c = std::min(chunk, b.count - done);
+    if (b.d_rows) d_mags = b.d_rows + (size_t)done * row;
+    if (b.ranges)
+      e = hipMemcpyAsync(d_ranges, b.ranges + 2 * done, (size_t)c * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "ranges upload: %s", hipGetErrorString(e));
+    if (rc == MX_OK) rc = run(done, c, d_ranges, d_mags, d_pitch, d_rgb);
+    if (rc) break;
+    if (b.mags_out)
+      e = hipMemcpyAsync(b.mags_out + (size_t)done * row, d_mags, (size_t)c * row * sizeof(float), hipMemcpyDeviceToHost,
+                         ctx->stream);
+    if (e == hipSuccess && b.pitch_out)
+      e = hipMemcpyAsync(b.pitch_out + done, d_pitch, (size_t)c * sizeof(mx_pitch), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && b.rgb_out)
+      e = hipMemcpyAsync(b.rgb_out + (size_t)done * row * 3, d_rgb, (size_t)c * row * 3, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "result download: %s", hipGetErrorString(e));
+  }
+  stage_trim(ctx);
+  return rc;
+}
 
 // The host-pointer form of a PCM entry point: `to_device(d_f32, d_i16)`, its device form, fills device buffers of n samples in the
 // formats the caller asked for; they reach the caller's buffers only if it succeeded.

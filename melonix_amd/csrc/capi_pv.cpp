@@ -322,17 +322,12 @@ int mx_pv_plan(int64_t n, int sampleRate, const mx_marker *markers, int nmarkers
     const int rc = build_pv_plan(markers, nmarkers, sampleRate, n, plan, err);
     if (rc) return fail(rc, "%s", err.c_str());
     const size_t F = plan.apos.size();
-    int64_t *pa = (int64_t *)malloc(F * 8), *pi = (int64_t *)malloc((F + 1) * 8);
-    double *pt = (double *)malloc(F * 8), *pr = (double *)malloc(F * 8);
-    if (!pa || !pi || !pt || !pr) {
-      free(pa); free(pi); free(pt); free(pr);
-      return fail(MX_ERR_NOMEM, "out of host memory");
-    }
-    memcpy(pa, plan.apos.data(), F * 8);
-    memcpy(pi, plan.i0.data(), (F + 1) * 8);
-    memcpy(pt, plan.tf.data(), F * 8);
-    memcpy(pr, plan.rf.data(), F * 8);
-    *apos = pa; *i0 = pi; *tf = pt; *rf = pr;
+    HandOver h;
+    h.add(apos, plan.apos.data(), F);
+    h.add(i0, plan.i0.data(), F + 1);
+    h.add(tf, plan.tf.data(), F);
+    h.add(rf, plan.rf.data(), F);
+    if (const int rc = h.give()) return rc;
     *frames = (int64_t)F;
     *nsamples = plan.n_out;
     return MX_OK;

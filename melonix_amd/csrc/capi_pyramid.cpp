@@ -23,18 +23,15 @@ int mx_minmax_pyramid(mx_ctx *ctx, const mx_audio *a, float *picks_out, int64_t 
     *nlevels = 0;
     if (a->n <= 2) return MX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    float *d = nullptr;
-    HIP_TRY(hipMalloc(&d, (size_t)a->n * 2 * sizeof(float)));
-    int rc = mx_minmax_pyramid_dev(ctx, a, d, counts_out, nlevels);
-    if (rc == MX_OK) {
-      int64_t pairs = 0;
-      for (int l = 0; l < *nlevels; ++l) pairs += counts_out[l];
-      hipError_t e = hipMemcpyAsync(picks_out, d, (size_t)pairs * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "pyramid download: %s", hipGetErrorString(e));
-    }
-    hipFree(d);
-    return rc;
+    DeviceArray<float> d;
+    HIP_TRY(d.alloc(ctx->stream, (size_t)a->n * 2));
+    const int rc = mx_minmax_pyramid_dev(ctx, a, d.p, counts_out, nlevels);
+    if (rc) return rc;
+    int64_t pairs = 0;
+    for (int l = 0; l < *nlevels; ++l) pairs += counts_out[l];
+    hipError_t e = d.download(picks_out, (size_t)pairs * 2);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "pyramid download: %s", hipGetErrorString(e));
   });
 }
 

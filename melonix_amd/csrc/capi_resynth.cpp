@@ -42,44 +42,20 @@ void mx_column_range(const mx_marker *m, int nm, int sr, double time, int width,
 }
 
 // ---- grains + schedule -----------------------------------------------------------
-static int export_vectors(const std::vector<int32_t> &s, const std::vector<int32_t> &l, int32_t **starts,
-                          int32_t **lens, int64_t *count) {
-  const size_t n = s.size();
-  int32_t *ps = (int32_t *)malloc(sizeof(int32_t) * std::max<size_t>(n, 1));
-  int32_t *pl = (int32_t *)malloc(sizeof(int32_t) * std::max<size_t>(n, 1));
-  if (!ps || !pl) { free(ps); free(pl); return fail(MX_ERR_NOMEM, "out of host memory"); }
-  if (n) { memcpy(ps, s.data(), n * sizeof(int32_t)); memcpy(pl, l.data(), n * sizeof(int32_t)); }
-  *starts = ps; *lens = pl; *count = (int64_t)n;
-  return MX_OK;
-}
-
 int mx_grains(const float *host_wav, int64_t n, int32_t **starts, int32_t **lens, int64_t *count) {
   return mx_guard([&]() -> int {
     if (!starts || !lens || !count || n < 0 || (n > 0 && !host_wav)) return fail(MX_ERR_INVALID, "bad argument");
-    try {
-      ZcBitmaps zc;
-      zc_bitmaps_host(host_wav, n, zc);
-      std::vector<int32_t> s, l;
-      grains_from_bitmaps(zc, s, l);
-      return export_vectors(s, l, starts, lens, count);
-    } catch (const std::bad_alloc &) {
-      return fail(MX_ERR_NOMEM, "out of host memory");
-    }
+    ZcBitmaps zc;
+    zc_bitmaps_host(host_wav, n, zc);
+    std::vector<int32_t> s, l;
+    grains_from_bitmaps(zc, s, l);
+    HandOver h;
+    h.add(starts, s.data(), s.size());
+    h.add(lens, l.data(), l.size());
+    if (const int rc = h.give()) return rc;
+    *count = (int64_t)s.size();
+    return MX_OK;
   });
-}
-
-// grow-only device buffer `slot` of the grain chain; caller holds ctx->zc_mu
-static hipError_t chain_buf(mx_ctx *ctx, int slot, size_t bytes, void **out) {
-  mx_ctx::Stage &st = ctx->chain[slot];
-  if (st.cap < bytes) {
-    if (st.p) hipFree(st.p);
-    st = {};
-    const hipError_t e = hipMalloc(&st.p, bytes);
-    if (e != hipSuccess) return e;
-    st.cap = bytes;
-  }
-  *out = st.p;
-  return hipSuccess;
 }
 
 int mx_grain_table_dev(mx_ctx *ctx, const mx_audio *a, int32_t **starts, int32_t **lens, float **firsts, int64_t *count) {
@@ -89,68 +65,55 @@ int mx_grain_table_dev(mx_ctx *ctx, const mx_audio *a, int32_t **starts, int32_t
     if (firsts) *firsts = nullptr;
     *count = 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool tr = getenv("MELONIX_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    const auto t0 = now();
+    PhaseClock phases;
     std::lock_guard<std::mutex> zlk(ctx->zc_mu);
     const int64_t n = a->n;
     const size_t words = (size_t)((n + 63) >> 6);
     uint32_t ngr = 0;
     int32_t *d_s = nullptr, *d_l = nullptr;
     float *d_f = nullptr;
-    auto t1 = t0, t2 = t0;
     if (words && n >= 1501) {  // (the reference's size_t arithmetic wraps below 1501 samples, app.cpp:161: no grains)
-      void *d7 = nullptr, *d3 = nullptr, *rk = nullptr, *ch = nullptr;
-      hipError_t e = chain_buf(ctx, 0, words * 8, &d7);
-      if (e == hipSuccess) e = chain_buf(ctx, 1, words * 8, &d3);
-      if (e == hipSuccess) e = chain_buf(ctx, 2, grain_rank_scratch_bytes(n), &rk);
+      uint64_t *d7 = nullptr, *d3 = nullptr;
+      void *rk = nullptr, *ch = nullptr;
+      hipError_t e = ctx->chain[kChainBitmap7].get(words * 8, &d7);
+      if (e == hipSuccess) e = ctx->chain[kChainBitmap3].get(words * 8, &d3);
+      if (e == hipSuccess) e = ctx->chain[kChainRanks].get(grain_rank_scratch_bytes(n), &rk);
       if (e != hipSuccess) return fail(MX_ERR_NOMEM, "grain chain buffers: %s", hipGetErrorString(e));
-      HIP_TRY(launch_zc_bitmaps(a->d_padded, n, (uint64_t *)d7, (uint64_t *)d3, ctx->stream));
-      HIP_TRY(launch_grain_rank(a->d_padded, n, (const uint64_t *)d7, (const uint64_t *)d3, rk, ctx->stream));
+      HIP_TRY(launch_zc_bitmaps(a->d_padded, n, d7, d3, ctx->stream));
+      HIP_TRY(launch_grain_rank(a->d_padded, n, d7, d3, rk, ctx->stream));
       uint32_t hdr[4] = {0, 0, 0, 0};
       HIP_TRY(hipMemcpyAsync(hdr, rk, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));  // the node count sizes the lifting tables
-      t1 = now();
+      phases.mark();
       int levels;
       uint32_t out_cap;
       size_t bytes;
       grain_chain_sizes(n, hdr[2], &levels, &out_cap, &bytes);
-      e = chain_buf(ctx, 3, bytes, &ch);
+      e = ctx->chain[kChainTables].get(bytes, &ch);
       if (e != hipSuccess) return fail(MX_ERR_NOMEM, "grain chain tables (%zu bytes): %s", bytes, hipGetErrorString(e));
-      HIP_TRY(launch_grain_chain(a->d_padded, n, (const uint64_t *)d7, (const uint64_t *)d3, rk, hdr[2], ch, &d_s, &d_l, &d_f,
-                                 ctx->stream));
+      HIP_TRY(launch_grain_chain(a->d_padded, n, d7, d3, rk, hdr[2], ch, &d_s, &d_l, &d_f, ctx->stream));
       HIP_TRY(hipMemcpyAsync(hdr, rk, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
-      t2 = now();
+      phases.mark();
       ngr = hdr[1];
       if (ngr > out_cap) return fail(MX_ERR_DEVICE, "grain chain: %u grains exceed the bound %u", ngr, out_cap);
     }
-    const size_t m = std::max<size_t>(ngr, 1);
-    int32_t *ps = (int32_t *)malloc(m * 4), *pl = (int32_t *)malloc(m * 4);
-    float *pf = firsts ? (float *)malloc(m * 4) : nullptr;
-    if (!ps || !pl || (firsts && !pf)) {
-      free(ps); free(pl); free(pf);
-      return fail(MX_ERR_NOMEM, "out of host memory");
-    }
+    HandOver h;  // (the arrays are filled by the download: nothing to copy)
+    int32_t *ps = h.add<int32_t>(starts, nullptr, ngr), *pl = h.add<int32_t>(lens, nullptr, ngr);
+    float *pf = firsts ? h.add<float>(firsts, nullptr, ngr) : nullptr;
+    if (!h.ok()) return h.give();
     if (ngr) {
       hipError_t e = hipMemcpyAsync(ps, d_s, (size_t)ngr * 4, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess) e = hipMemcpyAsync(pl, d_l, (size_t)ngr * 4, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess && pf) e = hipMemcpyAsync(pf, d_f, (size_t)ngr * 4, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) {
-        free(ps); free(pl); free(pf);
-        return fail(MX_ERR_DEVICE, "grain table download: %s", hipGetErrorString(e));
-      }
+      if (e != hipSuccess) return fail(MX_ERR_DEVICE, "grain table download: %s", hipGetErrorString(e));
     }
-    if (tr)
-      fprintf(stderr, "mx_grain_table_dev: bitmaps + ranks %.2f ms, chain %.2f, download of %u grains %.2f\n", ms(t0, t1),
-              ms(t1, t2), ngr, ms(t2, now()));
-    *starts = ps;
-    *lens = pl;
-    if (firsts) *firsts = pf;
+    if (phases.on)
+      fprintf(stderr, "mx_grain_table_dev: bitmaps + ranks %.2f ms, chain %.2f, download of %u grains %.2f\n", phases.ms(0),
+              phases.ms(1), ngr, phases.ms(2));
     *count = (int64_t)ngr;
-    return MX_OK;
+    return h.give();
   });
 }
 
@@ -158,6 +121,37 @@ int mx_grains_dev(mx_ctx *ctx, const mx_audio *a, int32_t **starts, int32_t **le
   return mx_guard([&]() -> int {
     return mx_grain_table_dev(ctx, a, starts, lens, nullptr, count);
   });
+}
+
+// the schedule from a grain table: first samples read from host_wav, or from `firsts` where the caller has no samples
+static int schedule_common(const float *host_wav, const float *firsts, int64_t n, int sampleRate, const int32_t *grain_starts,
+                           const int32_t *grain_lens, int64_t ngrains, const mx_marker *markers, int nmarkers,
+                           double cursor0, int64_t need, mx_step **steps, int64_t *nsteps, int64_t *nsamples,
+                           double *cursor_end) {
+  if (!steps || !nsteps || !nsamples || n < 0 || ngrains < 0 || nmarkers < 0 ||
+      (ngrains > 0 && (!grain_starts || !grain_lens)) || (nmarkers > 0 && !markers))
+    return fail(MX_ERR_INVALID, "bad argument");
+  PhaseClock phases;
+  for (int64_t g = 0; g < ngrains; ++g)
+    if (grain_starts[g] < 0 || grain_lens[g] <= 0 || (int64_t)grain_starts[g] + grain_lens[g] > n)
+      return fail(MX_ERR_INVALID, "grain %lld lies outside the audio", (long long)g);
+  std::vector<mx_step> v;
+  std::string err;
+  int64_t total = 0;
+  phases.mark();
+  int rc = build_schedule(host_wav, n, sampleRate, grain_starts, grain_lens, ngrains, markers, nmarkers, v, total, err,
+                          cursor0, need, cursor_end, firsts);
+  phases.mark();
+  if (rc) return fail(rc, "%s", err.c_str());
+  HandOver h;
+  h.add(steps, v.data(), v.size());
+  if ((rc = h.give())) return rc;
+  if (phases.on)
+    fprintf(stderr, "mx_schedule_build: validate %.2f ms, recurrence %.2f ms (%zu steps), hand-over %.2f ms\n", phases.ms(0),
+            phases.ms(1), v.size(), phases.ms(2));
+  *nsteps = (int64_t)v.size();
+  *nsamples = total;
+  return MX_OK;
 }
 
 int mx_schedule_build(const float *host_wav, int64_t n, int sampleRate, const int32_t *grain_starts,
@@ -168,11 +162,6 @@ int mx_schedule_build(const float *host_wav, int64_t n, int sampleRate, const in
                                   steps, nsteps, nsamples, nullptr);
   });
 }
-
-static int schedule_common(const float *host_wav, const float *firsts, int64_t n, int sampleRate, const int32_t *grain_starts,
-                           const int32_t *grain_lens, int64_t ngrains, const mx_marker *markers, int nmarkers,
-                           double cursor0, int64_t need, mx_step **steps, int64_t *nsteps, int64_t *nsamples,
-                           double *cursor_end);
 
 int mx_schedule_build_from(const float *host_wav, int64_t n, int sampleRate, const int32_t *grain_starts,
                            const int32_t *grain_lens, int64_t ngrains, const mx_marker *markers, int nmarkers,
@@ -196,45 +185,6 @@ int mx_schedule_build_table(int64_t n, int sampleRate, const int32_t *grain_star
                            markers, nmarkers, cursor0, need, steps, nsteps, nsamples, cursor_end);
   });
 }
-
-static int schedule_common(const float *host_wav, const float *firsts, int64_t n, int sampleRate, const int32_t *grain_starts,
-                           const int32_t *grain_lens, int64_t ngrains, const mx_marker *markers, int nmarkers,
-                           double cursor0, int64_t need, mx_step **steps, int64_t *nsteps, int64_t *nsamples,
-                           double *cursor_end) {
-  if (!steps || !nsteps || !nsamples || n < 0 || ngrains < 0 || nmarkers < 0 ||
-      (ngrains > 0 && (!grain_starts || !grain_lens)) || (nmarkers > 0 && !markers))
-    return fail(MX_ERR_INVALID, "bad argument");
-  const bool tr = getenv("MELONIX_TIMING") != nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (int64_t g = 0; g < ngrains; ++g)
-    if (grain_starts[g] < 0 || grain_lens[g] <= 0 || (int64_t)grain_starts[g] + grain_lens[g] > n)
-      return fail(MX_ERR_INVALID, "grain %lld lies outside the audio", (long long)g);
-  try {
-    std::vector<mx_step> v;
-    std::string err;
-    int64_t total = 0;
-    const auto t1 = std::chrono::steady_clock::now();
-    const int rc = build_schedule(host_wav, n, sampleRate, grain_starts, grain_lens, ngrains, markers, nmarkers, v,
-                                  total, err, cursor0, need, cursor_end, firsts);
-    const auto t2 = std::chrono::steady_clock::now();
-    if (rc) return fail(rc, "%s", err.c_str());
-    mx_step *p = (mx_step *)malloc(sizeof(mx_step) * std::max<size_t>(v.size(), 1));
-    if (!p) return fail(MX_ERR_NOMEM, "out of host memory");
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(mx_step));
-    if (tr)
-      fprintf(stderr, "mx_schedule_build: validate %.2f ms, recurrence %.2f ms (%zu steps), hand-over %.2f ms\n",
-              std::chrono::duration<double, std::milli>(t1 - t0).count(),
-              std::chrono::duration<double, std::milli>(t2 - t1).count(), v.size(),
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
-    *steps = p;
-    *nsteps = (int64_t)v.size();
-    *nsamples = total;
-    return MX_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(MX_ERR_NOMEM, "out of host memory");
-  }
-}
-
 
 // ---- resynthesis -------------------------------------------------------------------
 int mx_resynth_dev(mx_ctx *ctx, const mx_audio *a, const mx_step *d_steps, int64_t nsteps, int64_t nsamples,
@@ -366,29 +316,25 @@ int mx_export_wav(mx_ctx *ctx, const float *host_wav, int64_t n, int sampleRate,
                   int nmarkers, const char *path, int strict_reference_header) {
   return mx_guard([&]() -> int {
     if (!ctx || !path || n < 0 || (n > 0 && !host_wav)) return fail(MX_ERR_INVALID, "bad argument");
-    const bool tr = getenv("MELONIX_TIMING") != nullptr;
-    using clk = std::chrono::steady_clock;
-    auto ms = [](clk::time_point x, clk::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    const auto t0 = clk::now();
+    PhaseClock phases;
     mx_audio *a = nullptr;
     int rc = mx_audio_upload(ctx, host_wav, n, &a);
     if (rc) return rc;
-    const auto t1 = clk::now();
+    phases.mark();
     int32_t *gs = nullptr, *gl = nullptr;
     int64_t ng = 0, nsteps = 0, nsamples = 0;
     mx_step *steps = nullptr;
     rc = mx_grains_dev(ctx, a, &gs, &gl, &ng);
-    const auto t2 = clk::now();
+    phases.mark();
     if (rc == MX_OK) rc = mx_schedule_build(host_wav, n, sampleRate, gs, gl, ng, markers, nmarkers, &steps, &nsteps, &nsamples);
-    const auto t3 = clk::now();
+    phases.mark();
     if (rc == MX_OK) rc = mx_resynth_to_wav(ctx, a, steps, nsteps, nsamples, path, sampleRate, strict_reference_header);
-    const auto t4 = clk::now();
-    const auto t5 = t4;
+    phases.mark();
     mx_free(steps); mx_free(gs); mx_free(gl);
     mx_audio_free(ctx, a);
-    if (tr)
+    if (phases.on)
       fprintf(stderr, "mx_export_wav: upload %.2f ms, grains %.2f, schedule %.2f, resynth + D2H + file %.2f, free %.2f\n",
-              ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t5, clk::now()));
+              phases.ms(0), phases.ms(1), phases.ms(2), phases.ms(3), phases.ms(4));
     return rc;
   });
 }

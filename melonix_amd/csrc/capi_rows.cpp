@@ -13,6 +13,8 @@ struct mx_rows {
   int device = 0;
   int64_t count = 0;
   float *d = nullptr;  // count x N/2
+  // (a plain hipFree, which synchronises the device itself: kept rows outlive mx_ctx_set_stream changes, no stream is theirs)
+  ~mx_rows() { hipFree(d); }
 };
 
 int mx_stft_ranges_keep(mx_ctx *ctx, const mx_audio *a, int N, const int32_t *ranges, int64_t count, float k,
@@ -35,36 +37,12 @@ int mx_stft_ranges_keep(mx_ctx *ctx, const mx_audio *a, int N, const int32_t *ra
     keep->count = count;
     hipError_t e = hipMalloc((void **)&keep->d, (size_t)count * row * sizeof(float));
     if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device rows (%lld x %zu floats): %s", (long long)count, row, hipGetErrorString(e));
-    const int64_t chunk = std::min<int64_t>(count, chunk_frames(N));
-    uint8_t *d_rgb = nullptr;
-    int32_t *d_ranges = nullptr;
-    {
-      std::lock_guard<std::mutex> slk(ctx->stage_mu);
-      e = hipSuccess;
-      if (want_rgb) e = stage_get(ctx, 3, (size_t)chunk * row * 3, (void **)&d_rgb);
-      if (e == hipSuccess) e = stage_get(ctx, 2, (size_t)chunk * 2 * sizeof(int32_t), (void **)&d_ranges);
-      if (e != hipSuccess) rc = fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
-      for (int64_t done = 0; done < count && rc == MX_OK; done += chunk) {
-        const int64_t c = std::min(chunk, count - done);
-        float *dm = keep->d + (size_t)done * row;
-        e = hipMemcpyAsync(d_ranges, ranges + 2 * done, (size_t)c * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { rc = fail(MX_ERR_DEVICE, "ranges upload: %s", hipGetErrorString(e)); break; }
-        rc = want_rgb ? mx_stft_ranges_rgb_dev(ctx, a, N, d_ranges, c, k, dm, d_rgb)
-                      : mx_stft_ranges_dev(ctx, a, N, d_ranges, c, -1, -1, dm, nullptr);
-        if (rc) break;
-        if (want_rgb)
-          e = hipMemcpyAsync(rgb_out + (size_t)done * row * 3, d_rgb, (size_t)c * row * 3, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && mags_out)
-          e = hipMemcpyAsync(mags_out + (size_t)done * row, dm, (size_t)c * row * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "row download: %s", hipGetErrorString(e));
-      }
-      stage_trim(ctx);
-    }
-    if (rc) {
-      hipFree(keep->d);
-      return rc;
-    }
+    const StagedBatch b{N, count, ranges, mags_out, nullptr, want_rgb ? rgb_out : nullptr, keep->d};
+    rc = staged_batch(ctx, b, [&](int64_t, int64_t c, const int32_t *d_ranges, float *d_mags, mx_pitch *, uint8_t *d_rgb) {
+      return want_rgb ? mx_stft_ranges_rgb_dev(ctx, a, N, d_ranges, c, k, d_mags, d_rgb)
+                      : mx_stft_ranges_dev(ctx, a, N, d_ranges, c, -1, -1, d_mags, nullptr);
+    });
+    if (rc) return rc;
     *rows_out = keep.release();
     return MX_OK;
   });
@@ -80,7 +58,6 @@ void mx_rows_free(mx_ctx *ctx, mx_rows *rows) {
   mx_guard_void([&] {
     if (!rows) return;
     if (ctx) hipSetDevice(ctx->device);
-    if (rows->d) hipFree(rows->d);
     delete rows;
   });
 }
@@ -112,23 +89,13 @@ int mx_rows_colormap(mx_ctx *ctx, const mx_rows *rows, int64_t first, int64_t co
   return mx_guard([&]() -> int {
     int rc = rows_span_ok(ctx, rows, first, count, rgb_out);
     if (rc || count == 0) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    // the rows are where they stay: each chunk of the span is re-coloured into the texel staging buffer
     const size_t row = (size_t)(rows->N / 2);
-    const int64_t chunk = std::min<int64_t>(count, chunk_frames(rows->N));
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);
-    uint8_t *d_rgb = nullptr;
-    hipError_t e = stage_get(ctx, 3, (size_t)chunk * row * 3, (void **)&d_rgb);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device staging buffer: %s", hipGetErrorString(e));
-    for (int64_t done = 0; done < count && rc == MX_OK; done += chunk) {
-      const int64_t c = std::min(chunk, count - done);
-      e = launch_colormap(rows->d + (size_t)(first + done) * row, d_rgb, (int64_t)c * (int64_t)row, k, ctx->stream);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(rgb_out + (size_t)done * row * 3, d_rgb, (size_t)c * row * 3, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "re-colouring rows: %s", hipGetErrorString(e));
-    }
-    stage_trim(ctx);
-    return rc;
+    const StagedBatch b{rows->N, count, nullptr, nullptr, nullptr, rgb_out, rows->d + (size_t)first * row};
+    return staged_batch(ctx, b, [&](int64_t, int64_t c, const int32_t *, float *d_mags, mx_pitch *, uint8_t *d_rgb) {
+      HIP_TRY(launch_colormap(d_mags, d_rgb, (int64_t)c * (int64_t)row, k, ctx->stream));
+      return MX_OK;
+    });
   });
 }
 

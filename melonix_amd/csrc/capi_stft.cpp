@@ -45,22 +45,26 @@ int64_t mx_frame_count(int64_t n, int hop) {
   });
 }
 
-static int stft_hop_dev_run(mx_ctx *ctx, const mx_audio *a, int N, int hop, int64_t first_frame, int64_t count,
-                            int kmin, int kmax, float *d_mags, mx_pitch *d_pitch, int run_length) {
+// hop mode's argument checks, check_common's among them: once per call, host-staged or not
+static int stft_hop_check(mx_ctx *ctx, const mx_audio *a, int N, int hop, int64_t first_frame, int64_t count, int &kmin,
+                          int &kmax) {
   int rc = check_common(ctx, a, N, count, kmin, kmax);
   if (rc) return rc;
   if (hop <= 0 || hop > MX_AUDIO_PAD) return fail(MX_ERR_INVALID, "hop %d out of range [1,%d]", hop, MX_AUDIO_PAD);
   if (first_frame < 0 || (count > 0 && (first_frame + count - 1) * (int64_t)hop >= a->n))
     return fail(MX_ERR_INVALID, "frames [%lld,%lld) exceed ceil(n/hop)", (long long)first_frame,
                 (long long)(first_frame + count));
-  return stft_launch(ctx, a, N, (hop % 2 == 0) ? kBulkAligned : kBulkAny, hop, first_frame, nullptr, count, kmin,
-                     kmax, d_mags, d_pitch, nullptr, 0.f, run_length);
+  return MX_OK;
 }
+// hop mode's kernel variant
+static int bulk_mode(int hop) { return (hop % 2 == 0) ? kBulkAligned : kBulkAny; }
 
 int mx_stft_hop_dev(mx_ctx *ctx, const mx_audio *a, int N, int hop, int64_t first_frame, int64_t count,
                     int kmin, int kmax, float *d_mags, mx_pitch *d_pitch) {
   return mx_guard([&]() -> int {
-    return stft_hop_dev_run(ctx, a, N, hop, first_frame, count, kmin, kmax, d_mags, d_pitch, 0);
+    int rc = stft_hop_check(ctx, a, N, hop, first_frame, count, kmin, kmax);
+    if (rc) return rc;
+    return stft_launch(ctx, a, N, bulk_mode(hop), hop, first_frame, nullptr, count, kmin, kmax, d_mags, d_pitch, nullptr, 0.f);
   });
 }
 
@@ -74,56 +78,18 @@ int mx_stft_ranges_dev(mx_ctx *ctx, const mx_audio *a, int N, const int32_t *d_r
   });
 }
 
-static int stft_host_common(mx_ctx *ctx, const mx_audio *a, int N, bool ranges_mode, int hop, int64_t first_frame,
-                            const int32_t *ranges, int64_t count, int kmin, int kmax, float *mags_out,
-                            mx_pitch *pitch_out) {
-  int rc = check_common(ctx, a, N, count, kmin, kmax);
-  if (rc) return rc;
-  if (count == 0) return MX_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  const int64_t chunk = std::min<int64_t>(count, chunk_frames(N));
-  float *d_mags = nullptr;
-  mx_pitch *d_pitch = nullptr;
-  int32_t *d_ranges = nullptr;
-  const size_t row = (size_t)(N / 2);
-  hipError_t e = hipSuccess;
-  std::lock_guard<std::mutex> slk(ctx->stage_mu);
-  if (mags_out) e = stage_get(ctx, 0, (size_t)chunk * row * sizeof(float), (void **)&d_mags);
-  if (e == hipSuccess && pitch_out) e = stage_get(ctx, 1, (size_t)chunk * sizeof(mx_pitch), (void **)&d_pitch);
-  if (e == hipSuccess && ranges_mode) e = stage_get(ctx, 2, (size_t)chunk * 2 * sizeof(int32_t), (void **)&d_ranges);
-  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
-  rc = MX_OK;
-  // one run length for the whole call, whatever its staging chunks are (chunks are multiples of 32 frames): the rows
-  // are those of a single launch of `count` frames
-  const int run = ranges_mode ? 0 : default_frames_per_block(N, (hop % 2 == 0) ? kBulkAligned : kBulkAny, hop, count);
-  for (int64_t done = 0; done < count && rc == MX_OK; done += chunk) {
-    const int64_t c = std::min(chunk, count - done);
-    if (ranges_mode) {
-      e = hipMemcpyAsync(d_ranges, ranges + 2 * done, (size_t)c * 2 * sizeof(int32_t), hipMemcpyHostToDevice,
-                         ctx->stream);
-      if (e != hipSuccess) { rc = fail(MX_ERR_DEVICE, "ranges upload: %s", hipGetErrorString(e)); break; }
-      rc = mx_stft_ranges_dev(ctx, a, N, d_ranges, c, kmin, kmax, d_mags, d_pitch);
-    } else {
-      rc = stft_hop_dev_run(ctx, a, N, hop, first_frame + done, c, kmin, kmax, d_mags, d_pitch, run);
-    }
-    if (rc) break;
-    if (mags_out)
-      e = hipMemcpyAsync(mags_out + (size_t)done * row, d_mags, (size_t)c * row * sizeof(float),
-                         hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && pitch_out)
-      e = hipMemcpyAsync(pitch_out + done, d_pitch, (size_t)c * sizeof(mx_pitch), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "result download: %s", hipGetErrorString(e));
-  }
-  stage_trim(ctx);
-  return rc;
-}
-
 int mx_stft_hop(mx_ctx *ctx, const mx_audio *a, int N, int hop, int64_t first_frame, int64_t count, int kmin,
                 int kmax, float *mags_out, mx_pitch *pitch_out) {
   return mx_guard([&]() -> int {
-    if (hop <= 0) return fail(MX_ERR_INVALID, "hop must be positive");
-    return stft_host_common(ctx, a, N, false, hop, first_frame, nullptr, count, kmin, kmax, mags_out, pitch_out);
+    int rc = stft_hop_check(ctx, a, N, hop, first_frame, count, kmin, kmax);
+    if (rc || count == 0) return rc;
+    // one run length for the whole call, whatever its staging chunks are (chunks are multiples of 32 frames): the rows
+    // are those of a single launch of `count` frames
+    const int mode = bulk_mode(hop), run = default_frames_per_block(N, mode, hop, count);
+    const StagedBatch b{N, count, nullptr, mags_out, pitch_out};
+    return staged_batch(ctx, b, [&](int64_t done, int64_t c, const int32_t *, float *d_mags, mx_pitch *d_pitch, uint8_t *) {
+      return stft_launch(ctx, a, N, mode, hop, first_frame + done, nullptr, c, kmin, kmax, d_mags, d_pitch, nullptr, 0.f, run);
+    });
   });
 }
 
@@ -131,7 +97,12 @@ int mx_stft_ranges(mx_ctx *ctx, const mx_audio *a, int N, const int32_t *ranges,
                    float *mags_out, mx_pitch *pitch_out) {
   return mx_guard([&]() -> int {
     if (count > 0 && !ranges) return fail(MX_ERR_INVALID, "ranges is null");
-    return stft_host_common(ctx, a, N, true, 0, 0, ranges, count, kmin, kmax, mags_out, pitch_out);
+    int rc = check_common(ctx, a, N, count, kmin, kmax);
+    if (rc || count == 0) return rc;
+    const StagedBatch b{N, count, ranges, mags_out, pitch_out};
+    return staged_batch(ctx, b, [&](int64_t, int64_t c, const int32_t *d_ranges, float *d_mags, mx_pitch *d_pitch, uint8_t *) {
+      return mx_stft_ranges_dev(ctx, a, N, d_ranges, c, kmin, kmax, d_mags, d_pitch);
+    });
   });
 }
 
@@ -153,35 +124,12 @@ int mx_stft_ranges_rgb_mags(mx_ctx *ctx, const mx_audio *a, int N, const int32_t
   return mx_guard([&]() -> int {
     int kmin = -1, kmax = -1;
     int rc = check_common(ctx, a, N, count, kmin, kmax);
-    if (rc) return rc;
-    if (count == 0) return MX_OK;
+    if (rc || count == 0) return rc;
     if (!ranges || !rgb_out) return fail(MX_ERR_INVALID, "ranges / rgb_out is null");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t row = (size_t)(N / 2);
-    const int64_t chunk = std::min<int64_t>(count, chunk_frames(N));
-    float *d_mags = nullptr;
-    uint8_t *d_rgb = nullptr;
-    int32_t *d_ranges = nullptr;
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);
-    hipError_t e = stage_get(ctx, 3, (size_t)chunk * row * 3, (void **)&d_rgb);
-    if (e == hipSuccess && mags_out) e = stage_get(ctx, 0, (size_t)chunk * row * sizeof(float), (void **)&d_mags);
-    if (e == hipSuccess) e = stage_get(ctx, 2, (size_t)chunk * 2 * sizeof(int32_t), (void **)&d_ranges);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
-    for (int64_t done = 0; done < count && rc == MX_OK; done += chunk) {
-      const int64_t c = std::min(chunk, count - done);
-      e = hipMemcpyAsync(d_ranges, ranges + 2 * done, (size_t)c * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) { rc = fail(MX_ERR_DEVICE, "ranges upload: %s", hipGetErrorString(e)); break; }
-      rc = mx_stft_ranges_rgb_dev(ctx, a, N, d_ranges, c, k, d_mags, d_rgb);
-      if (rc) break;
-      e = hipMemcpyAsync(rgb_out + (size_t)done * row * 3, d_rgb, (size_t)c * row * 3, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess && mags_out)
-        e = hipMemcpyAsync(mags_out + (size_t)done * row, d_mags, (size_t)c * row * sizeof(float), hipMemcpyDeviceToHost,
-                           ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "texel download: %s", hipGetErrorString(e));
-    }
-    stage_trim(ctx);
-    return rc;
+    const StagedBatch b{N, count, ranges, mags_out, nullptr, rgb_out};
+    return staged_batch(ctx, b, [&](int64_t, int64_t c, const int32_t *d_ranges, float *d_mags, mx_pitch *, uint8_t *d_rgb) {
+      return mx_stft_ranges_rgb_dev(ctx, a, N, d_ranges, c, k, d_mags, d_rgb);
+    });
   });
 }
 

@@ -548,6 +548,11 @@ void device_entries() {
     }
     return {rc, h};
   });
+  sweep("mx_f0_track", [&]() -> Result {
+    std::vector<mx_f0> f0((size_t)F);
+    const int rc = mx_f0_track(ctx, a, sr, hop, 0, F, 55.f, 1760.f, 0.15f, f0.data());
+    return {rc, rc < 0 ? 0 : fnv(f0.data(), f0.size() * sizeof(mx_f0))};
+  });
   sweep("mx_ctx_release_scratch", [&]() -> Result { return {mx_ctx_release_scratch(ctx), 0}; });
   mx_free(steps);
   mx_free(gs);

@@ -10,7 +10,7 @@ through size-independent properties — the oracle cannot cover them in seconds:
 import numpy as np
 import pytest
 
-from conftest import SR, mag_tol
+from conftest import SR, mag_tol, noisy
 
 pytestmark = pytest.mark.gpu
 
@@ -412,5 +412,60 @@ def test_pv_more_than_2M_frames(gpu_ctx, hour):
     # the 110..1760 Hz sweep lands two octaves up: still a tone of the input's level where it stays below Nyquist
     seg = slice(n // 8, n // 4)
     assert 0.5 < np.sqrt((y[seg].astype(np.float64) ** 2).mean()) / np.sqrt((w[seg].astype(np.float64) ** 2).mean()) < 1.1
+    gpu_ctx.release_scratch()
+    a.free()
+
+
+def test_host_staged_paths_across_a_staging_chunk_boundary(gpu_ctx, sweep10):
+    """The host-staged entry points walk a batch in staging chunks of ~1 GiB of rows: 16384 columns at N = 32768.  A
+    batch of 16384 + 40 columns crosses that boundary once on every path that has one — ranges mode with magnitudes and
+    pitch records, the texel rows with magnitudes, the kept rows with texels and magnitudes, and the re-colouring of
+    kept rows.  Ranges-mode rows do not depend on their batch, so the one call must equal, bit for bit, two calls of
+    one chunk each put end to end (the per-chunk offsets into the ranges, the rows, the texels and the kept rows)."""
+    N3, C, K = 32768, 16384, 900.0
+    count = C + 40
+    a = gpu_ctx.upload(noisy(sweep10))
+    start = np.arange(count) * ((len(sweep10) - 375) // count)
+    cols = np.stack([start, start + 375], axis=1).astype(np.int32)
+
+    def halves_equal(whole, head, tail):
+        return np.array_equal(whole[:C], head) and np.array_equal(whole[C:], tail)
+
+    # ranges mode: magnitudes + pitch records
+    m, p = gpu_ctx.stft_ranges(a, N3, cols)
+    assert m.shape == (count, N3 // 2) and float(m[C:].max()) > 0
+    mh, ph = gpu_ctx.stft_ranges(a, N3, cols[:C])
+    assert np.array_equal(m[:C], mh) and np.array_equal(p[:C], ph)
+    del mh
+    mt, pt = gpu_ctx.stft_ranges(a, N3, cols[C:])
+    assert np.array_equal(m[C:], mt) and np.array_equal(p[C:], pt)
+    del m, mt
+
+    # texel rows with the magnitudes of the same launch
+    rgb, m = gpu_ctx.stft_ranges_rgb(a, N3, cols, K, want_mags=True)
+    assert int(rgb[C:].max()) > 0
+    rh, mh = gpu_ctx.stft_ranges_rgb(a, N3, cols[:C], K, want_mags=True)
+    rt, mt = gpu_ctx.stft_ranges_rgb(a, N3, cols[C:], K, want_mags=True)
+    assert halves_equal(rgb, rh, rt) and halves_equal(m, mh, mt)
+    del rgb, m, rh, mh, rt, mt
+
+    # kept rows: the texels and magnitudes that come back, the rows that stay, and their re-colouring
+    rows, rgb, m = gpu_ctx.stft_ranges_keep(a, N3, cols, k=K, want_mags=True)
+    rows_h, rh, mh = gpu_ctx.stft_ranges_keep(a, N3, cols[:C], k=K, want_mags=True)
+    rows_t, rt, mt = gpu_ctx.stft_ranges_keep(a, N3, cols[C:], k=K, want_mags=True)
+    assert len(rows) == count
+    assert halves_equal(rgb, rh, rt) and halves_equal(m, mh, mt)
+    del rgb, rh, rt, mh, mt
+    assert np.array_equal(rows.fetch(0, count), m)  # what stayed is what came back
+    assert np.array_equal(rows.fetch(C - 20, 40), m[C - 20:C + 20])
+    del m
+    K2 = 400.0
+    c = rows.colormap(0, count, K2)
+    assert int(c[C:].max()) > 0
+    assert halves_equal(c, rows_h.colormap(0, C, K2), rows_t.colormap(0, count - C, K2))
+    assert np.array_equal(rows.colormap(8, C + 16, K2), c[8:C + 24])  # a span that starts inside the batch
+    del c
+    for r in (rows, rows_h, rows_t):
+        r.free()
     gpu_ctx.release_scratch()
     a.free()
