@@ -33,8 +33,10 @@ UNITS = [
     ("resynth_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("colormap_kernel.hip", "hip", ["-ffp-contract=off"]),
     ("grain_chain.hip", "hip", []),
-    # build-defined phase vocoder: shares the FFT passes of stft_core.h (explicit FMAs)
-    ("pv_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # build-defined phase vocoder, a unit per stage (pv_common.h): shares the FFT passes of stft_core.h (explicit FMAs)
+    ("pv_analysis.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    ("pv_lock.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    ("pv_synthesis.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     # build-defined YIN f0 tracker: three transforms per frame on the same FFT passes
     ("f0_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
@@ -51,9 +53,24 @@ UNITS = [
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
-HEADERS = ["kernels.h", "colormap_core.h", "stft_kernel_impl.h", "stft_core.h", "pk_math.h", "stft_tables.h", "stft_consts.inc",
-           "host_logic.h", "capi_internal.h", "pv_pipe.h", "f0_notes.h",
-           os.path.join("..", "..", "include", "melonix_amd.h")]
+PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units
+
+
+def headers(csrc: str | None = None) -> list[str]:
+    """Every header of the library, relative to `csrc`: what lies there (*.h, *.inc) and the public header."""
+    names = [n for n in os.listdir(csrc or CSRC) if n.endswith((".h", ".inc"))]
+    return sorted(names + [os.path.join("..", "..", "include", "melonix_amd.h")])
+
+
+def unit_command(src: str) -> list[str]:
+    """How unit `src` of UNITS is compiled — compiler, target, flags, source —, for the caller to append what it wants of
+    the compile to: `-c -o x.o`, `-S --cuda-device-only -o x.s`, `-Rpass-analysis=...`.  build() and the tests that
+    look at a unit's ISA or resource usage share it."""
+    kind, extra = next((k, e) for s, k, e in UNITS if s == src)
+    sp = os.path.join(CSRC, src)
+    if kind == "hip":
+        return [HIPCC, f"--offload-arch={ARCH}", "-x", "hip"] + COMMON + extra + [sp]
+    return [CXX, "-O2", "-std=c++17", "-fPIC", "-Wall"] + extra + [sp]
 
 
 def source_sha(csrc: str | None = None, extra_defines: list[str] | None = None) -> str:
@@ -62,7 +79,7 @@ def source_sha(csrc: str | None = None, extra_defines: list[str] | None = None) 
     melonix_amd._capi.lib() refuses a library whose digits differ from the tree it is loaded from."""
     csrc = csrc or CSRC
     h = hashlib.sha1()
-    for name in sorted([u[0] for u in UNITS] + HEADERS):
+    for name in sorted([u[0] for u in UNITS] + headers(csrc)):
         h.update(os.path.basename(name).encode() + b"\0")
         with open(os.path.join(csrc, name), "rb") as fh:
             h.update(fh.read())
@@ -72,7 +89,7 @@ def source_sha(csrc: str | None = None, extra_defines: list[str] | None = None) 
 
 
 def _newest_header() -> float:
-    return max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
+    return max(os.path.getmtime(os.path.join(CSRC, h)) for h in headers())
 
 
 def build(force: bool = False, verbose: bool = False, extra_defines: list[str] | None = None) -> str:
@@ -93,11 +110,9 @@ def build(force: bool = False, verbose: bool = False, extra_defines: list[str] |
             stale = True
         if not stale:
             continue
+        cmd = unit_command(src) + ["-c", "-o", op]
         if kind == "hip":
-            cmd = [HIPCC, f"--offload-arch={ARCH}", "-x", "hip"] + COMMON + extra + (extra_defines or []) + \
-                  ([f'-DMX_SRC_SHA="{sha}"'] if ident else []) + ["-c", sp, "-o", op]
-        else:
-            cmd = [CXX, "-O2", "-std=c++17", "-fPIC", "-Wall"] + extra + ["-c", sp, "-o", op]
+            cmd += (extra_defines or []) + ([f'-DMX_SRC_SHA="{sha}"'] if ident else [])
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)

@@ -4,7 +4,7 @@
 // transform entry point needs a live gfx950 device and fails with MX_ERR_DEVICE otherwise.
 //
 // A call the arena holds in one chunk runs its kernels once each; what does not fit is walked chunk by chunk.  What one chunk
-// hands the next is what one rank of a multi-GPU run hands its neighbour (pv_kernels.hip, mx_pv_shard_*): the frame before the
+// hands the next is what one rank of a multi-GPU run hands its neighbour (pv_common.h, mx_pv_shard_*): the frame before the
 // chunk is analysed again as its row 0, the dense offset row behind the chunk's last frame is the next chunk's carry_in, and the
 // N - Hs samples across the boundary are the left chunk's raw tail plus the right chunk's raw head.  Chunks start on multiples
 // of 32 frames (= the synthesis workgroups), so every float sum groups exactly as in one launch over the whole signal: outputs

@@ -34,8 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
-#include "stft_core.h"
-#include "stft_kernel_impl.h"  // wave_reduce_u32
+#include "wave_walk.h"
 
 namespace mx {
 namespace {
@@ -52,20 +51,6 @@ __device__ __forceinline__ int dd_idx(int i) { return i + (i >> 4); }
 constexpr int kSqLen = kF0N + kF0N / 32 + 1;
 constexpr int kDdLen = kF0W + kF0W / 16 + 2;
 static_assert(kDdLen <= 2 * kF0M, "d fits the FFT image (as floats)");
-
-// inclusive sum over the 64 lanes of a wavefront (row_shr 1, 2, 4, 8; row_bcast:15, row_bcast:31), f32
-__device__ __forceinline__ float wave_scan_addf(float x) {
-#define MX_SCAN_STEP(CTRL, ROWS) \
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROWS, 0xf, false));
-  MX_SCAN_STEP(0x111, 0xf)
-  MX_SCAN_STEP(0x112, 0xf)
-  MX_SCAN_STEP(0x114, 0xf)
-  MX_SCAN_STEP(0x118, 0xf)
-  MX_SCAN_STEP(0x142, 0xa)
-  MX_SCAN_STEP(0x143, 0xc)
-#undef MX_SCAN_STEP
-  return x;
-}
 
 // max |x| over the thread's 32 samples and then the wavefront, as float bits (|x| orders as its bits; NaN above Inf)
 __device__ __forceinline__ unsigned wave_absmax_bits(const cpx (&xr)[FP::E]) {
@@ -109,16 +94,8 @@ __device__ __forceinline__ void f0_passes(int t, bool wave0, const cpx (&Y)[FP::
   store_t2<P>(t, v, img);
   __syncthreads();
   load_t2<P>(t, v, img);
-  cpx g1 = w3b[0];
-  asm volatile("" : "+v"(g1.x), "+v"(g1.y));  // (not hoisted out of the frame loop)
   cpx w3r[P::R3 - 1];
-  w3r[0] = g1;
-  w3r[1] = w3b[1];
-  w3r[3] = w3b[2];
-  w3r[2] = pk_cmul2(w3b[1], g1);
-  w3r[4] = pk_cmul2(w3b[2], g1);
-  w3r[5] = pk_cmul2(w3b[2], w3b[1]);
-  w3r[6] = pk_cmul2(w3b[2], w3r[2]);
+  root_powers7(w3b, w3r);
   if (wave0) pass3_reg<P, true>(t, v, w3r);
   else pass3_reg<P, false>(t, v, w3r);
 }
@@ -131,15 +108,7 @@ __device__ __forceinline__ void f0_forward(int t, bool wave0, const cpx (&Y)[FP:
   cpx v[P::E];
   f0_passes(t, wave0, Y, v, img, ltw2, w3b);
   ny = 2.0f * (v[0].x - v[0].y);  // X[M] = Re Z[0] - Im Z[0] (thread 0's P-butterfly element 0)
-  cpx ulo = ulo0, uhi = uhi0, u[P::R3];
-  asm volatile("" : "+v"(ulo.x), "+v"(ulo.y), "+v"(uhi.x), "+v"(uhi.y));
-  if (wave0) {
-    PostFly<P, 0>::run(ulo, uhi, u);
-    post_cplx<P, true>(t, v, u, X);
-  } else {
-    PostFly<P, 0>::run(ulo, ulo, u);
-    post_cplx<P, false>(t, v, u, X);
-  }
+  post_split<P>(t, wave0, ulo0, uhi0, v, X);
 }
 
 // block minimum of a u64 key over the two wavefronts (slot: two LDS words per call site)
@@ -167,23 +136,13 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
   cpx ulo0, uhi0;
   post_bases<P>(t_, a.ubase, ulo0, uhi0);
   cpx w3b[3];
-  {
-    const int col = t_ ? t_ : P::NS3 / 2;
-    w3b[0] = a.tw3[0 * P::NS3 + col];
-    w3b[1] = a.tw3[1 * P::NS3 + col];
-    w3b[2] = a.tw3[3 * P::NS3 + col];
-  }
+  load_w3_bases<P>(a.tw3, t_ ? t_ : P::NS3 / 2, w3b);
   // e^{+2 pi i c/N} for the thread's points c = t + T e: e^{+2 pi i t/N} (ubase[t] = i e^{-2 pi i t/N} = (sin, cos))
   // times e^{2 pi i e/32} (compile-time)
   const cpx wb = mk(a.ubase[t_].y, a.ubase[t_].x);
   for (int i = t_; i < P::TW2; i += P::T) ltw2[i] = a.tw2[i];
 
-  // XCD-aware block -> frame-run map (as stft_kernel): neighbouring runs share their samples in one XCD's L2
-  unsigned lb = blockIdx.x;
-  {
-    const unsigned nb = gridDim.x, xcd = lb & 7u, q = nb >> 3, rr = nb & 7u;
-    lb = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (lb >> 3);
-  }
+  const unsigned lb = xcd_block(blockIdx.x, gridDim.x);
   const int64_t f0 = (int64_t)lb * a.frames_per_block;
   const int64_t f1 = f0 + a.frames_per_block < a.count ? f0 + a.frames_per_block : a.count;
   if (f0 >= f1) return;
@@ -228,7 +187,7 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
 #pragma unroll
       for (int j = 0; j < 32; ++j) run += s[j];
     }
-    const float incl = wave_scan_addf(run);
+    const float incl = wave_scan_add(run);
     if (lane == 63) wtot[t >> 6] = incl;
     // X = DFT(x); the next frame's samples travel under the rest of this one
 #pragma unroll
@@ -299,7 +258,7 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
       dv[j] = dd[dd_idx(16 * t + 1 + j)];
       crun += dv[j];
     }
-    const float cinc = wave_scan_addf(crun);
+    const float cinc = wave_scan_add(crun);
     if (lane == 63) wtot[t >> 6] = cinc;
     __syncthreads();
     float cum = cinc - crun + (wave0 ? 0.f : wtot[0]);

@@ -53,7 +53,7 @@ struct ResynthArgs {
 };
 hipError_t launch_resynth(const ResynthArgs &a, hipStream_t s);
 
-// Build-defined phase-vocoder pitch shifter (pv_kernels.hip; no reference counterpart).
+// Build-defined phase-vocoder pitch shifter (pv_common.h and its units pv_*.hip; no reference counterpart).
 struct PvArgs {
   const float *audio;  // padded image (zeros in the pads)
   int64_t n;
@@ -124,7 +124,7 @@ struct PvArgs {
 hipError_t launch_pv(const PvArgs &a, hipStream_t s);
 hipError_t launch_pv_analyze(const PvArgs &a, hipStream_t s);
 hipError_t launch_pv_synthesize(const PvArgs &a, hipStream_t s);
-// the same stages in the pieces the chunked pipeline puts on streams of their own (pv_kernels.hip: launch_pv_analyze =
+// the same stages in the pieces the chunked pipeline puts on streams of their own (pv_synthesis.hip: launch_pv_analyze =
 // analysis + maps, launch_pv_synthesize = offsets + synthesis)
 hipError_t launch_pv_analysis(const PvArgs &a, hipStream_t s);
 hipError_t launch_pv_maps(const PvArgs &a, hipStream_t s);

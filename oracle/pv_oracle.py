@@ -43,7 +43,8 @@ The phase bookkeeping is integer (the one binary64 product is rounded identicall
 update is a map k -> (source bin, delta) or a restart, so composing those maps in any grouping — a parallel
 scan over frames — gives exactly the serial result.
 
-How the product evaluates this definition (round 4; melonix_amd/csrc/pv_kernels.hip): with identity phase locking
+How the product evaluates this definition (round 4; melonix_amd/csrc/pv_common.h names the stages,
+pv_analysis.hip / pv_lock.hip / pv_synthesis.hip hold them): with identity phase locking
 Phi_f[k] - P_f[k] = C_f[p] is one number per PEAK (p = the owner of k), so the synthesis coefficient
 |X_f[k]| e^{2 pi i Phi_f[k]/2^32} equals X_f[k] e^{2 pi i C_f[p]/2^32} up to the 2^-31-turn quantisation of P_f[k]
 (3e-9 rad).  The product therefore keeps phases at the peaks only — the same uint32 arithmetic as above on the same

@@ -65,11 +65,41 @@ def test_fails_loudly_without_gpu(mxlib):
     assert e.value.code == -2 and "no CPU path" in str(e.value)
 
 
+def _resource_usage(unit):
+    """(kernel names, scratch bytes per lane, VGPRs) of a unit of build.UNITS, compiled as the build compiles it."""
+    from melonix_amd import build
+
+    out = subprocess.run(build.unit_command(unit) + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", out.stderr)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
+    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
+    assert len(names) == len(scratch) == len(vgprs)
+    return names, scratch, vgprs
+
+
+def _lds_audited(unit, tmp_path):
+    """Kernels of a unit of build.UNITS that tools/lds_audit.py walked, in the ISA the build's own command gives: no findings."""
+    import sys
+
+    from melonix_amd import build
+
+    asm = tmp_path / (unit + ".s")
+    out = subprocess.run(build.unit_command(unit) + ["--cuda-device-only", "-S", "-o", str(asm)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    aud = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lds_audit.py"), str(asm)], capture_output=True, text=True)
+    assert aud.returncode == 0, aud.stdout[-3000:]
+    m = re.fullmatch(r"(\d+) kernel\(s\) audited, 0 finding\(s\)", aud.stdout.splitlines()[-1])
+    assert m, aud.stdout[-500:]
+    return int(m.group(1))
+
+
 def test_resampler_isa_has_no_fma():
     """resynth_kernels.hip must not contract (1-f)*a + f*b (bit-exact PCM)."""
-    src = os.path.join(ROOT, "melonix_amd", "csrc", "resynth_kernels.hip")
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S",
-                          "--cuda-device-only", "-x", "hip", src, "-o", "-"], capture_output=True, text=True)
+    from melonix_amd import build
+
+    out = subprocess.run(build.unit_command("resynth_kernels.hip") + ["-S", "--cuda-device-only", "-o", "-"], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     body = out.stdout  # every kernel of the file: scalar, LDS-staged vector and long-grain resamplers
     assert body.count("s_endpgm") >= 4
@@ -79,14 +109,8 @@ def test_resampler_isa_has_no_fma():
 
 def test_stft_kernels_do_not_spill():
     """Every shipped STFT kernel instantiation must be scratch-free (a silent spill cost ~7 % once)."""
-    src = os.path.join(ROOT, "melonix_amd", "csrc", "stft_kernels.hip")
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-ffp-contract=off", "-c", "-x", "hip", src,
-                          "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
-    assert len(names) == len(scratch) == len(vgprs) and len(names) >= 9
+    names, scratch, vgprs = _resource_usage("stft_kernels.hip")
+    assert len(names) >= 9
     # no exceptions (round 3: the three kernels that parked 12-24 bytes per lane lost thread 0's second post-split base
     # register — it is re-selected per frame in the one wavefront that holds thread 0 — and are scratch-free as well)
     bad = [(n, sc) for n, sc in zip(names, scratch) if "stft_kernel" in n and sc != 0]
@@ -97,35 +121,33 @@ def test_stft_kernels_do_not_spill():
 def test_pv_kernels_do_not_spill():
     """The phase-vocoder kernels share the FFT passes; the synthesis kernel lives close to the 256-VGPR line
     (its window and split twiddles stay in registers): keep it scratch-free."""
-    src = os.path.join(ROOT, "melonix_amd", "csrc", "pv_kernels.hip")
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-ffp-contract=off", "-c", "-x", "hip", src,
-                          "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
-    assert len(names) == len(scratch) == len(vgprs) and len(names) >= 7
-    assert not [(n, s) for n, s in zip(names, scratch) if s != 0]
-    assert max(vgprs) <= 256
+    from melonix_amd import build
+
+    assert len(build.PV_UNITS) == 3
+    total = 0
+    for unit in build.PV_UNITS:
+        names, scratch, vgprs = _resource_usage(unit)
+        assert names, unit
+        assert not [(n, s) for n, s in zip(names, scratch) if s != 0], unit
+        assert max(vgprs) <= 256, unit
+        total += len(names)
+    assert total >= 12  # every kernel of the three stages reported
 
 
-@pytest.mark.parametrize("unit", ["stft_kernels.hip", "pv_kernels.hip"])
+@pytest.mark.parametrize("unit", ["stft_kernels.hip", "pv_units"])
 def test_hand_issued_lds_reads_are_covered_by_their_waits(unit, tmp_path):
     """The transposition reads are inline-asm ds_read_b64 behind a hand-placed s_waitcnt (stft_core.h lds_rd64 / lds_wait):
     hipcc neither counts them nor knows their destinations are invalid until that wait.  tools/lds_audit.py walks the
     ISA of every instantiation with the hardware's LGKM queue: no instruction may touch a destination register between its
     read and the wait that covers it (round 4 found — and removed — a v_mov that copied one into an unused pad register),
-    no scalar memory operation may be in flight at a counted wait."""
-    import sys
-    src = os.path.join(ROOT, "melonix_amd", "csrc", unit)
-    asm = tmp_path / (unit + ".s")
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-ffp-contract=off", "-x", "hip",
-                          "--cuda-device-only", "-S", src, "-o", str(asm)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    aud = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lds_audit.py"), str(asm)], capture_output=True, text=True)
-    assert aud.returncode == 0, aud.stdout[-3000:]
-    m = re.fullmatch(r"(\d+) kernel\(s\) audited, 0 finding\(s\)", aud.stdout.splitlines()[-1])
-    assert m and int(m.group(1)) >= 7, aud.stdout[-500:]
+    no scalar memory operation may be in flight at a counted wait.  `pv_units`: every phase-vocoder unit of the build."""
+    from melonix_amd import build
+
+    if unit == "pv_units":
+        assert len(build.PV_UNITS) == 3
+        assert sum(_lds_audited(u, tmp_path) for u in build.PV_UNITS) >= 12
+    else:
+        assert _lds_audited(unit, tmp_path) >= 7
 
 
 def test_kept_traffic_figure_belongs_to_the_shipped_kernel_sources():

@@ -199,8 +199,9 @@ def test_reference_fft_matches_the_literal_sum():
 
 
 def _kernel_cmd(extra):
-    src = os.path.join(ROOT, "melonix_amd", "csrc", "f0_kernels.hip")
-    return ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-ffp-contract=off", "-x", "hip", src] + extra
+    from melonix_amd import build
+
+    return build.unit_command("f0_kernels.hip") + extra
 
 
 def test_f0_kernel_is_scratch_free():
