@@ -394,7 +394,7 @@ void mx_minmax_range(const float *host_wav, int64_t n, const float *picks, const
  * Defaults fmin = 55, fmax = 1760 Hz (notes 24..84), threshold 0.15.  Note law (mx_bin_note's):
  * note = 24 + 12*log2(sr / period / 55). */
 typedef struct mx_f0 {
-  int32_t tau;        /* tau* (0: silent frame) */
+  int32_t tau;        /* tau* (0: silent, or unvoiced in a decoded track) */
   float period;       /* tau* + parabolic offset, samples (0: silent) */
   float aperiodicity; /* d'(tau*) (1: silent) */
   float rms;          /* sqrt(sum x_j^2 / N) over the frame (0: silent) */
@@ -408,6 +408,80 @@ int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t
 /* Same, the records stay in HBM (count x 16 bytes).  Asynchronous on the context's stream. */
 int mx_f0_track_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                     float fmin, float fmax, float threshold, mx_f0 *d_out);
+
+/* ---- Candidate ladder and Viterbi f0 decoding (BUILD-DEFINED, like the tracker; restated by tests/f0_decode_ref.py) ----
+ * One YIN pick per frame looks at no other frame: where a subharmonic or a strong partial lifts d' at the true period
+ * just above the threshold, "the first dip under theta" lands an octave away for a few frames.  The ladder keeps several
+ * period candidates per frame and the decoder picks one path through the whole take.
+ *
+ * Candidate ladder.  Per frame, with d' and the search range of the YIN section above:
+ *   rungs     theta_k = threshold * {2, 1, 1/2, 1/4}, k = 0..3, formed in f32;
+ *   rung k    the tracker's tau* rule with theta_k: the first tau in range with d' < theta_k, then forward while
+ *             d'(tau+1) < d'(tau) and tau+1 <= tau_max; no tau under theta_k: the rung is empty;
+ *   fallback  rung 0 empty: slot 0 takes the argmin of d' over the range (lowest tau on ties), YIN's own fallback;
+ *   a rung whose tau equals an earlier rung's is empty; a slot whose d' is not finite is empty; a silent frame (all
+ *   samples zero) has four empty slots.
+ *   Empty slot: {0, 0.f, 1.f, 0}.  Filled slot: period and aperiodicity by the tracker's arithmetic at that tau, and
+ *   cents = (int32_t)rintf(1200.f * log2f((float)sr / period / 55.f)) + 2400 (100 x the note of mx_bin_note's law).
+ * Wherever the plain record has aperiodicity < threshold, some slot has its tau and the same period and aperiodicity
+ * bits.  Like the plain record a frame's slots depend on nothing but its samples: the same bytes whatever the launch split. */
+#define MX_F0_CANDS 4
+typedef struct mx_f0_cand {
+  int32_t tau;        /* the rung's tau (0: empty slot) */
+  float period;       /* tau + parabolic offset, samples (0: empty) */
+  float aperiodicity; /* d'(tau) (1: empty) */
+  int32_t cents;      /* 100 x note, rounded (0: empty) */
+} mx_f0_cand;
+
+/* Frames [first_frame, first_frame + count): MX_F0_CANDS records per frame, slot-major within the frame (frame f's slot k
+ * at d_cands[4 f + k]), in HBM.  d_track may be NULL; otherwise it receives exactly mx_f0_track_dev's bytes, from the same
+ * launch.  Asynchronous on the context's stream.  Argument checks: mx_f0_track's. */
+int mx_f0_candidates_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                         float fmin, float fmax, float threshold, mx_f0 *d_track, mx_f0_cand *d_cands);
+/* Same, host pointers (track may be NULL), through the context's staging buffers.  Blocks. */
+int mx_f0_candidates(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                     float fmin, float fmax, float threshold, mx_f0 *track, mx_f0_cand *cands);
+
+/* Decoder: the cheapest path through the frames' states.  All arithmetic in int64; Q = 65536, q(x) = (int64)rint(x * Q) on
+ * the f32 value, INF = 2^56.  States j = 0..3: the frame's slots (a slot is empty when its tau is <= 0); j = 4: unvoiced.
+ *   O_f(j)     min(q(aperiodicity), 2Q) for a filled slot (at least 0; 2Q for a NaN), INF for an empty one,
+ *              q(unvoiced_cost) for j = 4;
+ *   T_f(i, j)  between frames f-1 and f: 0 for 4 -> 4; q(switch_cost) between 4 and a slot, either way; between two filled
+ *              slots q(jump_cost) * min(|cents_j - cents_i|, max_jump_cents) / 100 (integer division); 0 where either
+ *              slot is empty;
+ *   V_0(j) = O_0(j); V_f(j) = min_i (V_{f-1}(i) + T_f(i, j)) + O_f(j), bp_f(j) the lowest i attaining the minimum;
+ *   the end state is the lowest j attaining min V_{F-1}, s_{f-1} = bp_f(s_f).  The path never enters an empty slot: the
+ *   all-unvoiced path costs at most count * 16 * Q < INF.
+ * Output record of frame f: the chosen slot's {tau, period, aperiodicity} with rms from track[f]; {0, 0.f, 1.f,
+ * track[f].rms} where the path is unvoiced.  Output state: one uint8_t per frame, 0..4.
+ * The device walks the take in chunks (min-plus products per chunk, one pass over the chunks, a re-walk per chunk; the
+ * maps bp the same way backwards): no kernel takes more than max(chunk, count / chunk) dependent steps, and integers make
+ * every V_f, hence the path, independent of the chunk length.
+ * Defaults {0.3, 0.1, 0.5, 1200}.  Nobody has tuned them on recorded voices: they are values for which the f64 reference
+ * decodes tests/f0_decode_ref.py's GLITCH signal (a steady 220 Hz tone with subharmonic and second-partial bursts: 18
+ * plain frames an octave down, 5 notes) cleanly: no frame off, 1 note.  At switch_cost 0.1 the path escapes through the
+ * unvoiced state instead and 28 of the 359 frames 8..F-9 come out wrong. */
+typedef struct mx_f0_decode_params {
+  float unvoiced_cost, jump_cost, switch_cost; /* each finite, in [0, 16] */
+  int32_t max_jump_cents;                      /* in [0, 12000] */
+} mx_f0_decode_params;
+/* {0.3f, 0.1f, 0.5f, 1200} */
+void mx_f0_decode_params_default(mx_f0_decode_params *p);
+/* count frames: d_track (rms), d_cands (4 per frame) -> d_out (may alias d_track) and d_state (may be NULL), all in HBM.
+ * p NULL: the defaults.  Asynchronous on the context's stream.  Work memory (2 bytes per frame and 202 per chunk) belongs
+ * to the context, kept between calls, released by mx_ctx_release_scratch; MX_ERR_NOMEM when it cannot be had.
+ * MX_ERR_INVALID for a cost outside [0, 16] or not finite, or max_jump_cents outside [0, 12000]. */
+int mx_f0_decode_dev(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, int64_t count,
+                     const mx_f0_decode_params *p, mx_f0 *d_out, uint8_t *d_state);
+/* Same, host pointers (state may be NULL; out may alias track).  Blocks. */
+int mx_f0_decode(mx_ctx *ctx, const mx_f0 *track, const mx_f0_cand *cands, int64_t count, const mx_f0_decode_params *p,
+                 mx_f0 *out, uint8_t *state);
+/* Candidates and decode in one call: the decoded track of frames [first_frame, first_frame + count), host output. */
+int mx_f0_track_decoded(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                        float fmin, float fmax, float threshold, const mx_f0_decode_params *p, mx_f0 *out);
+/* Frames per chunk of the decode (0: the default, about sqrt(count) / 3).  For tests, like mx_pv_set_chunk_frames: the output
+ * does not depend on it. */
+int mx_f0_decode_set_chunk(mx_ctx *ctx, int64_t frames);
 
 /* Notes (host, double).  A frame is voiced when tau > 0, aperiodicity < threshold and rms >= rms_floor.  A note is a
  * maximal run of voiced frames; a new run starts before frame f when |m_f - m_{f-1}| > max_jump or

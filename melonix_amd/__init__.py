@@ -14,11 +14,11 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import F0_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, PITCH_DTYPE, STEP_DTYPE, MxError  # noqa: F401
+from ._capi import F0_CAND_DTYPE, F0_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, PITCH_DTYPE, STEP_DTYPE, MxError  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
-           "F0_DTYPE", "NOTE_DTYPE", "MARKER_DTYPE", "note_params_default", "detect_notes", "correction_markers"]
+           "F0_DTYPE", "F0_CAND_DTYPE", "f0_decode_params_default", "NOTE_DTYPE", "MARKER_DTYPE", "note_params_default", "detect_notes", "correction_markers"]
 
 
 def _ptr(a):
@@ -249,6 +249,57 @@ class Context:
         """The records stay in HBM at d_out (count x 16 bytes); asynchronous on the context's stream."""
         _capi.check(_capi.lib().mx_f0_track_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
                                                 C.c_void_p(d_out or 0)))
+
+    # ---- candidate ladder and Viterbi decode (build-defined) ----
+    def f0_candidates(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
+                      fmin: float = 55.0, fmax: float = 1760.0, threshold: float = 0.15):
+        """-> (track: F0_DTYPE records, exactly f0_track's; cands: count x 4 F0_CAND_DTYPE, the frames' candidate ladders)."""
+        if count is None:
+            count = frame_count(audio.n, hop) - first
+        track = np.empty(max(count, 0), dtype=F0_DTYPE)
+        cands = np.empty((max(count, 0), _capi.F0_CANDS), dtype=F0_CAND_DTYPE)
+        _capi.check(_capi.lib().mx_f0_candidates(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
+                                                 _ptr(track), _ptr(cands)))
+        return track, cands
+
+    def f0_candidates_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_track: int | None, d_cands: int,
+                          fmin: float = 55.0, fmax: float = 1760.0, threshold: float = 0.15):
+        """The ladders stay in HBM at d_cands (count x 64 bytes), the plain records at d_track (count x 16 bytes; None: not
+        wanted); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_f0_candidates_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
+                                                     C.c_void_p(d_track or 0), C.c_void_p(d_cands or 0)))
+
+    def f0_decode(self, track, cands, **params):
+        """The cheapest path through the frames' candidates and the unvoiced state -> (decoded F0_DTYPE track, uint8 state
+        per frame: the slot taken, 4 = unvoiced).  params: fields of f0_decode_params_default()."""
+        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+        cands = np.ascontiguousarray(cands, dtype=F0_CAND_DTYPE).reshape(-1, _capi.F0_CANDS)
+        if len(cands) != len(track):
+            raise ValueError("one row of candidates per frame of the track")
+        out = np.empty(len(track), dtype=F0_DTYPE)
+        state = np.empty(len(track), dtype=np.uint8)
+        _capi.check(_capi.lib().mx_f0_decode(self.handle, _ptr(track), _ptr(cands), len(track), _decode_params(params),
+                                             _ptr(out), _ptr(state)))
+        return out, state
+
+    def f0_decode_dev(self, d_track: int, d_cands: int, count: int, d_out: int, d_state: int | None = None, **params):
+        """Device pointers (d_out may be d_track; d_state None: not wanted); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_f0_decode_dev(self.handle, C.c_void_p(d_track or 0), C.c_void_p(d_cands or 0), count,
+                                                 _decode_params(params), C.c_void_p(d_out or 0), C.c_void_p(d_state or 0)))
+
+    def f0_track_decoded(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
+                         fmin: float = 55.0, fmax: float = 1760.0, threshold: float = 0.15, **params):
+        """Candidates and decode in one call -> the decoded F0_DTYPE track (tau 0: silent or unvoiced)."""
+        if count is None:
+            count = frame_count(audio.n, hop) - first
+        out = np.empty(max(count, 0), dtype=F0_DTYPE)
+        _capi.check(_capi.lib().mx_f0_track_decoded(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
+                                                    _decode_params(params), _ptr(out)))
+        return out
+
+    def f0_decode_set_chunk(self, frames: int):
+        """Frames per chunk of the decode's scans (0 = the default); for tests: the output does not depend on it."""
+        _capi.check(_capi.lib().mx_f0_decode_set_chunk(self.handle, int(frames)))
 
     # ---- grains / resynthesis ----
     def grains_dev(self, audio: Audio):
@@ -494,6 +545,25 @@ def column_range(markers, sr, time, width, range_time):
 
 
 # ---- notes and correction markers (host; build-defined) ----
+def f0_decode_params_default() -> dict:
+    p = _capi.F0DecodeParams()
+    _capi.lib().mx_f0_decode_params_default(C.byref(p))
+    return {k: getattr(p, k) for k, _ in _capi.F0DecodeParams._fields_}
+
+
+def _decode_params(params: dict):
+    """The defaults with `params` over them, for the C-ABI; nothing given: NULL (the library's defaults)."""
+    if not params:
+        return None
+    d = f0_decode_params_default()
+    unknown = set(params) - set(d)
+    if unknown:
+        raise TypeError(f"unknown decode parameters {sorted(unknown)}")
+    d.update(params)
+    return C.byref(_capi.F0DecodeParams(float(d["unvoiced_cost"]), float(d["jump_cost"]), float(d["switch_cost"]),
+                                        int(d["max_jump_cents"])))
+
+
 def note_params_default() -> dict:
     p = _capi.NoteParams()
     _capi.lib().mx_note_params_default(C.byref(p))

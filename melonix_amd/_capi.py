@@ -43,6 +43,15 @@ class F0(C.Structure):
     _fields_ = [("tau", C.c_int32), ("period", C.c_float), ("aperiodicity", C.c_float), ("rms", C.c_float)]
 
 
+class F0Cand(C.Structure):
+    _fields_ = [("tau", C.c_int32), ("period", C.c_float), ("aperiodicity", C.c_float), ("cents", C.c_int32)]
+
+
+class F0DecodeParams(C.Structure):
+    _fields_ = [("unvoiced_cost", C.c_float), ("jump_cost", C.c_float), ("switch_cost", C.c_float),
+                ("max_jump_cents", C.c_int32)]
+
+
 class NoteParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("rms_floor", C.c_float), ("max_jump", C.c_double), ("max_dev", C.c_double),
                 ("min_frames", C.c_int32)]
@@ -57,13 +66,15 @@ PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
 F0_DTYPE = np.dtype([("tau", "<i4"), ("period", "<f4"), ("aperiodicity", "<f4"), ("rms", "<f4")])
+F0_CANDS = 4
+F0_CAND_DTYPE = np.dtype([("tau", "<i4"), ("period", "<f4"), ("aperiodicity", "<f4"), ("cents", "<i4")])
 NOTE_DTYPE = np.dtype([("start_sample", "<i4"), ("end_sample", "<i4"), ("first_frame", "<i4"), ("frames", "<i4"),
                        ("note", "<f8"), ("aperiodicity", "<f4"), ("spread", "<f4")])
 MARKER_DTYPE = np.dtype({"names": ["sample", "note", "dTime", "pitchBend"], "formats": ["<i4", "<f8", "<f8", "<f8"],
                          "offsets": [0, 8, 16, 24], "itemsize": 32})
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
-assert MARKER_DTYPE.itemsize == C.sizeof(Marker)
+assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
 
 # name -> (restype, argtypes); kept in the order of include/melonix_amd.h
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -145,6 +156,13 @@ SIGNATURES = {
     "mx_minmax_range": (None, [_vp, _i64, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f)]),
     "mx_f0_track": (_i, [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f, _vp]),
     "mx_f0_track_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f, _vp]),
+    "mx_f0_candidates_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f, _vp, _vp]),
+    "mx_f0_candidates": (_i, [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f, _vp, _vp]),
+    "mx_f0_decode_params_default": (None, [C.POINTER(F0DecodeParams)]),
+    "mx_f0_decode_dev": (_i, [_vp, _vp, _vp, _i64, C.POINTER(F0DecodeParams), _vp, _vp]),
+    "mx_f0_decode": (_i, [_vp, _vp, _vp, _i64, C.POINTER(F0DecodeParams), _vp, _vp]),
+    "mx_f0_track_decoded": (_i, [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f, C.POINTER(F0DecodeParams), _vp]),
+    "mx_f0_decode_set_chunk": (_i, [_vp, _i64]),
     "mx_note_params_default": (None, [C.POINTER(NoteParams)]),
     "mx_detect_notes": (_i, [_vp, _i64, _i, _i, _i64, C.POINTER(NoteParams), C.POINTER(C.POINTER(Note)), C.POINTER(_i64)]),
     "mx_correction_markers": (_i, [_vp, _i64, _d, _i, _vp]),

@@ -39,6 +39,8 @@ UNITS = [
     ("pv_synthesis.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     # build-defined YIN f0 tracker: three transforms per frame on the same FFT passes
     ("f0_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # build-defined Viterbi decode over the YIN candidate ladder: integer min-plus scans, no floating point beyond q()
+    ("f0_decode.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),

@@ -7,8 +7,8 @@ namespace melonix {
 static_assert(sizeof(Marker) == sizeof(mx_marker), "Marker must stay layout-compatible with mx_marker");
 
 PitchTrack::PitchTrack(std::span<const float> wav, int sampleRate, int hop, float fmin, float fmax, float threshold,
-                       int device)
-    : sampleRate(sampleRate), hop_(hop) {
+                       int device, bool decoded)
+    : sampleRate(sampleRate), hop_(hop), threshold_(threshold), decoded_(decoded) {
   mx_ctx *ctx = nullptr;
   if (mx_ctx_create(device, &ctx) != MX_OK) return;
   mx_audio *audio = nullptr;
@@ -16,7 +16,8 @@ PitchTrack::PitchTrack(std::span<const float> wav, int sampleRate, int hop, floa
     const int64_t frames = mx_frame_count((int64_t)wav.size(), hop);
     if (frames >= 0) {
       track.resize((size_t)frames);
-      good = mx_f0_track(ctx, audio, sampleRate, hop, 0, frames, fmin, fmax, threshold, track.data()) == MX_OK;
+      good = (decoded ? mx_f0_track_decoded(ctx, audio, sampleRate, hop, 0, frames, fmin, fmax, threshold, nullptr, track.data())
+                      : mx_f0_track(ctx, audio, sampleRate, hop, 0, frames, fmin, fmax, threshold, track.data())) == MX_OK;
       if (!good) track.clear();
     }
     mx_audio_free(ctx, audio);
@@ -27,6 +28,7 @@ PitchTrack::PitchTrack(std::span<const float> wav, int sampleRate, int hop, floa
 std::vector<mx_note> PitchTrack::notes() const {
   mx_note_params p;
   mx_note_params_default(&p);
+  if (decoded_) p.threshold = 2.f * threshold_;
   return notes(p);
 }
 

@@ -18,14 +18,17 @@ namespace melonix {
 class PitchTrack {
 public:
   // hop: samples between frame centres; fmin / fmax / threshold: the tracker's band and YIN threshold
+  // decoded: frames() holds the Viterbi-decoded track (mx_f0_track_decoded, default parameters) instead of the plain one: one
+  // path through each frame's candidate ladder, which does not jump an octave for a few frames where plain YIN does
   PitchTrack(std::span<const float> wav, int sampleRate, int hop = 256, float fmin = 55.f, float fmax = 1760.f,
-             float threshold = 0.15f, int device = 0);
+             float threshold = 0.15f, int device = 0, bool decoded = false);
 
   bool ok() const { return good; }
   int hop() const { return hop_; }
   // one record per frame h (centred on sample h * hop)
   const std::vector<mx_f0> &frames() const { return track; }
-  // notes with the default parameters (mx_note_params_default), or with `p`
+  // notes with the default parameters (mx_note_params_default), or with `p`.  On a decoded track the defaults take
+  // threshold = 2 x the tracker's: the decoder has made the voicing decision, and its candidates reach up to 2 theta
   std::vector<mx_note> notes() const;
   std::vector<mx_note> notes(const mx_note_params &p) const;
   // two markers per note: strength in [0, 1], scaleMask bits 0..11 = pitch classes (A = 0), 0 = all twelve
@@ -33,6 +36,8 @@ public:
 
 private:
   int sampleRate, hop_;
+  float threshold_;
+  bool decoded_;
   bool good = false;
   std::vector<mx_f0> track;
 };

@@ -211,6 +211,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
     for (auto &st : ctx->stage) st.drop();
     for (auto &st : ctx->chain) st.drop();
+    for (auto &st : ctx->f0dec) st.drop();
     pv_release(ctx);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -259,6 +260,10 @@ int mx_ctx_release_scratch(mx_ctx *ctx) {
       std::lock_guard<std::mutex> lk(ctx->zc_mu);
       ctx->zc_scratch = ZcBitmaps{};
       for (auto &st : ctx->chain) st.drop();
+    }
+    {
+      std::lock_guard<std::mutex> lk(ctx->f0_mu);
+      for (auto &st : ctx->f0dec) st.drop();
     }
     return MX_OK;
   });

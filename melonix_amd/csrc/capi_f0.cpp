@@ -1,5 +1,5 @@
-// capi_f0.cpp — the YIN f0 tracker (f0_kernels.hip), notes and correction markers (f0_notes.cpp): BUILD-DEFINED, the
-// reference has no detector.  One unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).
+// capi_f0.cpp — the YIN f0 tracker and its candidate ladder (f0_kernels.hip), the Viterbi decode over the ladder
+// (f0_decode.hip), notes and correction markers (f0_notes.cpp): BUILD-DEFINED, the reference has no detector.  One unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).
 #include "capi_internal.h"
 #include "f0_notes.h"
 
@@ -36,8 +36,9 @@ int f0_check(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t fi
   return f0_range(sampleRate, fmin, fmax, tmin, tmax);
 }
 
+// d_cands set: the ladder instantiation (d_out may then be null); sampleRate: the ladder's cents
 int f0_launch(mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_frame, int64_t count, int tmin, int tmax,
-              float threshold, mx_f0 *d_out) {
+              float threshold, mx_f0 *d_out, mx_f0_cand *d_cands = nullptr, int sampleRate = 0) {
   HIP_TRY(hipSetDevice(ctx->device));
   NTables t;
   if (const int rc = get_tables(ctx, 4096, t)) return rc;
@@ -53,8 +54,86 @@ int f0_launch(mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_frame, int6
   g.tw3 = t.tw3;
   g.ubase = t.ubase;
   g.out = d_out;
+  g.cands = d_cands;
+  g.sample_rate = sampleRate;
   HIP_TRY(launch_f0(g, ctx->stream));
   return MX_OK;
+}
+
+const mx_f0_decode_params kDecodeDefaults{0.3f, 0.1f, 0.5f, 1200};
+
+// the parameters in force (p null: the defaults), checked
+int decode_params(const mx_f0_decode_params *p, mx_f0_decode_params &out) {
+  out = p ? *p : kDecodeDefaults;
+  for (const float c : {out.unvoiced_cost, out.jump_cost, out.switch_cost})
+    if (!std::isfinite(c) || c < 0.f || c > 16.f) return fail(MX_ERR_INVALID, "decode cost %g outside [0, 16]", (double)c);
+  if (out.max_jump_cents < 0 || out.max_jump_cents > 12000)
+    return fail(MX_ERR_INVALID, "max_jump_cents %d outside [0, 12000]", out.max_jump_cents);
+  return MX_OK;
+}
+
+int64_t q16(float x) { return (int64_t)std::rint((double)x * 65536.0); }
+
+// queues the decode of `count` frames on the context's stream; its work buffers are the context's (f0_mu)
+int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, int64_t count, const mx_f0_decode_params &p,
+                  mx_f0 *d_out, uint8_t *d_state) {
+  if (count == 0) return MX_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> lk(ctx->f0_mu);
+  F0DecodeArgs g{};
+  g.track = d_track;
+  g.cands = d_cands;
+  g.count = count;
+  g.q_unvoiced = q16(p.unvoiced_cost);
+  g.q_jump = q16(p.jump_cost);
+  g.q_switch = q16(p.switch_cost);
+  g.max_jump_cents = p.max_jump_cents;
+  g.chunk = ctx->f0_chunk > 0 ? ctx->f0_chunk : f0_decode_default_chunk(count);
+  const size_t nchunks = (size_t)((count + g.chunk - 1) / g.chunk);
+  hipError_t e = ctx->f0dec[kF0DecBp].get((size_t)count * sizeof(uint16_t), &g.bp);
+  if (e == hipSuccess) e = ctx->f0dec[kF0DecProd].get(nchunks * 25 * sizeof(int64_t), &g.prod);
+  if (e == hipSuccess) e = ctx->f0dec[kF0DecMap].get(nchunks * sizeof(uint16_t), &g.map);
+  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "f0 decode work buffers: %s", hipGetErrorString(e));
+  g.out = d_out;
+  g.state = d_state;
+  HIP_TRY(launch_f0_decode(g, ctx->stream));
+  return MX_OK;
+}
+
+// The host-pointer forms: the records pass through the context's staging buffers (candidates in the magnitude rows' buffer,
+// the track — decoded in place — in the pitch records', states in the texels').  `in`: upload the caller's track and
+// candidates; `run(d_track, d_cands, d_state)` queues the device form; the outputs that are set come back.  Blocks.
+template <class F>
+int f0_staged(mx_ctx *ctx, int64_t count, const mx_f0 *track_in, const mx_f0_cand *cands_in, mx_f0 *track_out,
+              mx_f0_cand *cands_out, uint8_t *state_out, F &&run) {
+  if (count == 0) return MX_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t n = (size_t)count;
+  std::lock_guard<std::mutex> lk(ctx->stage_mu);
+  mx_f0_cand *d_cands = nullptr;
+  mx_f0 *d_track = nullptr;
+  uint8_t *d_state = nullptr;
+  hipError_t e = ctx->stage[kStageMags].get(n * MX_F0_CANDS * sizeof(mx_f0_cand), &d_cands);
+  if (e == hipSuccess) e = ctx->stage[kStagePitch].get(n * sizeof(mx_f0), &d_track);
+  if (e == hipSuccess && state_out) e = ctx->stage[kStageTexels].get(n, &d_state);
+  int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
+  if (rc == MX_OK && track_in) e = hipMemcpyAsync(d_track, track_in, n * sizeof(mx_f0), hipMemcpyHostToDevice, ctx->stream);
+  if (rc == MX_OK && e == hipSuccess && cands_in)
+    e = hipMemcpyAsync(d_cands, cands_in, n * MX_F0_CANDS * sizeof(mx_f0_cand), hipMemcpyHostToDevice, ctx->stream);
+  if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "f0 upload: %s", hipGetErrorString(e));
+  if (rc == MX_OK) rc = run(d_track, d_cands, d_state);
+  if (rc == MX_OK) {
+    if (track_out) e = hipMemcpyAsync(track_out, d_track, n * sizeof(mx_f0), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && cands_out)
+      e = hipMemcpyAsync(cands_out, d_cands, n * MX_F0_CANDS * sizeof(mx_f0_cand), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && state_out) e = hipMemcpyAsync(state_out, d_state, n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "f0 download: %s", hipGetErrorString(e));
+  } else {
+    hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's memory: done before the call returns)
+  }
+  stage_trim(ctx);
+  return rc;
 }
 
 }  // namespace
@@ -91,6 +170,86 @@ int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t
     }
     stage_trim(ctx);
     return rc;
+  });
+}
+
+int mx_f0_candidates_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                         float fmin, float fmax, float threshold, mx_f0 *d_track, mx_f0_cand *d_cands) {
+  return mx_guard([&]() -> int {
+    int tmin = 0, tmax = 0;
+    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
+    if (count > 0 && !d_cands) return fail(MX_ERR_INVALID, "null output");
+    if (count == 0) return MX_OK;
+    return f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_track, d_cands, sampleRate);
+  });
+}
+
+int mx_f0_candidates(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                     float fmin, float fmax, float threshold, mx_f0 *track, mx_f0_cand *cands) {
+  return mx_guard([&]() -> int {
+    int tmin = 0, tmax = 0;
+    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
+    if (count > 0 && !cands) return fail(MX_ERR_INVALID, "null output");
+    return f0_staged(ctx, count, nullptr, nullptr, track, cands, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
+      return f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_track, d_cands, sampleRate);
+    });
+  });
+}
+
+void mx_f0_decode_params_default(mx_f0_decode_params *p) {
+  mx_guard_void([&] {
+    if (p) *p = kDecodeDefaults;
+  });
+}
+
+int mx_f0_decode_dev(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, int64_t count,
+                     const mx_f0_decode_params *p, mx_f0 *d_out, uint8_t *d_state) {
+  return mx_guard([&]() -> int {
+    mx_f0_decode_params dp;
+    if (const int rc = decode_params(p, dp)) return rc;
+    if (!ctx) return fail(MX_ERR_INVALID, "null context");
+    if (count < 0) return fail(MX_ERR_INVALID, "negative frame count");
+    if (count > 0 && (!d_track || !d_cands || !d_out)) return fail(MX_ERR_INVALID, "null argument");
+    return decode_launch(ctx, d_track, d_cands, count, dp, d_out, d_state);
+  });
+}
+
+int mx_f0_decode(mx_ctx *ctx, const mx_f0 *track, const mx_f0_cand *cands, int64_t count, const mx_f0_decode_params *p,
+                 mx_f0 *out, uint8_t *state) {
+  return mx_guard([&]() -> int {
+    mx_f0_decode_params dp;
+    if (const int rc = decode_params(p, dp)) return rc;
+    if (!ctx) return fail(MX_ERR_INVALID, "null context");
+    if (count < 0) return fail(MX_ERR_INVALID, "negative frame count");
+    if (count > 0 && (!track || !cands || !out)) return fail(MX_ERR_INVALID, "null argument");
+    return f0_staged(ctx, count, track, cands, out, nullptr, state, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *d_state) {
+      return decode_launch(ctx, d_track, d_cands, count, dp, d_track, d_state);
+    });
+  });
+}
+
+int mx_f0_track_decoded(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                        float fmin, float fmax, float threshold, const mx_f0_decode_params *p, mx_f0 *out) {
+  return mx_guard([&]() -> int {
+    mx_f0_decode_params dp;
+    if (const int rc = decode_params(p, dp)) return rc;
+    int tmin = 0, tmax = 0;
+    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
+    if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
+    return f0_staged(ctx, count, nullptr, nullptr, out, nullptr, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
+      if (const int rc = f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_track, d_cands, sampleRate))
+        return rc;
+      return decode_launch(ctx, d_track, d_cands, count, dp, d_track, nullptr);
+    });
+  });
+}
+
+int mx_f0_decode_set_chunk(mx_ctx *ctx, int64_t frames) {
+  return mx_guard([&]() -> int {
+    if (!ctx || frames < 0) return fail(MX_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lk(ctx->f0_mu);
+    ctx->f0_chunk = frames;
+    return MX_OK;
   });
 }
 

@@ -143,6 +143,8 @@ struct GrowBuf {
 // under zc_mu): the two predicate bitmaps, the rank tables, the lifting tables
 enum StageSlot { kStageMags, kStagePitch, kStageRanges, kStageTexels, kStageSlots };
 enum ChainSlot { kChainBitmap7, kChainBitmap3, kChainRanks, kChainTables, kChainSlots };
+// work buffers of the f0 decode (mx_ctx::f0dec, under f0_mu): bp rows, chunk products, chunk maps
+enum F0DecSlot { kF0DecBp, kF0DecProd, kF0DecMap, kF0DecSlots };
 
 // Arrays handed to the caller, who frees them with mx_free.  add(): a fresh malloc block of n elements (at least one, so an
 // empty result is not a null pointer), copied from src or, src null, left for a download.  give(): every block is there and
@@ -211,11 +213,16 @@ struct mx_ctx {
   std::mutex zc_mu;
   mx::ZcBitmaps zc_scratch;
   // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
-  // mx_f0_track), kept between calls.  One host-staged call per context at a time.
+  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded), kept between calls.  One host-staged call per context at a time.
   std::mutex stage_mu;
   mx::GrowBuf stage[mx::kStageSlots];
   // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)
   mx::GrowBuf chain[mx::kChainSlots];
+  // device work buffers of the f0 decode (mx_f0_decode*), kept between calls like the staging buffers; f0_chunk = 0: the default
+  // chunk length
+  std::mutex f0_mu;
+  mx::GrowBuf f0dec[mx::kF0DecSlots];
+  int64_t f0_chunk = 0;
   // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;

@@ -120,6 +120,71 @@ __device__ __forceinline__ unsigned long long block_min_u64(int t, unsigned long
   return a < b ? a : b;
 }
 
+// The candidate ladder of frame f (header: "Candidate ladder"), behind the plain pick of the same launch: d in dd, d' in sq,
+// both complete and at rest until the frame's last barrier.  Rung 1 is the plain pick wherever something lies under theta;
+// where nothing does, rungs 1..3 are empty (theta_k <= theta for them) and the plain pick is the argmin — slot 0's
+// fallback when nothing lies under 2 theta either.  So rungs 0, 2 and 3 alone are searched, by the plain pick's two block
+// minima each (red: a slot pair per minimum); every branch around a barrier is block-uniform.  Thread k writes slot k
+// with the arithmetic of the plain record.
+__device__ __forceinline__ void f0_ladder(int t, const F0Args &a, int64_t f, bool under_theta, int tau_s, bool silent,
+                                          const float *dd, const float *sq, unsigned long long (*red)[2]) {
+  const int tmax = a.tau_max;
+  int taus[MX_F0_CANDS];
+  taus[1] = under_theta ? tau_s : 0;
+#pragma unroll
+  for (int k = 0; k < MX_F0_CANDS; ++k) {
+    if (k == 1) continue;
+    taus[k] = k == 0 ? tau_s : 0;
+    if (k > 1 && !under_theta) continue;
+    const float theta = a.threshold * (k == 0 ? 2.0f : k == 2 ? 0.5f : 0.25f);
+    int under = 0x7fffffff;
+#pragma unroll
+    for (int j = 15; j >= 0; --j) {
+      const int tau = 16 * t + 1 + j;
+      if (tau >= a.tau_min && tau <= tmax && sq[dd_idx(tau)] < theta) under = tau;
+    }
+    const unsigned long long umin = block_min_u64(t, (unsigned long long)(unsigned)under, red[k ? 2 * k - 2 : 0]);
+    if (umin == 0x7fffffffull) continue;
+    const int tau1 = (int)umin;
+    int stop = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int tau = 16 * t + 1 + j;
+      if (tau >= tau1 && tau <= tmax && tau < stop) {
+        if (tau == tmax || !(sq[dd_idx(tau + 1)] < sq[dd_idx(tau)])) stop = tau;
+      }
+    }
+    taus[k] = (int)block_min_u64(t, (unsigned long long)(unsigned)stop, red[k ? 2 * k - 1 : 1]);
+  }
+  if (t < MX_F0_CANDS) {
+    const int tk = t == 0 ? taus[0] : t == 1 ? taus[1] : t == 2 ? taus[2] : taus[3];
+    bool filled = !silent && tk > 0;
+#pragma unroll
+    for (int j = 0; j < MX_F0_CANDS - 1; ++j) filled = filled && !(j < t && taus[j] == tk);
+    mx_f0_cand c;
+    c.tau = 0;
+    c.period = 0.f;
+    c.aperiodicity = 1.f;
+    c.cents = 0;
+    if (filled) {
+      const float ap = sq[dd_idx(tk)];
+      if (__builtin_isfinite(ap)) {
+        const float dm = dd[dd_idx(tk - 1)], d0 = dd[dd_idx(tk)], dp = dd[dd_idx(tk + 1)];
+        const float den = 2.0f * ((dm - 2.0f * d0) + dp);
+        float delta = den > 0.f ? (dm - dp) / den : 0.f;
+        delta = delta < -0.5f ? -0.5f : delta > 0.5f ? 0.5f : delta;
+        c.tau = tk;
+        c.period = (float)tk + delta;
+        c.aperiodicity = ap;
+        c.cents = (int32_t)rintf(1200.f * log2f((float)a.sample_rate / c.period / 55.f)) + 2400;
+      }
+    }
+    a.cands[f * MX_F0_CANDS + t] = c;
+  }
+}
+
+// LADDER: the second instantiation — the plain record (where a.out is set) and, behind it, the frame's candidate ladder.
+template <bool LADDER>
 __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
   using P = FP;
   __shared__ __attribute__((aligned(16))) float2 img[P::M];       // FFT image; then P in bin order; then d
@@ -311,7 +376,11 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
         r.aperiodicity = sq[dd_idx(tau_s)];
         r.rms = __builtin_ldexpf(__builtin_sqrtf(etot * (1.0f / kF0N)), lv);
       }
-      a.out[f] = r;
+      if (!LADDER || a.out) a.out[f] = r;
+    }
+    if constexpr (LADDER) {
+      __shared__ unsigned long long lred[6][2];
+      f0_ladder(t, a, f, umin != 0x7fffffffull, tau_s, etot == 0.f, dd, sq, lred);
     }
     if (f + 1 < f1) {  // the next frame's level (its samples have long arrived)
       const unsigned m = wave_absmax_bits(xr);
@@ -328,7 +397,8 @@ hipError_t launch_f0(const F0Args &a0, hipStream_t s) {
   F0Args a = a0;
   if (a.frames_per_block <= 0) a.frames_per_block = 8;
   const int64_t blocks = (a.count + a.frames_per_block - 1) / a.frames_per_block;
-  hipLaunchKernelGGL(f0_yin, dim3((unsigned)blocks), dim3(FP::T), 0, s, a);
+  if (a.cands) hipLaunchKernelGGL(f0_yin<true>, dim3((unsigned)blocks), dim3(FP::T), 0, s, a);
+  else hipLaunchKernelGGL(f0_yin<false>, dim3((unsigned)blocks), dim3(FP::T), 0, s, a);
   return hipGetLastError();
 }
 

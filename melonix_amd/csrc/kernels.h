@@ -153,8 +153,30 @@ struct F0Args {
   const float2 *tw2, *tw3, *ubase;  // Plan<4096,16> tables
   mx_f0 *out;
   int frames_per_block;  // 0: the default
+  // the candidate ladder (f0_yin's second instantiation): set, a frame's MX_F0_CANDS slots go to cands[4 f ..] and `out` may
+  // be null; null: the plain tracker.  sample_rate: the ladder's cents
+  mx_f0_cand *cands;
+  int sample_rate;
 };
 hipError_t launch_f0(const F0Args &a, hipStream_t s);
+
+// Build-defined Viterbi decode over the ladder (f0_decode.hip).  Costs already in Q16 (q() of the header).  Scratch, all of
+// the caller's: bp (count words), prod (25 int64 per chunk), map (one word per chunk); chunk: frames per chunk, >= 1.
+struct F0DecodeArgs {
+  const mx_f0 *track;
+  const mx_f0_cand *cands;
+  int64_t count;
+  int64_t q_unvoiced, q_jump, q_switch;
+  int32_t max_jump_cents;
+  int64_t chunk;
+  uint16_t *bp;
+  int64_t *prod;
+  uint16_t *map;
+  mx_f0 *out;      // may alias track
+  uint8_t *state;  // may be null
+};
+int64_t f0_decode_default_chunk(int64_t count);
+hipError_t launch_f0_decode(const F0DecodeArgs &a, hipStream_t s);
 // spec-cache.cpp:77-96 colormap: nbins_total magnitudes -> 3*nbins_total bytes (both device).
 hipError_t launch_colormap(const float *mags, uint8_t *rgb, int64_t nbins_total, float k, hipStream_t s);
 
