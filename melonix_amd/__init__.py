@@ -70,6 +70,15 @@ def frame_count(n: int, hop: int) -> int:
     return _capi.lib().mx_frame_count(n, hop)
 
 
+def _frames_from(audio, hop: int, first: int, count: int | None) -> int:
+    """count, or (None) the frames from `first` to the end of the file."""
+    return frame_count(audio.n, hop) - first if count is None else count
+
+
+# the f0 wrappers' default band (Hz) and threshold
+_F0_FMIN, _F0_FMAX, _F0_THRESHOLD = 55.0, 1760.0, 0.15
+
+
 class Audio:
     def __init__(self, ctx: "Context", handle, n: int, keepalive=None):
         self.ctx, self.handle, self.n, self._keep = ctx, handle, n, keepalive
@@ -177,8 +186,7 @@ class Context:
     # ---- STFT, host outputs ----
     def stft_hop(self, audio: Audio, N: int, hop: int, first: int = 0, count: int | None = None, band=(-1, -1),
                  want_mags: bool = True, want_pitch: bool = True):
-        if count is None:
-            count = frame_count(audio.n, hop) - first
+        count = _frames_from(audio, hop, first, count)
         mags = np.empty((count, N // 2), dtype=np.float32) if want_mags else None
         pitch = np.empty(count, dtype=PITCH_DTYPE) if want_pitch else None
         _capi.check(_capi.lib().mx_stft_hop(self.handle, audio.handle, N, hop, first, count, band[0], band[1],
@@ -234,28 +242,26 @@ class Context:
                                                    C.c_void_p(d_pitch or 0)))
 
     # ---- YIN f0 tracking (build-defined; include/melonix_amd.h) ----
-    def f0_track(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, fmin: float = 55.0,
-                 fmax: float = 1760.0, threshold: float = 0.15):
+    def f0_track(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, fmin: float = _F0_FMIN,
+                 fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """-> F0_DTYPE records of frames [first, first + count) (frame h centred on sample h*hop)."""
-        if count is None:
-            count = frame_count(audio.n, hop) - first
+        count = _frames_from(audio, hop, first, count)
         out = np.empty(max(count, 0), dtype=F0_DTYPE)
         _capi.check(_capi.lib().mx_f0_track(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
                                             _ptr(out)))
         return out
 
-    def f0_track_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_out: int, fmin: float = 55.0,
-                     fmax: float = 1760.0, threshold: float = 0.15):
+    def f0_track_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_out: int, fmin: float = _F0_FMIN,
+                     fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """The records stay in HBM at d_out (count x 16 bytes); asynchronous on the context's stream."""
         _capi.check(_capi.lib().mx_f0_track_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
                                                 C.c_void_p(d_out or 0)))
 
     # ---- candidate ladder and Viterbi decode (build-defined) ----
     def f0_candidates(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
-                      fmin: float = 55.0, fmax: float = 1760.0, threshold: float = 0.15):
+                      fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """-> (track: F0_DTYPE records, exactly f0_track's; cands: count x 4 F0_CAND_DTYPE, the frames' candidate ladders)."""
-        if count is None:
-            count = frame_count(audio.n, hop) - first
+        count = _frames_from(audio, hop, first, count)
         track = np.empty(max(count, 0), dtype=F0_DTYPE)
         cands = np.empty((max(count, 0), _capi.F0_CANDS), dtype=F0_CAND_DTYPE)
         _capi.check(_capi.lib().mx_f0_candidates(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
@@ -263,7 +269,7 @@ class Context:
         return track, cands
 
     def f0_candidates_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_track: int | None, d_cands: int,
-                          fmin: float = 55.0, fmax: float = 1760.0, threshold: float = 0.15):
+                          fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """The ladders stay in HBM at d_cands (count x 64 bytes), the plain records at d_track (count x 16 bytes; None: not
         wanted); asynchronous on the context's stream."""
         _capi.check(_capi.lib().mx_f0_candidates_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
@@ -288,10 +294,9 @@ class Context:
                                                  _decode_params(params), C.c_void_p(d_out or 0), C.c_void_p(d_state or 0)))
 
     def f0_track_decoded(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
-                         fmin: float = 55.0, fmax: float = 1760.0, threshold: float = 0.15, **params):
+                         fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD, **params):
         """Candidates and decode in one call -> the decoded F0_DTYPE track (tau 0: silent or unvoiced)."""
-        if count is None:
-            count = frame_count(audio.n, hop) - first
+        count = _frames_from(audio, hop, first, count)
         out = np.empty(max(count, 0), dtype=F0_DTYPE)
         _capi.check(_capi.lib().mx_f0_track_decoded(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
                                                     _decode_params(params), _ptr(out)))

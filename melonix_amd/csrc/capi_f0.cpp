@@ -23,8 +23,19 @@ int f0_range(int sampleRate, float fmin, float fmax, int &tmin, int &tmax) {
   return MX_OK;
 }
 
-int f0_check(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
-             float fmax, float threshold, int &tmin, int &tmax) {
+// What the tracker-side entry points share: their arguments, checked, with the search range they give
+struct F0Call {
+  mx_ctx *ctx;
+  const mx_audio *a;
+  int sampleRate, hop;
+  int64_t first_frame, count;
+  int tmin, tmax;
+  float threshold;
+};
+
+// out: the output the entry point cannot do without (null only where count is 0)
+int f0_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
+             float fmax, float threshold, const void *out, F0Call &q) {
   if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
   if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
   if (!std::isfinite(threshold)) return fail(MX_ERR_INVALID, "threshold is not finite");
@@ -33,30 +44,33 @@ int f0_check(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t fi
   if (first_frame > frames || count > frames - first_frame)
     return fail(MX_ERR_INVALID, "frames [%lld, %lld) outside the %lld frames of the file", (long long)first_frame,
                 (long long)(first_frame + count), (long long)frames);
-  return f0_range(sampleRate, fmin, fmax, tmin, tmax);
+  q = F0Call{ctx, a, sampleRate, hop, first_frame, count, 0, 0, threshold};
+  if (const int rc = f0_range(sampleRate, fmin, fmax, q.tmin, q.tmax)) return rc;
+  if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
+  return MX_OK;
 }
 
-// d_cands set: the ladder instantiation (d_out may then be null); sampleRate: the ladder's cents
-int f0_launch(mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_frame, int64_t count, int tmin, int tmax,
-              float threshold, mx_f0 *d_out, mx_f0_cand *d_cands = nullptr, int sampleRate = 0) {
-  HIP_TRY(hipSetDevice(ctx->device));
+// d_cands set: the ladder instantiation (d_out may then be null)
+int f0_launch(const F0Call &q, mx_f0 *d_out, mx_f0_cand *d_cands) {
+  if (q.count == 0) return MX_OK;
+  HIP_TRY(hipSetDevice(q.ctx->device));
   NTables t;
-  if (const int rc = get_tables(ctx, 4096, t)) return rc;
+  if (const int rc = get_tables(q.ctx, 4096, t)) return rc;
   F0Args g{};
-  g.audio = a->d_padded;
-  g.hop = hop;
-  g.first_frame = first_frame;
-  g.count = count;
-  g.tau_min = tmin;
-  g.tau_max = tmax;
-  g.threshold = threshold;
+  g.audio = q.a->d_padded;
+  g.hop = q.hop;
+  g.first_frame = q.first_frame;
+  g.count = q.count;
+  g.tau_min = q.tmin;
+  g.tau_max = q.tmax;
+  g.threshold = q.threshold;
   g.tw2 = t.tw2;
   g.tw3 = t.tw3;
   g.ubase = t.ubase;
   g.out = d_out;
   g.cands = d_cands;
-  g.sample_rate = sampleRate;
-  HIP_TRY(launch_f0(g, ctx->stream));
+  g.sample_rate = q.sampleRate;
+  HIP_TRY(launch_f0(g, q.ctx->stream));
   return MX_OK;
 }
 
@@ -69,6 +83,16 @@ int decode_params(const mx_f0_decode_params *p, mx_f0_decode_params &out) {
     if (!std::isfinite(c) || c < 0.f || c > 16.f) return fail(MX_ERR_INVALID, "decode cost %g outside [0, 16]", (double)c);
   if (out.max_jump_cents < 0 || out.max_jump_cents > 12000)
     return fail(MX_ERR_INVALID, "max_jump_cents %d outside [0, 12000]", out.max_jump_cents);
+  return MX_OK;
+}
+
+// what the two decode forms check; -> the parameters in force
+int decode_parse(mx_ctx *ctx, const void *track, const void *cands, int64_t count, const mx_f0_decode_params *p, const void *out,
+                 mx_f0_decode_params &dp) {
+  if (const int rc = decode_params(p, dp)) return rc;
+  if (!ctx) return fail(MX_ERR_INVALID, "null context");
+  if (count < 0) return fail(MX_ERR_INVALID, "negative frame count");
+  if (count > 0 && (!track || !cands || !out)) return fail(MX_ERR_INVALID, "null argument");
   return MX_OK;
 }
 
@@ -89,10 +113,10 @@ int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, 
   g.q_switch = q16(p.switch_cost);
   g.max_jump_cents = p.max_jump_cents;
   g.chunk = ctx->f0_chunk > 0 ? ctx->f0_chunk : f0_decode_default_chunk(count);
-  const size_t nchunks = (size_t)((count + g.chunk - 1) / g.chunk);
-  hipError_t e = ctx->f0dec[kF0DecBp].get((size_t)count * sizeof(uint16_t), &g.bp);
-  if (e == hipSuccess) e = ctx->f0dec[kF0DecProd].get(nchunks * 25 * sizeof(int64_t), &g.prod);
-  if (e == hipSuccess) e = ctx->f0dec[kF0DecMap].get(nchunks * sizeof(uint16_t), &g.map);
+  const F0DecodeScratch need = f0_decode_scratch(count, g.chunk);
+  hipError_t e = ctx->f0dec[kF0DecBp].get(need.bp, &g.bp);
+  if (e == hipSuccess) e = ctx->f0dec[kF0DecProd].get(need.prod, &g.prod);
+  if (e == hipSuccess) e = ctx->f0dec[kF0DecMap].get(need.map, &g.map);
   if (e != hipSuccess) return fail(MX_ERR_NOMEM, "f0 decode work buffers: %s", hipGetErrorString(e));
   g.out = d_out;
   g.state = d_state;
@@ -100,11 +124,12 @@ int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, 
   return MX_OK;
 }
 
-// The host-pointer forms: the records pass through the context's staging buffers (candidates in the magnitude rows' buffer,
-// the track — decoded in place — in the pitch records', states in the texels').  `in`: upload the caller's track and
-// candidates; `run(d_track, d_cands, d_state)` queues the device form; the outputs that are set come back.  Blocks.
+// The host-pointer forms: the records pass through the context's staging buffers (the track — decoded in place — in the pitch
+// records', states in the texels' and, where the call has candidates (`ladder`), those in the magnitude rows').  `in`: upload
+// the caller's track and candidates; `run(d_track, d_cands, d_state)` queues the device form; the outputs that are set come
+// back.  Blocks.
 template <class F>
-int f0_staged(mx_ctx *ctx, int64_t count, const mx_f0 *track_in, const mx_f0_cand *cands_in, mx_f0 *track_out,
+int f0_staged(mx_ctx *ctx, int64_t count, bool ladder, const mx_f0 *track_in, const mx_f0_cand *cands_in, mx_f0 *track_out,
               mx_f0_cand *cands_out, uint8_t *state_out, F &&run) {
   if (count == 0) return MX_OK;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -113,8 +138,8 @@ int f0_staged(mx_ctx *ctx, int64_t count, const mx_f0 *track_in, const mx_f0_can
   mx_f0_cand *d_cands = nullptr;
   mx_f0 *d_track = nullptr;
   uint8_t *d_state = nullptr;
-  hipError_t e = ctx->stage[kStageMags].get(n * MX_F0_CANDS * sizeof(mx_f0_cand), &d_cands);
-  if (e == hipSuccess) e = ctx->stage[kStagePitch].get(n * sizeof(mx_f0), &d_track);
+  hipError_t e = ctx->stage[kStagePitch].get(n * sizeof(mx_f0), &d_track);
+  if (e == hipSuccess && ladder) e = ctx->stage[kStageMags].get(n * MX_F0_CANDS * sizeof(mx_f0_cand), &d_cands);
   if (e == hipSuccess && state_out) e = ctx->stage[kStageTexels].get(n, &d_state);
   int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
   if (rc == MX_OK && track_in) e = hipMemcpyAsync(d_track, track_in, n * sizeof(mx_f0), hipMemcpyHostToDevice, ctx->stream);
@@ -143,56 +168,38 @@ extern "C" {
 int mx_f0_track_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                     float fmin, float fmax, float threshold, mx_f0 *d_out) {
   return mx_guard([&]() -> int {
-    int tmin = 0, tmax = 0;
-    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
-    if (count > 0 && !d_out) return fail(MX_ERR_INVALID, "null output");
-    return f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_out);
+    F0Call q;
+    if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, d_out, q)) return rc;
+    return f0_launch(q, d_out, nullptr);
   });
 }
 
 int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
                 float fmax, float threshold, mx_f0 *out) {
   return mx_guard([&]() -> int {
-    int tmin = 0, tmax = 0;
-    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
-    if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
-    if (count == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)count * sizeof(mx_f0);
-    std::lock_guard<std::mutex> lk(ctx->stage_mu);
-    mx_f0 *d = nullptr;
-    HIP_TRY(ctx->stage[kStageMags].get(bytes, &d));  // (no magnitude rows in this call: their buffer holds the records)
-    int rc = f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d);
-    if (rc == MX_OK) {
-      hipError_t e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "f0 download: %s", hipGetErrorString(e));
-    }
-    stage_trim(ctx);
-    return rc;
+    F0Call q;
+    if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, out, q)) return rc;
+    return f0_staged(ctx, count, false, nullptr, nullptr, out, nullptr, nullptr,
+                     [&](mx_f0 *d_track, mx_f0_cand *, uint8_t *) { return f0_launch(q, d_track, nullptr); });
   });
 }
 
 int mx_f0_candidates_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                          float fmin, float fmax, float threshold, mx_f0 *d_track, mx_f0_cand *d_cands) {
   return mx_guard([&]() -> int {
-    int tmin = 0, tmax = 0;
-    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
-    if (count > 0 && !d_cands) return fail(MX_ERR_INVALID, "null output");
-    if (count == 0) return MX_OK;
-    return f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_track, d_cands, sampleRate);
+    F0Call q;
+    if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, d_cands, q)) return rc;
+    return f0_launch(q, d_track, d_cands);
   });
 }
 
 int mx_f0_candidates(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                      float fmin, float fmax, float threshold, mx_f0 *track, mx_f0_cand *cands) {
   return mx_guard([&]() -> int {
-    int tmin = 0, tmax = 0;
-    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
-    if (count > 0 && !cands) return fail(MX_ERR_INVALID, "null output");
-    return f0_staged(ctx, count, nullptr, nullptr, track, cands, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
-      return f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_track, d_cands, sampleRate);
-    });
+    F0Call q;
+    if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, cands, q)) return rc;
+    return f0_staged(ctx, count, true, nullptr, nullptr, track, cands, nullptr,
+                     [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) { return f0_launch(q, d_track, d_cands); });
   });
 }
 
@@ -206,10 +213,7 @@ int mx_f0_decode_dev(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cand
                      const mx_f0_decode_params *p, mx_f0 *d_out, uint8_t *d_state) {
   return mx_guard([&]() -> int {
     mx_f0_decode_params dp;
-    if (const int rc = decode_params(p, dp)) return rc;
-    if (!ctx) return fail(MX_ERR_INVALID, "null context");
-    if (count < 0) return fail(MX_ERR_INVALID, "negative frame count");
-    if (count > 0 && (!d_track || !d_cands || !d_out)) return fail(MX_ERR_INVALID, "null argument");
+    if (const int rc = decode_parse(ctx, d_track, d_cands, count, p, d_out, dp)) return rc;
     return decode_launch(ctx, d_track, d_cands, count, dp, d_out, d_state);
   });
 }
@@ -218,11 +222,8 @@ int mx_f0_decode(mx_ctx *ctx, const mx_f0 *track, const mx_f0_cand *cands, int64
                  mx_f0 *out, uint8_t *state) {
   return mx_guard([&]() -> int {
     mx_f0_decode_params dp;
-    if (const int rc = decode_params(p, dp)) return rc;
-    if (!ctx) return fail(MX_ERR_INVALID, "null context");
-    if (count < 0) return fail(MX_ERR_INVALID, "negative frame count");
-    if (count > 0 && (!track || !cands || !out)) return fail(MX_ERR_INVALID, "null argument");
-    return f0_staged(ctx, count, track, cands, out, nullptr, state, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *d_state) {
+    if (const int rc = decode_parse(ctx, track, cands, count, p, out, dp)) return rc;
+    return f0_staged(ctx, count, true, track, cands, out, nullptr, state, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *d_state) {
       return decode_launch(ctx, d_track, d_cands, count, dp, d_track, d_state);
     });
   });
@@ -233,12 +234,10 @@ int mx_f0_track_decoded(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop,
   return mx_guard([&]() -> int {
     mx_f0_decode_params dp;
     if (const int rc = decode_params(p, dp)) return rc;
-    int tmin = 0, tmax = 0;
-    if (const int rc = f0_check(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, tmin, tmax)) return rc;
-    if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
-    return f0_staged(ctx, count, nullptr, nullptr, out, nullptr, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
-      if (const int rc = f0_launch(ctx, a, hop, first_frame, count, tmin, tmax, threshold, d_track, d_cands, sampleRate))
-        return rc;
+    F0Call q;
+    if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, out, q)) return rc;
+    return f0_staged(ctx, count, true, nullptr, nullptr, out, nullptr, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
+      if (const int rc = f0_launch(q, d_track, d_cands)) return rc;
       return decode_launch(ctx, d_track, d_cands, count, dp, d_track, nullptr);
     });
   });

@@ -31,6 +31,40 @@ constexpr int kDecT = 256;
 constexpr int kProdTile = 256;   // chunk products per LDS tile of f0_dec_starts (50 KiB)
 constexpr int kMapTile = 4096;   // chunk maps per LDS tile of f0_dec_ends
 
+// The scratch layout, owned here.  prod holds kProdWords int64 per chunk: the chunk's product row-major, as f0_dec_products
+// leaves it; from f0_dec_starts on, its first row is V before the chunk's first frame, and behind the last chunk's f0_dec_walk
+// leaves V_{F-1}.  bp: a word per frame; map: a word per chunk.
+constexpr int kProdWords = kStates * kStates;
+__device__ __forceinline__ int64_t *prod_row(const F0DecodeArgs &a, int64_t c, int row) {
+  return a.prod + c * kProdWords + row * kStates;
+}
+__device__ __forceinline__ int64_t *start_vec(const F0DecodeArgs &a, int64_t c) { return prod_row(a, c, 0); }
+__device__ __forceinline__ int64_t *end_vec(const F0DecodeArgs &a, int64_t nchunks) { return prod_row(a, nchunks - 1, 1); }
+__host__ __device__ constexpr int64_t chunk_count(int64_t count, int64_t chunk) { return (count + chunk - 1) / chunk; }
+
+// chunk c's frames [fa, fb)
+__device__ __forceinline__ void chunk_bounds(const F0DecodeArgs &a, int64_t c, int64_t &fa, int64_t &fb) {
+  fa = c * a.chunk;
+  fb = fa + a.chunk < a.count ? fa + a.chunk : a.count;
+}
+
+// The min-plus step: min over the predecessors i of V[i] + cost(i) and, in bi, the lowest i attaining it — the first strictly
+// smaller value wins, the unvoiced state is compared last.
+template <class Cost>
+__device__ __forceinline__ int64_t best_pred(const int64_t (&V)[kStates], unsigned &bi, Cost &&cost) {
+  int64_t best = V[0] + cost(0);
+  bi = 0;
+#pragma unroll
+  for (int i = 1; i < kStates; ++i) {
+    const int64_t v = V[i] + cost(i);
+    if (v < best) {
+      best = v;
+      bi = i;
+    }
+  }
+  return best;
+}
+
 struct DecFrame {
   int32_t cents[MX_F0_CANDS];
   unsigned filled;  // bit j: slot j holds a candidate
@@ -59,52 +93,25 @@ __device__ __forceinline__ unsigned dec_step(const F0DecodeArgs &a, int64_t (&V)
   const int64_t qs = first ? 0 : a.q_switch;
   const unsigned pf = first ? 0u : p.filled;
   int64_t Vn[kStates];
-  unsigned bp = 0;
+  unsigned bp = 0, bi;
 #pragma unroll
   for (int j = 0; j < MX_F0_CANDS; ++j) {
-    int64_t best = 0;
-    unsigned bi = 0;
-#pragma unroll
-    for (int i = 0; i < MX_F0_CANDS; ++i) {
+    const int64_t best = best_pred(V, bi, [&](int i) -> int64_t {
+      if (i == kUnvoiced) return qs;
       int64_t t = 0;
       if ((pf >> i & 1u) && (c.filled >> j & 1u)) {
-        int64_t dc = (int64_t)c.cents[j] - (int64_t)p.cents[i];
-        dc = dc < 0 ? -dc : dc;
+        const int32_t x = c.cents[j], y = p.cents[i];
+        int64_t dc = (uint32_t)(x > y ? x : y) - (uint32_t)(x < y ? x : y);  // |x - y|: fits 32 bits unsigned
         dc = dc < a.max_jump_cents ? dc : a.max_jump_cents;
         t = (int64_t)((uint64_t)(a.q_jump * dc) / 100u);
       }
-      const int64_t v = V[i] + t;
-      if (i == 0 || v < best) {
-        best = v;
-        bi = i;
-      }
-    }
-    const int64_t v = V[kUnvoiced] + qs;
-    if (v < best) {
-      best = v;
-      bi = kUnvoiced;
-    }
+      return t;
+    });
     Vn[j] = best + c.obs[j];
     bp |= bi << (3 * j);
   }
-  {
-    int64_t best = V[0] + qs;
-    unsigned bi = 0;
-#pragma unroll
-    for (int i = 1; i < MX_F0_CANDS; ++i) {
-      const int64_t v = V[i] + qs;
-      if (v < best) {
-        best = v;
-        bi = i;
-      }
-    }
-    if (V[kUnvoiced] < best) {
-      best = V[kUnvoiced];
-      bi = kUnvoiced;
-    }
-    Vn[kUnvoiced] = best + c.obs[kUnvoiced];
-    bp |= bi << (3 * kUnvoiced);
-  }
+  Vn[kUnvoiced] = best_pred(V, bi, [&](int i) { return i == kUnvoiced ? (int64_t)0 : qs; }) + c.obs[kUnvoiced];
+  bp |= bi << (3 * kUnvoiced);
 #pragma unroll
   for (int j = 0; j < kStates; ++j) V[j] = Vn[j];
   return bp;
@@ -136,36 +143,32 @@ __global__ __launch_bounds__(kDecT) void f0_dec_products(const F0DecodeArgs a, i
   const int64_t c = g / kStates;
   const int row = (int)(g - c * kStates);
   if (c >= nchunks) return;
-  const int64_t fa = c * a.chunk, fb = fa + a.chunk < a.count ? fa + a.chunk : a.count;
+  int64_t fa, fb;
+  chunk_bounds(a, c, fa, fb);
   int64_t V[kStates];
 #pragma unroll
   for (int j = 0; j < kStates; ++j) V[j] = j == row ? 0 : kNoPath;
   dec_walk<false>(a, fa, fb, V);
 #pragma unroll
-  for (int j = 0; j < kStates; ++j) a.prod[c * 25 + row * kStates + j] = V[j];
+  for (int j = 0; j < kStates; ++j) prod_row(a, c, row)[j] = V[j];
 }
 
 __global__ __launch_bounds__(kDecT) void f0_dec_starts(const F0DecodeArgs a, int64_t nchunks) {
-  __shared__ int64_t tile[kProdTile * 25];
+  __shared__ int64_t tile[kProdTile * kProdWords];
   int64_t V[kStates] = {0, 0, 0, 0, 0};
   for (int64_t c0 = 0; c0 < nchunks; c0 += kProdTile) {
     const int n = (int)(nchunks - c0 < kProdTile ? nchunks - c0 : kProdTile);
-    for (int i = threadIdx.x; i < n * 25; i += kDecT) tile[i] = a.prod[c0 * 25 + i];
+    for (int i = threadIdx.x; i < n * kProdWords; i += kDecT) tile[i] = prod_row(a, c0, 0)[i];
     __syncthreads();
     if (threadIdx.x == 0) {
       for (int k = 0; k < n; ++k) {
-        const int64_t *P = tile + k * 25;
+        const int64_t *P = tile + k * kProdWords;
         int64_t Vn[kStates];
+        unsigned bi;
 #pragma unroll
         for (int j = 0; j < kStates; ++j) {
-          a.prod[(c0 + k) * 25 + j] = V[j];
-          int64_t best = V[0] + P[j];
-#pragma unroll
-          for (int i = 1; i < kStates; ++i) {
-            const int64_t v = V[i] + P[i * kStates + j];
-            best = v < best ? v : best;
-          }
-          Vn[j] = best;
+          start_vec(a, c0 + k)[j] = V[j];
+          Vn[j] = best_pred(V, bi, [&](int i) { return P[i * kStates + j]; });
         }
 #pragma unroll
         for (int j = 0; j < kStates; ++j) V[j] = Vn[j];
@@ -178,14 +181,15 @@ __global__ __launch_bounds__(kDecT) void f0_dec_starts(const F0DecodeArgs a, int
 __global__ __launch_bounds__(kDecT) void f0_dec_walk(const F0DecodeArgs a, int64_t nchunks) {
   const int64_t c = (int64_t)blockIdx.x * kDecT + threadIdx.x;
   if (c >= nchunks) return;
-  const int64_t fa = c * a.chunk, fb = fa + a.chunk < a.count ? fa + a.chunk : a.count;
+  int64_t fa, fb;
+  chunk_bounds(a, c, fa, fb);
   int64_t V[kStates];
 #pragma unroll
-  for (int j = 0; j < kStates; ++j) V[j] = a.prod[c * 25 + j];
+  for (int j = 0; j < kStates; ++j) V[j] = start_vec(a, c)[j];
   a.map[c] = (uint16_t)dec_walk<true>(a, fa, fb, V);
-  if (c == nchunks - 1) {  // V_{F-1}, behind the start vector
+  if (c == nchunks - 1) {
 #pragma unroll
-    for (int j = 0; j < kStates; ++j) a.prod[c * 25 + kStates + j] = V[j];
+    for (int j = 0; j < kStates; ++j) end_vec(a, nchunks)[j] = V[j];
   }
 }
 
@@ -193,7 +197,7 @@ __global__ __launch_bounds__(kDecT) void f0_dec_ends(const F0DecodeArgs a, int64
   __shared__ uint16_t tile[kMapTile];
   unsigned s = 0;
   if (threadIdx.x == 0) {  // the lowest j attaining min V_{F-1}
-    const int64_t *V = a.prod + (nchunks - 1) * 25 + kStates;
+    const int64_t *V = end_vec(a, nchunks);
     int64_t best = V[0];
     for (int j = 1; j < kStates; ++j)
       if (V[j] < best) {
@@ -220,14 +224,11 @@ __global__ __launch_bounds__(kDecT) void f0_dec_ends(const F0DecodeArgs a, int64
 __global__ __launch_bounds__(kDecT) void f0_dec_path(const F0DecodeArgs a, int64_t nchunks) {
   const int64_t c = (int64_t)blockIdx.x * kDecT + threadIdx.x;
   if (c >= nchunks) return;
-  const int64_t fa = c * a.chunk, fb = fa + a.chunk < a.count ? fa + a.chunk : a.count;
+  int64_t fa, fb;
+  chunk_bounds(a, c, fa, fb);
   unsigned s = a.map[c];
   for (int64_t f = fb - 1; f >= fa; --f) {
-    mx_f0 r;
-    r.tau = 0;
-    r.period = 0.f;
-    r.aperiodicity = 1.f;
-    r.rms = a.track[f].rms;  // (read before the write below: out may be track)
+    mx_f0 r{0, 0.f, 1.f, a.track[f].rms};  // unvoiced (rms read before the write below: out may be track)
     if (s != kUnvoiced) {
       const mx_f0_cand k = a.cands[f * MX_F0_CANDS + s];
       r.tau = k.tau;
@@ -250,9 +251,14 @@ int64_t f0_decode_default_chunk(int64_t count) {
   return c;
 }
 
+F0DecodeScratch f0_decode_scratch(int64_t count, int64_t chunk) {
+  const size_t nchunks = (size_t)chunk_count(count, chunk);
+  return {(size_t)count * sizeof(uint16_t), nchunks * kProdWords * sizeof(int64_t), nchunks * sizeof(uint16_t)};
+}
+
 hipError_t launch_f0_decode(const F0DecodeArgs &a, hipStream_t s) {
   if (a.count <= 0) return hipSuccess;
-  const int64_t nchunks = (a.count + a.chunk - 1) / a.chunk;
+  const int64_t nchunks = chunk_count(a.count, a.chunk);
   const dim3 per_chunk((unsigned)((nchunks + kDecT - 1) / kDecT));
   hipLaunchKernelGGL(f0_dec_products, dim3((unsigned)((nchunks * kStates + kDecT - 1) / kDecT)), dim3(kDecT), 0, s, a, nchunks);
   hipLaunchKernelGGL(f0_dec_starts, dim3(1), dim3(kDecT), 0, s, a, nchunks);

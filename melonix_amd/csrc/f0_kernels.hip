@@ -52,8 +52,9 @@ constexpr int kSqLen = kF0N + kF0N / 32 + 1;
 constexpr int kDdLen = kF0W + kF0W / 16 + 2;
 static_assert(kDdLen <= 2 * kF0M, "d fits the FFT image (as floats)");
 
-// max |x| over the thread's 32 samples and then the wavefront, as float bits (|x| orders as its bits; NaN above Inf)
-__device__ __forceinline__ unsigned wave_absmax_bits(const cpx (&xr)[FP::E]) {
+// max |x| over the thread's 32 samples and then the wavefront, as float bits (|x| orders as its bits; NaN above Inf), to
+// the wavefront's word of s_max: the level of the frame that xr holds
+__device__ __forceinline__ void wave_absmax_bits(int t, int lane, const cpx (&xr)[FP::E], unsigned *s_max) {
   unsigned m = 0;
 #pragma unroll
   for (int e = 0; e < FP::E; ++e) {
@@ -61,7 +62,8 @@ __device__ __forceinline__ unsigned wave_absmax_bits(const cpx (&xr)[FP::E]) {
     m = m > a ? m : a;
     m = m > b ? m : b;
   }
-  return wave_reduce_u32<true>(m);
+  m = wave_reduce_u32<true>(m);
+  if (lane == 0) s_max[t >> 6] = m;
 }
 
 // s with 2^s <= |x| < 2^(s+1) for the magnitude bits m of a finite non-zero |x|; 0 for 0, Inf and NaN
@@ -120,6 +122,33 @@ __device__ __forceinline__ unsigned long long block_min_u64(int t, unsigned long
   return a < b ? a : b;
 }
 
+// Step 4's descent from tau1 over d' (dp): the first tau >= tau1 that is tau_max or not above d'(tau+1) — each thread over
+// its 16 lags, then the block minimum.  The plain pick and every rung of the ladder end here.
+__device__ __forceinline__ int descent_end(int t, int tau1, int tmax, const float *dp, unsigned long long *slot) {
+  int stop = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int tau = 16 * t + 1 + j;
+    if (tau >= tau1 && tau <= tmax && tau < stop) {
+      if (tau == tmax || !(dp[dd_idx(tau + 1)] < dp[dd_idx(tau)])) stop = tau;
+    }
+  }
+  return (int)block_min_u64(t, (unsigned long long)(unsigned)stop, slot);
+}
+
+// Step 5: tau + the parabolic offset on d at tau-1, tau, tau+1
+__device__ __forceinline__ float refined_period(const float *dd, int tau) {
+  const float dm = dd[dd_idx(tau - 1)], d0 = dd[dd_idx(tau)], dp = dd[dd_idx(tau + 1)];
+  const float den = 2.0f * ((dm - 2.0f * d0) + dp);
+  float delta = den > 0.f ? (dm - dp) / den : 0.f;
+  delta = delta < -0.5f ? -0.5f : delta > 0.5f ? 0.5f : delta;
+  return (float)tau + delta;
+}
+
+// step 6's silent frame and the ladder's empty slot
+constexpr mx_f0 kSilentF0{0, 0.f, 1.f, 0.f};
+constexpr mx_f0_cand kEmptyCand{0, 0.f, 1.f, 0};
+
 // The candidate ladder of frame f (header: "Candidate ladder"), behind the plain pick of the same launch: d in dd, d' in sq,
 // both complete and at rest until the frame's last barrier.  Rung 1 is the plain pick wherever something lies under theta;
 // where nothing does, rungs 1..3 are empty (theta_k <= theta for them) and the plain pick is the argmin — slot 0's
@@ -131,11 +160,11 @@ __device__ __forceinline__ void f0_ladder(int t, const F0Args &a, int64_t f, boo
   const int tmax = a.tau_max;
   int taus[MX_F0_CANDS];
   taus[1] = under_theta ? tau_s : 0;
-#pragma unroll
-  for (int k = 0; k < MX_F0_CANDS; ++k) {
-    if (k == 1) continue;
+  static_for<0, MX_F0_CANDS>([&](auto kk) {
+    constexpr int k = decltype(kk)::value;
+    if (k == 1) return;
     taus[k] = k == 0 ? tau_s : 0;
-    if (k > 1 && !under_theta) continue;
+    if (k > 1 && !under_theta) return;
     const float theta = a.threshold * (k == 0 ? 2.0f : k == 2 ? 0.5f : 0.25f);
     int under = 0x7fffffff;
 #pragma unroll
@@ -144,37 +173,19 @@ __device__ __forceinline__ void f0_ladder(int t, const F0Args &a, int64_t f, boo
       if (tau >= a.tau_min && tau <= tmax && sq[dd_idx(tau)] < theta) under = tau;
     }
     const unsigned long long umin = block_min_u64(t, (unsigned long long)(unsigned)under, red[k ? 2 * k - 2 : 0]);
-    if (umin == 0x7fffffffull) continue;
-    const int tau1 = (int)umin;
-    int stop = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int tau = 16 * t + 1 + j;
-      if (tau >= tau1 && tau <= tmax && tau < stop) {
-        if (tau == tmax || !(sq[dd_idx(tau + 1)] < sq[dd_idx(tau)])) stop = tau;
-      }
-    }
-    taus[k] = (int)block_min_u64(t, (unsigned long long)(unsigned)stop, red[k ? 2 * k - 1 : 1]);
-  }
+    if (umin != 0x7fffffffull) taus[k] = descent_end(t, (int)umin, tmax, sq, red[k ? 2 * k - 1 : 1]);
+  });
   if (t < MX_F0_CANDS) {
     const int tk = t == 0 ? taus[0] : t == 1 ? taus[1] : t == 2 ? taus[2] : taus[3];
     bool filled = !silent && tk > 0;
 #pragma unroll
     for (int j = 0; j < MX_F0_CANDS - 1; ++j) filled = filled && !(j < t && taus[j] == tk);
-    mx_f0_cand c;
-    c.tau = 0;
-    c.period = 0.f;
-    c.aperiodicity = 1.f;
-    c.cents = 0;
+    mx_f0_cand c = kEmptyCand;
     if (filled) {
       const float ap = sq[dd_idx(tk)];
       if (__builtin_isfinite(ap)) {
-        const float dm = dd[dd_idx(tk - 1)], d0 = dd[dd_idx(tk)], dp = dd[dd_idx(tk + 1)];
-        const float den = 2.0f * ((dm - 2.0f * d0) + dp);
-        float delta = den > 0.f ? (dm - dp) / den : 0.f;
-        delta = delta < -0.5f ? -0.5f : delta > 0.5f ? 0.5f : delta;
         c.tau = tk;
-        c.period = (float)tk + delta;
+        c.period = refined_period(dd, tk);
         c.aperiodicity = ap;
         c.cents = (int32_t)rintf(1200.f * log2f((float)a.sample_rate / c.period / 55.f)) + 2400;
       }
@@ -214,10 +225,7 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
   const float *const base = a.audio + MX_AUDIO_PAD - kF0W;
   cpx xr[P::E];
   load_raw<P, false>(t_, xr, base + (a.first_frame + f0) * (int64_t)a.hop);
-  {
-    const unsigned m = wave_absmax_bits(xr);
-    if (lane == 0) s_max[t_ >> 6] = m;
-  }
+  wave_absmax_bits(t_, lane, xr, s_max);
   __syncthreads();
   const float theta = a.threshold;
   const int tmin = a.tau_min, tmax = a.tau_max;
@@ -343,36 +351,13 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
       }
     }
     const unsigned long long umin = block_min_u64(t, (unsigned long long)(unsigned)under, red[0]);  // + barrier: d' is complete
-    int tau_s;
-    if (umin != 0x7fffffffull) {
-      // the end of the descent: the first tau >= tau1 that is tau_max or not above d'(tau+1)
-      const int tau1 = (int)umin;
-      int stop = 0x7fffffff;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int tau = 16 * t + 1 + j;
-        if (tau >= tau1 && tau <= tmax && tau < stop) {
-          if (tau == tmax || !(sq[dd_idx(tau + 1)] < sq[dd_idx(tau)])) stop = tau;
-        }
-      }
-      tau_s = (int)block_min_u64(t, (unsigned long long)(unsigned)stop, red[1]);
-    } else {
-      tau_s = (int)(unsigned)block_min_u64(t, key, red[2]);
-    }
+    // the end of the descent, or the argmin where nothing lies under theta
+    const int tau_s = umin != 0x7fffffffull ? descent_end(t, (int)umin, tmax, sq, red[1]) : (int)(unsigned)block_min_u64(t, key, red[2]);
     if (t == 0) {
-      mx_f0 r;
-      if (etot == 0.f) {
-        r.tau = 0;
-        r.period = 0.f;
-        r.aperiodicity = 1.f;
-        r.rms = 0.f;
-      } else {
-        const float dm = dd[dd_idx(tau_s - 1)], d0 = dd[dd_idx(tau_s)], dp = dd[dd_idx(tau_s + 1)];
-        const float den = 2.0f * ((dm - 2.0f * d0) + dp);
-        float delta = den > 0.f ? (dm - dp) / den : 0.f;
-        delta = delta < -0.5f ? -0.5f : delta > 0.5f ? 0.5f : delta;
+      mx_f0 r = kSilentF0;
+      if (etot != 0.f) {
         r.tau = tau_s;
-        r.period = (float)tau_s + delta;
+        r.period = refined_period(dd, tau_s);
         r.aperiodicity = sq[dd_idx(tau_s)];
         r.rms = __builtin_ldexpf(__builtin_sqrtf(etot * (1.0f / kF0N)), lv);
       }
@@ -382,10 +367,7 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
       __shared__ unsigned long long lred[6][2];
       f0_ladder(t, a, f, umin != 0x7fffffffull, tau_s, etot == 0.f, dd, sq, lred);
     }
-    if (f + 1 < f1) {  // the next frame's level (its samples have long arrived)
-      const unsigned m = wave_absmax_bits(xr);
-      if (lane == 0) s_max[t >> 6] = m;
-    }
+    if (f + 1 < f1) wave_absmax_bits(t, lane, xr, s_max);  // the next frame's level (its samples have long arrived)
     __syncthreads();  // the images are read: the next frame may write them; s_max is written
   }
 }

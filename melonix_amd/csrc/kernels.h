@@ -161,7 +161,7 @@ struct F0Args {
 hipError_t launch_f0(const F0Args &a, hipStream_t s);
 
 // Build-defined Viterbi decode over the ladder (f0_decode.hip).  Costs already in Q16 (q() of the header).  Scratch, all of
-// the caller's: bp (count words), prod (25 int64 per chunk), map (one word per chunk); chunk: frames per chunk, >= 1.
+// the caller's, of the byte counts f0_decode_scratch(count, chunk) gives; chunk: frames per chunk, >= 1.
 struct F0DecodeArgs {
   const mx_f0 *track;
   const mx_f0_cand *cands;
@@ -176,6 +176,10 @@ struct F0DecodeArgs {
   uint8_t *state;  // may be null
 };
 int64_t f0_decode_default_chunk(int64_t count);
+struct F0DecodeScratch {
+  size_t bp, prod, map;  // bytes
+};
+F0DecodeScratch f0_decode_scratch(int64_t count, int64_t chunk);
 hipError_t launch_f0_decode(const F0DecodeArgs &a, hipStream_t s);
 // spec-cache.cpp:77-96 colormap: nbins_total magnitudes -> 3*nbins_total bytes (both device).
 hipError_t launch_colormap(const float *mags, uint8_t *rgb, int64_t nbins_total, float k, hipStream_t s);

@@ -65,17 +65,6 @@ def thetas(threshold):
     return [float(np.float32(th * np.float32(m))) for m in RUNGS]
 
 
-def rung_pick(dp_row, tmin, tmax, theta):
-    """Step 4 with theta and no fallback: the tau, or 0 for an empty rung."""
-    under = np.nonzero(dp_row[tmin:tmax + 1] < theta)[0]
-    if not len(under):
-        return 0
-    t = tmin + int(under[0])
-    while t + 1 <= tmax and dp_row[t + 1] < dp_row[t]:
-        t += 1
-    return t
-
-
 def cents_of(period, sr):
     return int(np.rint(1200.0 * math.log2(float(sr) / float(period) / 55.0))) + 2400
 
@@ -83,37 +72,27 @@ def cents_of(period, sr):
 def ladder(w, sr, hop=256, first=0, count=None, fmin=55.0, fmax=1760.0, threshold=0.15, chunk=2048):
     """-> (cands: F x 4 CAND_REF_DTYPE, dp: F x (W+1) d' rows, rung_taus: F x 4 — the tau each rung picked before the
     duplicate rule, 0 where the rung is empty (slot 0: the fallback's tau)."""
-    n = len(w)
-    if count is None:
-        count = -(-n // hop) - first
+    count = Y.default_count(len(w), hop, first, count)
     tmin, tmax = Y.tau_range(sr, fmin, fmax)
     th = thetas(threshold)
     cands = np.zeros((count, CANDS), dtype=CAND_REF_DTYPE)
     cands["aperiodicity"] = 1.0
     picked = np.zeros((count, CANDS), dtype=np.int64)
     dps = []
-    for c0 in range(0, count, chunk):
-        x = Y.frames_of(w, hop, first + c0, min(chunk, count - c0))
+    for c0, x, d, dp in Y.frame_chunks(w, hop, first, count, chunk):
         with np.errstate(invalid="ignore", over="ignore"):
-            d = Y.diff_fft(x)
-            dp = Y.cmnd(d)
             energy = np.sum(x * x, axis=1)
         dps.append(dp)
         for i in range(x.shape[0]):
             if energy[i] == 0:
                 continue
-            taus = [rung_pick(dp[i], tmin, tmax, th[k]) for k in range(CANDS)]
-            if taus[0] == 0:
-                taus[0] = tmin + int(np.argmin(dp[i, tmin:tmax + 1]))
+            taus = [Y.pick(dp[i], tmin, tmax, th[0])] + [Y.under(dp[i], tmin, tmax, th[k]) for k in range(1, CANDS)]
             picked[c0 + i] = taus
             for k, t in enumerate(taus):
                 if t == 0 or t in taus[:k] or not np.isfinite(dp[i, t]):
                     continue
-                dm, d0, dq = d[i, t - 1], d[i, t], d[i, t + 1]
-                den = 2 * (dm - 2 * d0 + dq)
-                delta = (dm - dq) / den if den > 0 else 0.0
-                delta = min(0.5, max(-0.5, delta))
-                cands[c0 + i, k] = (t, t + delta, dp[i, t], cents_of(t + delta, sr))
+                period = Y.refine(d[i], t)
+                cands[c0 + i, k] = (t, period, dp[i, t], cents_of(period, sr))
     return cands, (np.concatenate(dps) if dps else np.zeros((0, Y.W + 1))), picked
 
 

@@ -92,19 +92,55 @@ def test_guard_bands(gpu_ctx, first, count, hop):
 
 
 def test_argument_errors(gpu_ctx, mxlib):
+    """Every f0 entry point turns every bad argument down with MX_ERR_INVALID and writes no output: the tracker-side five
+    share one parse, the decode forms one check.  Launches of at most four frames, or none."""
+    from melonix_amd import _capi
+    lib, ctx = _capi.lib(), gpu_ctx.handle
     a = gpu_ctx.upload(np.zeros(10000, np.float32))
     F = mxlib.frame_count(10000, HOP)
+    # outputs, filled: host (track, cands, state) and device; sized for the four frames no case exceeds
+    host = [np.full(n, 0x5A, np.uint8) for n in (4 * 16, 4 * 64, 4)]
+    dev = [DevBuf(n, 0x5A) for n in (4 * 16, 4 * 64, 4)]
+    (h_track, h_cands, h_state), (d_track, d_cands, d_state) = [[b.ctypes.data for b in host], [b.ptr for b in dev]]
+
+    def untouched():
+        return all((b == 0x5A).all() for b in host) and all((b.read() == 0x5A).all() for b in dev)
+
     for kw in (dict(sr=0), dict(hop=0), dict(hop=20000), dict(first=F - 1, count=2), dict(fmin=0.0), dict(fmin=-5.0),
                dict(fmin=1000.0, fmax=900.0), dict(fmin=10.0, fmax=20.0), dict(threshold=float("nan"))):
         args = dict(sr=SR, hop=HOP, first=0, count=4)
         args.update(kw)
-        out = np.full(max(args["count"], 1), 0x5A, np.uint8).repeat(16)
-        from melonix_amd import _capi
-        rc = _capi.lib().mx_f0_track(gpu_ctx.handle, a.handle, args["sr"], args["hop"], args["first"], args["count"],
-                                     args.get("fmin", 55.0), args.get("fmax", 1760.0), args.get("threshold", 0.15),
-                                     out.ctypes.data)
-        assert rc == _capi.MX_ERR_INVALID, kw
-        assert (out == 0x5A).all()
+        common = (ctx, a.handle, args["sr"], args["hop"], args["first"], args["count"], args.get("fmin", 55.0),
+                  args.get("fmax", 1760.0), args.get("threshold", 0.15))
+        for name, rc in (("mx_f0_track", lib.mx_f0_track(*common, h_track)),
+                         ("mx_f0_track_dev", lib.mx_f0_track_dev(*common, d_track)),
+                         ("mx_f0_candidates", lib.mx_f0_candidates(*common, h_track, h_cands)),
+                         ("mx_f0_candidates_dev", lib.mx_f0_candidates_dev(*common, d_track, d_cands)),
+                         ("mx_f0_track_decoded", lib.mx_f0_track_decoded(*common, None, h_track))):
+            assert rc == _capi.MX_ERR_INVALID, (name, kw)
+        assert untouched(), kw
+
+    # the decode forms' own: a valid table of four frames, one bad argument at a time
+    track = np.zeros(4, mxlib.F0_DTYPE)
+    cands = np.zeros((4, 4), mxlib.F0_CAND_DTYPE)
+    d_tin, d_cin = DevBuf(track.nbytes), DevBuf(cands.nbytes)
+    good = (0.3, 0.1, 0.5, 1200)
+    bad_params = [good[:k] + (v,) + good[k + 1:] for k in range(3) for v in (float("nan"), -1.0, 17.0)]
+    bad_params += [good[:3] + (v,) for v in (-1, 12001)]
+    for vals in bad_params:
+        p = C.byref(_capi.F0DecodeParams(*vals))
+        rcs = (lib.mx_f0_decode(ctx, track.ctypes.data, cands.ctypes.data, 4, p, h_track, h_state),
+               lib.mx_f0_decode_dev(ctx, d_tin.ptr, d_cin.ptr, 4, p, d_track, d_state),
+               lib.mx_f0_track_decoded(ctx, a.handle, SR, HOP, 0, 4, 55.0, 1760.0, 0.15, p, h_track))
+        assert rcs == (_capi.MX_ERR_INVALID,) * 3, vals
+        assert untouched(), vals
+    for fn, t, c, o, st in ((lib.mx_f0_decode, track.ctypes.data, cands.ctypes.data, h_track, h_state),
+                            (lib.mx_f0_decode_dev, d_tin.ptr, d_cin.ptr, d_track, d_state)):
+        for call in ((t, c, -1, None, o, st), (None, c, 4, None, o, st), (t, None, 4, None, o, st), (t, c, 4, None, None, st)):
+            assert fn(ctx, *call) == _capi.MX_ERR_INVALID, (fn.__name__, call)
+            assert untouched(), (fn.__name__, call)
+    for b in dev + [d_tin, d_cin]:
+        b.free()
     a.free()
 
 

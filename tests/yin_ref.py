@@ -57,28 +57,51 @@ def cmnd(d):
     return np.concatenate([np.ones((d.shape[0], 1)), dp], axis=1)
 
 
+def descend(dp_row, t, tmax):
+    """Step 4's descent: forward from t while t+1 <= tmax and d'(t+1) < d'(t)."""
+    while t + 1 <= tmax and dp_row[t + 1] < dp_row[t]:
+        t += 1
+    return t
+
+
+def under(dp_row, tmin, tmax, theta):
+    """Step 4 without the fallback: the end of the descent from the first tau in range with d' < theta, or 0 for none."""
+    hit = np.nonzero(dp_row[tmin:tmax + 1] < theta)[0]
+    return descend(dp_row, tmin + int(hit[0]), tmax) if len(hit) else 0
+
+
 def pick(dp_row, tmin, tmax, theta):
-    under = np.nonzero(dp_row[tmin:tmax + 1] < theta)[0]
-    if len(under):
-        t = tmin + int(under[0])
-        while t + 1 <= tmax and dp_row[t + 1] < dp_row[t]:
-            t += 1
-        return t
-    return tmin + int(np.argmin(dp_row[tmin:tmax + 1]))
+    return under(dp_row, tmin, tmax, theta) or tmin + int(np.argmin(dp_row[tmin:tmax + 1]))
+
+
+def refine(d_row, t):
+    """Step 5: t + the clamped parabolic offset on d at t-1, t, t+1."""
+    dm, d0, dq = d_row[t - 1], d_row[t], d_row[t + 1]
+    den = 2 * (dm - 2 * d0 + dq)
+    delta = (dm - dq) / den if den > 0 else 0.0
+    return t + min(0.5, max(-0.5, delta))
+
+
+def frame_chunks(w, hop, first, count, chunk):
+    """The frames [first, first + count) in chunks: (c0, x, d, d') per chunk, c0 the chunk's first row."""
+    for c0 in range(0, count, chunk):
+        x = frames_of(w, hop, first + c0, min(chunk, count - c0))
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = diff_fft(x)
+            dp = cmnd(d)
+        yield c0, x, d, dp
+
+
+def default_count(n, hop, first, count):
+    return -(-n // hop) - first if count is None else count
 
 
 def track(w, sr, hop=256, first=0, count=None, fmin=55.0, fmax=1760.0, threshold=0.15, chunk=2048):
     """-> (records: list of (tau, period, aperiodicity, rms), dp: F x (W+1) d' rows, or None when not kept)."""
-    n = len(w)
-    if count is None:
-        count = -(-n // hop) - first
     tmin, tmax = tau_range(sr, fmin, fmax)
     theta = float(np.float32(threshold))
     recs, dps = [], []
-    for c0 in range(0, count, chunk):
-        x = frames_of(w, hop, first + c0, min(chunk, count - c0))
-        d = diff_fft(x)
-        dp = cmnd(d)
+    for _, x, d, dp in frame_chunks(w, hop, first, default_count(len(w), hop, first, count), chunk):
         dps.append(dp)
         rms = np.sqrt(np.sum(x * x, axis=1) / N)
         for i in range(x.shape[0]):
@@ -86,11 +109,7 @@ def track(w, sr, hop=256, first=0, count=None, fmin=55.0, fmax=1760.0, threshold
                 recs.append(SILENT)
                 continue
             t = pick(dp[i], tmin, tmax, theta)
-            dm, d0, dq = d[i, t - 1], d[i, t], d[i, t + 1]
-            den = 2 * (dm - 2 * d0 + dq)
-            delta = (dm - dq) / den if den > 0 else 0.0
-            delta = min(0.5, max(-0.5, delta))
-            recs.append((t, t + delta, dp[i, t], rms[i]))
+            recs.append((t, refine(d[i], t), dp[i, t], rms[i]))
     return recs, np.concatenate(dps) if dps else np.zeros((0, W + 1))
 
 
