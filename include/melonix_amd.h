@@ -511,6 +511,82 @@ int mx_detect_notes(const mx_f0 *track, int64_t count, int sampleRate, int hop, 
  * dTime 0 (the time map stays the identity).  The notes must be in order and not overlap. */
 int mx_correction_markers(const mx_note *notes, int64_t count, double strength, int scale_mask, mx_marker *out);
 
+/* ---- Formant-preserving PSOLA rendering driven by the f0 track (BUILD-DEFINED; restated in f64 by tests/psola_ref.py) ----
+ * The granular resampler and the phase vocoder both move the spectral envelope with the pitch.  Time-domain
+ * pitch-synchronous overlap-add does not: two-period Hann grains are cut from the source at the spacing the f0 track gives
+ * and laid down again at that spacing divided by the pitch ratio; each grain keeps its shape, so the formants stay.  It wants
+ * a monophonic, tracked take.  Markers steer it as they steer mx_pv_render (same time map, same bend, same output length).
+ *
+ * Inputs: the audio (n samples at sr); a track of count = mx_frame_count(n, hop) mx_f0 records, frame h centred on h*hop,
+ * plain or decoded; the parameters below; the markers, sorted.  All planning arithmetic is host binary64, no contraction.
+ *   voicing   frame h is voiced by mx_detect_notes' rule (tau > 0, aperiodicity < threshold, rms >= rms_floor) and, in
+ *             addition, a finite period in [2, MX_PSOLA_MAX_HALF]; any other record is unvoiced.
+ *   P(x)      for a source position x, from frame h = clamp(floor(x/hop + 1/2), 0, count-1): (double)period_h if the frame
+ *             is voiced, else unvoiced_period U; voiced(x) is read the same way.
+ *   analysis  a_0 = 0, p_m = P(a_m), v_m = voiced(a_m), a_{m+1} = a_m + p_m, while a_m - p_m < n (the last window reaches
+ *             past the end of the file: the tail keeps its full window sum).
+ *   synthesis L = mx_pv_render_length(n, sr, markers).  s_0 = 0; src_k = max(time2sample(s_k/sr), 0); m(k) = the analysis
+ *             mark nearest to src_k (the last mark beyond it; ties: the HIGHER index — time2sample truncates, and at a
+ *             period of 2 the identity map lands halfway between two marks); H_k = p_{m(k)};
+ *             r_k = clamp(2^((double)time2pitchbend(s_k/sr) / 12), 1/2, 2) if v_{m(k)}, else 1 (unvoiced sound keeps its
+ *             spacing; a bend that is not a number counts as the lower clamp); s_{k+1} = s_k + H_k/r_k; grains while
+ *             s_k - H_k < L.  Time-stretching falls out of src_k: marks are repeated or skipped.
+ *   record    one mx_psola_grain per k (below).  A fraction that rounds to 1.f as binary32 moves into its integer.
+ *             centre is non-decreasing in k and can repeat (H = 2 at r = 2: a spacing of exactly 1, the least the clamps
+ *             allow); centre + centre_frac is strictly increasing.
+ *   output    for sample i, over the grains with out_lo <= i < out_hi IN ASCENDING k, two binary32 sums:
+ *               u = ((float)(i - centre) - centre_frac) * inv_half, the grain skipped if |u| >= 1;
+ *               w = 0.5 + 0.5 cos(pi u);  x = (1 - src_frac) * audio[i + src_off] + src_frac * audio[i + src_off + 1]
+ *               (zeros outside the file; the resampler's form, no contraction);  S += w * x, W += w;
+ *             y_i = W > 0 ? S / max(W, 0.25f) : 0;  int16 = (int16)(clamp(y, -1, 1) * 32767.) as in the phase vocoder.
+ *             Dividing by the window sum makes a zero-bend, identity-map render the input and keeps the level of a raised
+ *             pitch; the floor lets the tails taper where a lowered pitch leaves gaps.  The order is fixed, so the result
+ *             does not depend on how the kernel tiles the output. */
+#define MX_PSOLA_MAX_HALF 2048
+typedef struct mx_psola_params {
+  float threshold, rms_floor; /* the voicing rule's; finite */
+  float unvoiced_period;      /* U, samples, in [32, MX_PSOLA_MAX_HALF] */
+} mx_psola_params;
+typedef struct mx_psola_grain {
+  int32_t out_lo, out_hi; /* outputs i in [out_lo, out_hi): max(0, floor(s-H)+1) .. min(L, ceil(s+H)) */
+  int32_t src_off;        /* floor(a_m - s): the grain reads the source at i + src_off (+1) */
+  float src_frac;         /* (a_m - s) - src_off, in [0, 1) */
+  int32_t centre;         /* floor(s) */
+  float centre_frac;      /* s - centre */
+  float inv_half;         /* 1 / H */
+  int32_t mark;           /* m(k), for inspection */
+} mx_psola_grain;
+/* {0.15f, 1e-3f, 256.f} */
+void mx_psola_params_default(mx_psola_params *p);
+/* The grain records of a render and its length (host).  params NULL: the defaults.  *grains is library-allocated (free
+ * with mx_free).  MX_ERR_INVALID for count != mx_frame_count(n, hop), hop outside [1, 16384], sr <= 0, U out of range or a
+ * parameter that is not finite, n > INT32_MAX - 2*MX_AUDIO_PAD, and whatever mx_pv_render_length refuses of the markers. */
+int mx_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params *params,
+                  const mx_marker *markers, int nmarkers, mx_psola_grain **grains, int64_t *ngrains, int64_t *nsamples);
+/* The overlap-add over records in HBM; d_pcm_f32 / d_pcm_i16: nsamples each in HBM (either may be NULL).  Asynchronous on
+ * the context's stream.  nsamples == 0: nothing; ngrains == 0: the outputs are zero-filled.
+ * PRECONDITION (not checked on the device — mx_psola_synth, the host-pointer entry point, does check it): the records are
+ * what mx_psola_plan makes for this audio: centre + centre_frac strictly increasing, 0 <= out_lo <= out_hi <= nsamples,
+ * every window inside centre +- 2049, inv_half finite and >= 1/2048, both fractions in [0, 1), every source index
+ * i + src_off (+1) inside [-MX_AUDIO_PAD, n + MX_AUDIO_PAD - 1].  Records that break it give wrong samples and nothing
+ * worse: the kernel clamps every source index into the padded buffer, every scan to [0, ngrains), and stores nothing
+ * outside [0, nsamples). */
+int mx_psola_synth_dev(mx_ctx *ctx, const mx_audio *a, const mx_psola_grain *d_grains, int64_t ngrains, int64_t nsamples,
+                       float *d_pcm_f32, int16_t *d_pcm_i16);
+/* Same, host pointers.  Checks every record against the precondition above and returns MX_ERR_INVALID before any launch,
+ * the outputs untouched.  Blocks. */
+int mx_psola_synth(mx_ctx *ctx, const mx_audio *a, const mx_psola_grain *grains, int64_t ngrains, int64_t nsamples,
+                   float *pcm_f32_out, int16_t *pcm_i16_out);
+/* Plan and synthesis in one call: mx_pv_render_length(n, sr, markers) samples each (host, either may be NULL).  Blocks. */
+int mx_psola_render(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                    const mx_psola_params *params, const mx_marker *markers, int nmarkers, float *pcm_f32_out,
+                    int16_t *pcm_i16_out);
+/* Same, the PCM stays in HBM (the track and the markers are host arrays).  Blocks until the device is done with the
+ * records it uploaded. */
+int mx_psola_render_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                        const mx_psola_params *params, const mx_marker *markers, int nmarkers, float *d_pcm_f32,
+                        int16_t *d_pcm_i16);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

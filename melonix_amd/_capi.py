@@ -62,6 +62,15 @@ class Note(C.Structure):
                 ("note", C.c_double), ("aperiodicity", C.c_float), ("spread", C.c_float)]
 
 
+class PsolaParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("rms_floor", C.c_float), ("unvoiced_period", C.c_float)]
+
+
+class PsolaGrain(C.Structure):
+    _fields_ = [("out_lo", C.c_int32), ("out_hi", C.c_int32), ("src_off", C.c_int32), ("src_frac", C.c_float),
+                ("centre", C.c_int32), ("centre_frac", C.c_float), ("inv_half", C.c_float), ("mark", C.c_int32)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -72,6 +81,9 @@ NOTE_DTYPE = np.dtype([("start_sample", "<i4"), ("end_sample", "<i4"), ("first_f
                        ("note", "<f8"), ("aperiodicity", "<f4"), ("spread", "<f4")])
 MARKER_DTYPE = np.dtype({"names": ["sample", "note", "dTime", "pitchBend"], "formats": ["<i4", "<f8", "<f8", "<f8"],
                          "offsets": [0, 8, 16, 24], "itemsize": 32})
+PSOLA_GRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_off", "<i4"), ("src_frac", "<f4"), ("centre", "<i4"),
+                              ("centre_frac", "<f4"), ("inv_half", "<f4"), ("mark", "<i4")])
+assert PSOLA_GRAIN_DTYPE.itemsize == C.sizeof(PsolaGrain) == 32
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -166,6 +178,13 @@ SIGNATURES = {
     "mx_note_params_default": (None, [C.POINTER(NoteParams)]),
     "mx_detect_notes": (_i, [_vp, _i64, _i, _i, _i64, C.POINTER(NoteParams), C.POINTER(C.POINTER(Note)), C.POINTER(_i64)]),
     "mx_correction_markers": (_i, [_vp, _i64, _d, _i, _vp]),
+    "mx_psola_params_default": (None, [C.POINTER(PsolaParams)]),
+    "mx_psola_plan": (_i, [_i64, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, C.POINTER(_vp), C.POINTER(_i64),
+                           C.POINTER(_i64)]),
+    "mx_psola_synth_dev": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "mx_psola_synth": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "mx_psola_render": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _vp]),
+    "mx_psola_render_dev": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _vp]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

@@ -41,6 +41,8 @@ UNITS = [
     ("f0_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     # build-defined Viterbi decode over the YIN candidate ladder: integer min-plus scans, no floating point beyond q()
     ("f0_decode.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined PSOLA overlap-add: the resampler's interpolation form, products rounded before the sums
+    ("psola_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -50,9 +52,11 @@ UNITS = [
     ("capi_resynth.cpp", "hip", []),
     ("capi_pyramid.cpp", "hip", []),
     ("capi_f0.cpp", "hip", []),
+    ("capi_psola.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
+    ("psola_plan.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

@@ -32,6 +32,13 @@ std::vector<mx_note> PitchTrack::notes() const {
   return notes(p);
 }
 
+mx_psola_params PitchTrack::psolaParams() const {
+  mx_psola_params p;
+  mx_psola_params_default(&p);
+  if (decoded_) p.threshold = 2.f * threshold_;
+  return p;
+}
+
 std::vector<mx_note> PitchTrack::notes(const mx_note_params &p) const {
   mx_note *v = nullptr;
   int64_t n = 0;

@@ -4,7 +4,8 @@
 //
 //   melonix::PitchTrack track(wavData, sampleRate);   // uploads once, tracks every frame (hop 256) on the GPU
 //   markers = track.correctionMarkers(1.f, 0);          // every note onto the semitone grid ...
-//   invalidateCache();                                  // ... and exportWav / renderPV retune the take
+//   invalidateCache();                                  // ... and exportWav / renderPV retune the take;
+//   resynth.exportWavPSOLA(file, markers, track.frames(), track.hop());   // or, the formants left in place, PSOLA
 #pragma once
 #include <cstdint>
 #include <span>
@@ -31,6 +32,9 @@ public:
   // threshold = 2 x the tracker's: the decoder has made the voicing decision, and its candidates reach up to 2 theta
   std::vector<mx_note> notes() const;
   std::vector<mx_note> notes(const mx_note_params &p) const;
+  // the voicing parameters Resynth::renderPSOLA / exportWavPSOLA should read this track with: the defaults
+  // (mx_psola_params_default), on a decoded track with threshold = 2 x the tracker's, as notes() takes it
+  mx_psola_params psolaParams() const;
   // two markers per note: strength in [0, 1], scaleMask bits 0..11 = pitch classes (A = 0), 0 = all twelve
   std::vector<Marker> correctionMarkers(float strength, int scaleMask) const;
 

@@ -103,6 +103,34 @@ bool Resynth::exportWavPV(const std::string &fileName, const std::vector<Marker>
   return true;
 }
 
+std::vector<float> Resynth::renderPSOLA(const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
+                                        const mx_psola_params *params) const {
+  std::vector<float> pcm;
+  if (!ok()) return pcm;
+  const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
+  const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
+  if (m <= 0) return pcm;
+  pcm.resize((size_t)m);
+  if (mx_psola_render(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(), pcm.data(),
+                      nullptr) != MX_OK)
+    pcm.clear();
+  return pcm;
+}
+
+bool Resynth::exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track,
+                             int hop, const mx_psola_params *params) const {
+  if (!ok()) return false;
+  const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
+  const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
+  if (m <= 0) return false;
+  std::vector<int16_t> pcm16((size_t)m);
+  if (mx_psola_render(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(), nullptr,
+                      pcm16.data()) != MX_OK)
+    return false;
+  saveWav(fileName, pcm16, sampleRate);
+  return true;
+}
+
 bool Resynth::exportWav(const std::string &fileName, const std::vector<Marker> &markers) const {
   if (!ok()) return false;
   // schedule on the host, then resynthesis + int16 + saveWav (app.cpp:1209-1214) with the PCM streamed from the device

@@ -4,6 +4,8 @@
 //   melonix::Resynth r(wavData, sampleRate);          // uploads once, scans grains on the GPU
 //   r.exportWav(fileName, markers);                   // App::exportWav: schedule -> GPU -> saveWav
 //   auto pcm = r.render(markers);                     // the float PCM exportWav builds (app.cpp:1200-1207)
+//   r.exportWavPSOLA(fileName, markers, track.frames(), track.hop());   // NOT in the reference: the same markers rendered
+//                                                     // with the formants left in place (melonix::PitchTrack track)
 //
 //   double cur = cursorSec; auto buf = r.refill(markers, cur, dur + 1500, &cur);
 //                                                     // App::playback's refill loop (app.cpp:272-274):
@@ -24,6 +26,8 @@
 
 struct mx_ctx;
 struct mx_audio;
+struct mx_f0;
+struct mx_psola_params;
 
 namespace melonix {
 
@@ -49,6 +53,14 @@ public:
   // renderPV() is what exportWavPV() hands to saveWav.
   std::vector<float> renderPV(const std::vector<Marker> &markers) const;
   bool exportWavPV(const std::string &fileName, const std::vector<Marker> &markers) const;
+  // ... and formant-preserving: TD-PSOLA driven by the f0 track of the same take (mx_psola_render; PitchTrack::frames() and
+  // hop()).  The markers steer it as they steer renderPV(), and the output has renderPV()'s length; the vowel resonances
+  // stay where they were.  Wants a monophonic, tracked take.  params null: mx_psola_params_default — on a decoded track
+  // hand in PitchTrack::psolaParams() (twice the tracker's threshold, as PitchTrack::notes() takes it).
+  std::vector<float> renderPSOLA(const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
+                                 const mx_psola_params *params = nullptr) const;
+  bool exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
+                      const mx_psola_params *params = nullptr) const;
   // what App::playback appends to an empty restWav when asked for `need` samples at warped time `cursor`
   std::vector<float> refill(const std::vector<Marker> &markers, double cursor, std::size_t need,
                             double *cursorEnd = nullptr) const;

@@ -1,0 +1,134 @@
+// psola_plan.cpp — see psola_plan.h.  Built with g++ -ffp-contract=off: tests/psola_ref.py restates the plan in Python and
+// expects the same doubles.
+#include "psola_plan.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "host_logic.h"
+
+namespace mx {
+
+namespace {
+
+int invalid(std::string &err, const char *fmt, long long a = 0, long long b = 0) {
+  char buf[160];
+  snprintf(buf, sizeof buf, fmt, a, b);
+  err = buf;
+  return MX_ERR_INVALID;
+}
+
+}  // namespace
+
+int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
+                     const mx_marker *markers, int nmarkers, std::vector<mx_psola_grain> &grains, int64_t &nsamples,
+                     std::string &err) {
+  grains.clear();
+  nsamples = 0;
+  if (n < 0 || n > (int64_t)INT32_MAX - 2 * MX_AUDIO_PAD) return invalid(err, "%lld samples: outside [0, INT32_MAX - 2*MX_AUDIO_PAD]", n);
+  if (sampleRate <= 0) return invalid(err, "sample rate %lld", sampleRate);
+  if (hop < 1 || hop > 16384) return invalid(err, "hop %lld outside [1, 16384]", hop);
+  if (count != (n + hop - 1) / hop) return invalid(err, "%lld records for a file of %lld frames", count, (n + hop - 1) / hop);
+  if (count > 0 && !track) return invalid(err, "null track");
+  if (!std::isfinite(p.threshold) || !std::isfinite(p.rms_floor)) return invalid(err, "threshold / rms_floor is not finite");
+  if (!(p.unvoiced_period >= 32.f && p.unvoiced_period <= (float)MX_PSOLA_MAX_HALF))
+    return invalid(err, "unvoiced period outside [32, %lld]", MX_PSOLA_MAX_HALF);
+  // the output length, and the marker checks, are the phase vocoder's
+  PvPlan pv;
+  if (const int rc = build_pv_plan(markers, nmarkers, sampleRate, n, pv, err)) return rc;
+  const int64_t L = pv.n_out;
+  if (L > (int64_t)INT32_MAX - 2 * kPsolaReach) return invalid(err, "%lld output samples: centres beyond int32", L);
+  nsamples = L;
+  if (n == 0 || L == 0) return MX_OK;
+
+  const double U = (double)p.unvoiced_period;
+  // P(x) and voiced(x): period_of(x) < 0 marks an unvoiced frame
+  auto period_at = [&](double x, bool &voiced) {
+    double h = std::floor(x / (double)hop + 0.5);
+    h = h < 0. ? 0. : (h > (double)(count - 1) ? (double)(count - 1) : h);
+    const mx_f0 &r = track[(int64_t)h];
+    voiced = r.tau > 0 && r.aperiodicity < p.threshold && r.rms >= p.rms_floor && std::isfinite(r.period) && r.period >= 2.f &&
+             r.period <= (float)MX_PSOLA_MAX_HALF;
+    return voiced ? (double)r.period : U;
+  };
+
+  // analysis marks
+  std::vector<double> a, per;
+  std::vector<char> vo;
+  for (double am = 0.;;) {
+    bool v;
+    const double pm = period_at(am, v);
+    if (!(am - pm < (double)n)) break;
+    a.push_back(am);
+    per.push_back(pm);
+    vo.push_back((char)v);
+    am = am + pm;
+  }
+
+  // synthesis marks
+  const TimeMap tm(markers, nmarkers, sampleRate, n);
+  const double sr = (double)sampleRate;
+  int hint_s = -1, hint_b = -1;
+  for (double s = 0.;;) {
+    const double t = s / sr;
+    const int64_t src = std::max<int64_t>(tm.time2sample(t, hint_s), 0);
+    // the nearest mark (the marks are strictly increasing); beyond the last mark, the last.  Ties go to the HIGHER index:
+    // time2sample truncates, so the position it stands for lies in [src, src + 1) — at a period of 2 the identity map gives
+    // src = s - 1 for some even s, halfway between the mark the grain belongs to and the one before
+    size_t m = (size_t)(std::upper_bound(a.begin(), a.end(), (double)src) - a.begin());
+    if (m == a.size() || (m > 0 && (double)src - a[m - 1] < a[m] - (double)src)) --m;
+    const double H = per[m];
+    if (!(s - H < (double)L)) break;
+    double r = 1.;
+    if (vo[m]) {
+      r = std::exp2((double)tm.time2pitchbend(t, hint_b) / 12.0);
+      r = !(r >= 0.5) ? 0.5 : (r > 2. ? 2. : r);
+    }
+    mx_psola_grain g{};
+    g.out_lo = (int32_t)std::max(0., std::floor(s - H) + 1.);
+    g.out_hi = (int32_t)std::min((double)L, std::ceil(s + H));
+    const double d = a[m] - s, dfl = std::floor(d), cfl = std::floor(s);
+    g.src_off = (int32_t)dfl;
+    g.src_frac = (float)(d - dfl);
+    if (g.src_frac >= 1.f) {
+      g.src_off += 1;
+      g.src_frac = 0.f;
+    }
+    g.centre = (int32_t)cfl;
+    g.centre_frac = (float)(s - cfl);
+    if (g.centre_frac >= 1.f) {
+      g.centre += 1;
+      g.centre_frac = 0.f;
+    }
+    g.inv_half = (float)(1. / H);
+    g.mark = (int32_t)m;
+    grains.push_back(g);
+    s = s + H / r;
+  }
+  return MX_OK;
+}
+
+int check_psola_grains(const mx_psola_grain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err) {
+  double prev = -HUGE_VAL;
+  for (int64_t k = 0; k < ngrains; ++k) {
+    const mx_psola_grain &r = g[k];
+    if (!(r.centre_frac >= 0.f && r.centre_frac < 1.f) || !(r.src_frac >= 0.f && r.src_frac < 1.f))
+      return invalid(err, "grain %lld: a fraction outside [0, 1)", k);
+    const double key = (double)r.centre + (double)r.centre_frac;
+    if (!(key > prev)) return invalid(err, "grain %lld: centre + centre_frac does not increase", k);
+    prev = key;
+    if (r.out_lo < 0 || r.out_lo > r.out_hi || (int64_t)r.out_hi > nsamples)
+      return invalid(err, "grain %lld: window outside the %lld output samples", k, nsamples);
+    if (!std::isfinite(r.inv_half) || !(r.inv_half >= 1.f / (float)MX_PSOLA_MAX_HALF))
+      return invalid(err, "grain %lld: inv_half is not finite or below 1/%lld", k, MX_PSOLA_MAX_HALF);
+    if (r.out_lo == r.out_hi) continue;  // (no output reads it)
+    if ((int64_t)r.out_lo < (int64_t)r.centre - kPsolaReach || (int64_t)r.out_hi - 1 > (int64_t)r.centre + kPsolaReach)
+      return invalid(err, "grain %lld: window beyond centre +- %lld", k, kPsolaReach);
+    if ((int64_t)r.out_lo + r.src_off < -(int64_t)MX_AUDIO_PAD || (int64_t)r.out_hi + r.src_off > n + (int64_t)MX_AUDIO_PAD - 1)
+      return invalid(err, "grain %lld: reads the source outside its pads", k);
+  }
+  return MX_OK;
+}
+
+}  // namespace mx

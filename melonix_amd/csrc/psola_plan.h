@@ -1,0 +1,26 @@
+// psola_plan.h — the host side of the PSOLA renderer (definition: include/melonix_amd.h): analysis and synthesis marks from
+// an f0 track and the markers, as grain records for psola_kernels.hip; and the check the host-pointer entry point makes of
+// records it is handed.  Pure host code like host_logic.cpp.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/melonix_amd.h"
+
+namespace mx {
+
+constexpr mx_psola_params kPsolaDefaults{0.15f, 1e-3f, 256.f};
+// how far from its centre a grain's window may reach (MX_PSOLA_MAX_HALF + the centre's floor): what the kernel's search for
+// the first grain of a tile relies on, and what the record check enforces
+constexpr int kPsolaReach = MX_PSOLA_MAX_HALF + 1;
+
+// Arguments checked (the f0 family's conventions), then the plan.  MX_OK, or MX_ERR_INVALID with `err` set.
+int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
+                     const mx_marker *markers, int nmarkers, std::vector<mx_psola_grain> &grains, int64_t &nsamples,
+                     std::string &err);
+
+// The precondition of mx_psola_synth_dev on `ngrains` records for an audio of n samples.  MX_OK, or MX_ERR_INVALID with `err`.
+int check_psola_grains(const mx_psola_grain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err);
+
+}  // namespace mx
