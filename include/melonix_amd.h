@@ -587,6 +587,71 @@ int mx_psola_render_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop,
                         const mx_psola_params *params, const mx_marker *markers, int nmarkers, float *d_pcm_f32,
                         int16_t *d_pcm_i16);
 
+/* ---- Independent formant shift on the PSOLA renderer (BUILD-DEFINED; restated in f64 by tests/psola_formant_ref.py) ----
+ * PSOLA pins the spectral envelope; this moves it on purpose, by some semitones, while the note stays where the grain
+ * spacing puts it.  A grain that is read from the source at step phi instead of 1, inside the same output window and at the
+ * same output spacing, has its envelope scaled by phi; its pitch is still what the spacing says.  Marks, spacing, voicing,
+ * r_k and the output length are exactly mx_psola_plan's: the same k, the same out_lo / out_hi / centre / centre_frac /
+ * inv_half.
+ *   curve     npoints control points {sample, semitones}; sample is a position in the SOURCE.  Samples strictly increasing,
+ *             semitones finite, anything else MX_ERR_INVALID.  F(x) in binary64: the first point's value for x below its
+ *             sample, the last point's from its sample on, and between points j and j+1 (sample_j <= x < sample_{j+1})
+ *             F(x) = y_j + (x - sample_j) * (y_{j+1} - y_j) / (sample_{j+1} - sample_j), evaluated in that order; no
+ *             points: F = 0.
+ *   step      for grain k, phi_k = clamp(exp2(F(a_{m(k)}) / 12), 1/2, 2) in binary64, a_{m(k)} the analysis mark the plan
+ *             picks for the grain; voiced and unvoiced grains alike, so the timbre has no step at a voicing switch.
+ *             step_k = (int)floor(phi_k * 65536 + 0.5), in [32768, 131072].  The Q16 step IS the definition, not an
+ *             approximation of it: everything downstream is exact integer arithmetic, on the host and on the device.
+ *   record    p0 = a_m - ((double)step / 65536.0) * (double)centre_frac, the source position of output sample `centre`
+ *             (centre_frac the stored binary32 value, after its carry); q = (int64)floor(p0 * 65536.0 + 0.5);
+ *             src_idx = q >> 16 (a floor), src_q = q & 65535.
+ *   output    for sample i, over the grains in ascending k: u and w exactly as above;
+ *               pos = (src_idx << 16) + src_q + step * (i - centre)   (|step * (i - centre)| < 2^29: no window reaches
+ *               further than 2049 from its centre);  idx = pos >> 16;  f = (float)(pos & 65535) * 2^-16, exact;
+ *               x = (1 - f) * audio[idx] + f * audio[idx + 1] (zeros outside the file, no contraction);
+ *             S, W, the floor of 1/4 and the int16 conversion unchanged.
+ * What follows from the definition (not bugs):
+ *   - phi > 1 reads the source faster than it plays it, through linear interpolation and with no anti-alias filter: the
+ *     granular resampler at a raised pitch does the same.
+ *   - at phi = 2 every grain holds twice as many periods, and the render's pitch is an octave up (the reference render
+ *     shows +12.0 st at formant +12).  The clamp is therefore an octave; the useful range is a few semitones.
+ *   - the source reach grows to 2 * 2049 samples either side of a mark: still well inside MX_AUDIO_PAD. */
+typedef struct mx_formant_point {
+  int32_t sample;  /* position in the source */
+  float semitones; /* envelope shift there */
+} mx_formant_point;
+typedef struct mx_psola_fgrain {
+  int32_t out_lo, out_hi; /* as mx_psola_grain */
+  int32_t src_idx;        /* floor of the source position of output sample `centre` */
+  uint32_t src_q;         /* its fraction in Q16, < 65536 */
+  int32_t centre;         /* as mx_psola_grain */
+  float centre_frac;
+  float inv_half;
+  uint32_t step; /* Q16 source step per output sample, in [32768, 131072] */
+} mx_psola_fgrain;
+/* mx_psola_plan with the curve: one record per synthesis mark (npoints == 0: every step is 65536).  *fgrains is
+ * library-allocated (free with mx_free).  MX_ERR_INVALID for what mx_psola_plan refuses and for a bad curve. */
+int mx_psola_plan_formant(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params *params,
+                          const mx_marker *markers, int nmarkers, const mx_formant_point *points, int npoints,
+                          mx_psola_fgrain **fgrains, int64_t *ngrains, int64_t *nsamples);
+/* mx_psola_synth_dev over such records in HBM.  Asynchronous on the context's stream.
+ * PRECONDITION (not checked on the device — mx_psola_synth_formant does check it): mx_psola_synth_dev's on the fields the two
+ * records share, step in [32768, 131072], src_q < 65536, and every source index idx (+1) a window reaches inside
+ * [-MX_AUDIO_PAD, n + MX_AUDIO_PAD - 1].  Records that break it give wrong samples and nothing worse, by the same clamps. */
+int mx_psola_synth_formant_dev(mx_ctx *ctx, const mx_audio *a, const mx_psola_fgrain *d_fgrains, int64_t ngrains,
+                               int64_t nsamples, float *d_pcm_f32, int16_t *d_pcm_i16);
+/* Same, host pointers.  Checks every record and returns MX_ERR_INVALID before any launch, the outputs untouched.  Blocks. */
+int mx_psola_synth_formant(mx_ctx *ctx, const mx_audio *a, const mx_psola_fgrain *fgrains, int64_t ngrains, int64_t nsamples,
+                           float *pcm_f32_out, int16_t *pcm_i16_out);
+/* Plan and synthesis in one call, as mx_psola_render / mx_psola_render_dev.  With npoints == 0 they ARE those: the plain
+ * records, the plain kernel, the same bytes. */
+int mx_psola_render_formant(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                            const mx_psola_params *params, const mx_marker *markers, int nmarkers,
+                            const mx_formant_point *points, int npoints, float *pcm_f32_out, int16_t *pcm_i16_out);
+int mx_psola_render_formant_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                                const mx_psola_params *params, const mx_marker *markers, int nmarkers,
+                                const mx_formant_point *points, int npoints, float *d_pcm_f32, int16_t *d_pcm_i16);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

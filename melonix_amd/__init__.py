@@ -14,13 +14,14 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (F0_CAND_DTYPE, F0_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, PITCH_DTYPE, PSOLA_GRAIN_DTYPE,  # noqa: F401
-                    STEP_DTYPE, MxError)
+from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, PITCH_DTYPE,  # noqa: F401
+                    PSOLA_FGRAIN_DTYPE, PSOLA_GRAIN_DTYPE, STEP_DTYPE, MxError)
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
            "F0_DTYPE", "F0_CAND_DTYPE", "f0_decode_params_default", "NOTE_DTYPE", "MARKER_DTYPE", "note_params_default", "detect_notes", "correction_markers",
-           "PSOLA_GRAIN_DTYPE", "psola_params_default", "psola_plan"]
+           "PSOLA_GRAIN_DTYPE", "psola_params_default", "psola_plan",
+           "PSOLA_FGRAIN_DTYPE", "FORMANT_POINT_DTYPE", "psola_plan_formant"]
 
 
 def _ptr(a):
@@ -412,6 +413,39 @@ class Context:
                                                 len(track), _psola_params(params), m, len(markers), _ptr(f32), _ptr(i16)))
         return f32, i16
 
+    # ---- the independent formant shift on the PSOLA renderer (build-defined; include/melonix_amd.h) ----
+    def psola_synth_formant(self, audio: Audio, fgrains, nsamples: int, want_f32: bool = True, want_i16: bool = True):
+        """psola_synth over PSOLA_FGRAIN_DTYPE records (psola_plan_formant); the records are checked first."""
+        fgrains = np.ascontiguousarray(fgrains, dtype=PSOLA_FGRAIN_DTYPE)
+        f32 = np.empty(nsamples, dtype=np.float32) if want_f32 else None
+        i16 = np.empty(nsamples, dtype=np.int16) if want_i16 else None
+        _capi.check(_capi.lib().mx_psola_synth_formant(self.handle, audio.handle, _ptr(fgrains) if len(fgrains) else None,
+                                                       len(fgrains), nsamples, _ptr(f32), _ptr(i16)))
+        return f32, i16
+
+    def psola_synth_formant_dev(self, audio: Audio, d_fgrains: int, ngrains: int, nsamples: int, d_f32: int | None,
+                                d_i16: int | None):
+        """Device pointers; asynchronous on the context's stream.  The records are NOT checked (include/melonix_amd.h)."""
+        _capi.check(_capi.lib().mx_psola_synth_formant_dev(self.handle, audio.handle, C.c_void_p(d_fgrains or 0), ngrains, nsamples,
+                                                           C.c_void_p(d_f32 or 0), C.c_void_p(d_i16 or 0)))
+
+    def psola_render_formant(self, audio: Audio, sr: int, hop: int, track, markers, points, want_f32: bool = True,
+                             want_i16: bool = True, **params):
+        """psola_render with the envelope moved along `points`: (source sample, semitones) pairs, samples strictly
+        increasing.  No points: psola_render itself."""
+        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+        m = _capi.markers_array(markers)
+        pts = _formant_points(points)
+        cnt = _capi.lib().mx_pv_render_length(audio.n, sr, m, len(markers))
+        if cnt < 0:
+            _capi.check(int(cnt))
+        f32 = np.empty(cnt, dtype=np.float32) if want_f32 else None
+        i16 = np.empty(cnt, dtype=np.int16) if want_i16 else None
+        _capi.check(_capi.lib().mx_psola_render_formant(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
+                                                        len(track), _psola_params(params), m, len(markers),
+                                                        _ptr(pts) if len(pts) else None, len(pts), _ptr(f32), _ptr(i16)))
+        return f32, i16
+
     # ---- one rank of a multi-GPU phase-vocoder run (melonix_amd.shard.pv_pitch_shift_rank drives these) ----
     def pv_shard_analyze(self, audio: Audio, semitones: float, rank: int, world: int):
         """Stage 1 -> (tot_sums uint32[2048], tot_org uint16[2048]): this rank's frames as one map of the phase row."""
@@ -668,5 +702,31 @@ def psola_plan(n: int, sr: int, hop: int, track, markers, **params):
     _capi.check(L.mx_psola_plan(n, sr, hop, _ptr(track) if len(track) else None, len(track), _psola_params(params), m,
                                 len(markers), C.byref(out), C.byref(cnt), C.byref(ns)))
     grains = np.frombuffer(C.string_at(out, cnt.value * PSOLA_GRAIN_DTYPE.itemsize), dtype=PSOLA_GRAIN_DTYPE).copy()
+    L.mx_free(out)
+    return grains, ns.value
+
+
+def _formant_points(points):
+    """(sample, semitones) pairs, or a FORMANT_POINT_DTYPE array -> a contiguous FORMANT_POINT_DTYPE array."""
+    if isinstance(points, np.ndarray) and points.dtype == FORMANT_POINT_DTYPE:
+        return np.ascontiguousarray(points)
+    out = np.zeros(len(points), dtype=FORMANT_POINT_DTYPE)
+    for i, (s, st) in enumerate(points):
+        out[i] = (int(s), np.float32(st))
+    return out
+
+
+def psola_plan_formant(n: int, sr: int, hop: int, track, markers, points, **params):
+    """psola_plan with a formant curve -> (PSOLA_FGRAIN_DTYPE array, nsamples).  points: (source sample, semitones) pairs,
+    samples strictly increasing; none: every record's step is 65536."""
+    track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+    m = _capi.markers_array(markers)
+    pts = _formant_points(points)
+    out, cnt, ns = C.c_void_p(), C.c_int64(), C.c_int64()
+    L = _capi.lib()
+    _capi.check(L.mx_psola_plan_formant(n, sr, hop, _ptr(track) if len(track) else None, len(track), _psola_params(params), m,
+                                        len(markers), _ptr(pts) if len(pts) else None, len(pts), C.byref(out), C.byref(cnt),
+                                        C.byref(ns)))
+    grains = np.frombuffer(C.string_at(out, cnt.value * PSOLA_FGRAIN_DTYPE.itemsize), dtype=PSOLA_FGRAIN_DTYPE).copy()
     L.mx_free(out)
     return grains, ns.value

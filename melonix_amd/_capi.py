@@ -71,6 +71,15 @@ class PsolaGrain(C.Structure):
                 ("centre", C.c_int32), ("centre_frac", C.c_float), ("inv_half", C.c_float), ("mark", C.c_int32)]
 
 
+class FormantPoint(C.Structure):
+    _fields_ = [("sample", C.c_int32), ("semitones", C.c_float)]
+
+
+class PsolaFGrain(C.Structure):
+    _fields_ = [("out_lo", C.c_int32), ("out_hi", C.c_int32), ("src_idx", C.c_int32), ("src_q", C.c_uint32),
+                ("centre", C.c_int32), ("centre_frac", C.c_float), ("inv_half", C.c_float), ("step", C.c_uint32)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -84,6 +93,10 @@ MARKER_DTYPE = np.dtype({"names": ["sample", "note", "dTime", "pitchBend"], "for
 PSOLA_GRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_off", "<i4"), ("src_frac", "<f4"), ("centre", "<i4"),
                               ("centre_frac", "<f4"), ("inv_half", "<f4"), ("mark", "<i4")])
 assert PSOLA_GRAIN_DTYPE.itemsize == C.sizeof(PsolaGrain) == 32
+FORMANT_POINT_DTYPE = np.dtype([("sample", "<i4"), ("semitones", "<f4")])
+PSOLA_FGRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_idx", "<i4"), ("src_q", "<u4"), ("centre", "<i4"),
+                               ("centre_frac", "<f4"), ("inv_half", "<f4"), ("step", "<u4")])
+assert PSOLA_FGRAIN_DTYPE.itemsize == C.sizeof(PsolaFGrain) == 32 and FORMANT_POINT_DTYPE.itemsize == C.sizeof(FormantPoint) == 8
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -185,6 +198,12 @@ SIGNATURES = {
     "mx_psola_synth": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "mx_psola_render": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _vp]),
     "mx_psola_render_dev": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _vp]),
+    "mx_psola_plan_formant": (_i, [_i64, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, C.POINTER(_vp),
+                                   C.POINTER(_i64), C.POINTER(_i64)]),
+    "mx_psola_synth_formant_dev": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "mx_psola_synth_formant": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "mx_psola_render_formant": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, _vp]),
+    "mx_psola_render_formant_dev": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, _vp]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

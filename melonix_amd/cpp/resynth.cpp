@@ -105,27 +105,37 @@ bool Resynth::exportWavPV(const std::string &fileName, const std::vector<Marker>
 
 std::vector<float> Resynth::renderPSOLA(const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
                                         const mx_psola_params *params) const {
+  return renderPSOLA(markers, track, hop, std::vector<mx_formant_point>(), params);  // (no points: mx_psola_render itself)
+}
+
+bool Resynth::exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track,
+                             int hop, const mx_psola_params *params) const {
+  return exportWavPSOLA(fileName, markers, track, hop, std::vector<mx_formant_point>(), params);
+}
+
+std::vector<float> Resynth::renderPSOLA(const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
+                                        const std::vector<mx_formant_point> &formant, const mx_psola_params *params) const {
   std::vector<float> pcm;
   if (!ok()) return pcm;
   const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
   const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
   if (m <= 0) return pcm;
   pcm.resize((size_t)m);
-  if (mx_psola_render(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(), pcm.data(),
-                      nullptr) != MX_OK)
+  if (mx_psola_render_formant(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(),
+                              formant.data(), (int)formant.size(), pcm.data(), nullptr) != MX_OK)
     pcm.clear();
   return pcm;
 }
 
 bool Resynth::exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track,
-                             int hop, const mx_psola_params *params) const {
+                             int hop, const std::vector<mx_formant_point> &formant, const mx_psola_params *params) const {
   if (!ok()) return false;
   const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
   const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
   if (m <= 0) return false;
   std::vector<int16_t> pcm16((size_t)m);
-  if (mx_psola_render(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(), nullptr,
-                      pcm16.data()) != MX_OK)
+  if (mx_psola_render_formant(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(),
+                              formant.data(), (int)formant.size(), nullptr, pcm16.data()) != MX_OK)
     return false;
   saveWav(fileName, pcm16, sampleRate);
   return true;

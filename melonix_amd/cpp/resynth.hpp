@@ -28,6 +28,7 @@ struct mx_ctx;
 struct mx_audio;
 struct mx_f0;
 struct mx_psola_params;
+struct mx_formant_point;
 
 namespace melonix {
 
@@ -61,6 +62,13 @@ public:
                                  const mx_psola_params *params = nullptr) const;
   bool exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
                       const mx_psola_params *params = nullptr) const;
+  // ... and with the envelope moved on purpose (mx_psola_render_formant): `formant` holds {source sample, semitones} points,
+  // samples strictly increasing, linear between them and constant outside; the note still follows the markers alone.  A
+  // per-note value is two points, at the note's start_sample and end_sample.  No points: the calls above.
+  std::vector<float> renderPSOLA(const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
+                                 const std::vector<mx_formant_point> &formant, const mx_psola_params *params = nullptr) const;
+  bool exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
+                      const std::vector<mx_formant_point> &formant, const mx_psola_params *params = nullptr) const;
   // what App::playback appends to an empty restWav when asked for `need` samples at warped time `cursor`
   std::vector<float> refill(const std::vector<Marker> &markers, double cursor, std::size_t need,
                             double *cursorEnd = nullptr) const;

@@ -183,16 +183,21 @@ F0DecodeScratch f0_decode_scratch(int64_t count, int64_t chunk);
 hipError_t launch_f0_decode(const F0DecodeArgs &a, hipStream_t s);
 // Build-defined PSOLA overlap-add (psola_kernels.hip; records: psola_plan.cpp, definition: include/melonix_amd.h).  The
 // records are not validated on the device: bad ones give wrong samples, no access outside the padded audio or the outputs.
-struct PsolaArgs {
+// Rec: mx_psola_grain, or mx_psola_fgrain (the formant shift: the same walk, another source address per sample).
+template <class Rec>
+struct PsolaArgsT {
   const float *audio;  // padded image (zeros in the pads)
   int64_t n;
-  const mx_psola_grain *grains;
+  const Rec *grains;
   int64_t ngrains;
   int64_t nsamples;
   float *pcm_f32;    // may be null
   int16_t *pcm_i16;  // may be null
 };
+using PsolaArgs = PsolaArgsT<mx_psola_grain>;
+using PsolaFormantArgs = PsolaArgsT<mx_psola_fgrain>;
 hipError_t launch_psola(const PsolaArgs &a, hipStream_t s);
+hipError_t launch_psola(const PsolaFormantArgs &a, hipStream_t s);
 // spec-cache.cpp:77-96 colormap: nbins_total magnitudes -> 3*nbins_total bytes (both device).
 hipError_t launch_colormap(const float *mags, uint8_t *rgb, int64_t nbins_total, float k, hipStream_t s);
 

@@ -12,6 +12,10 @@
 // The device form cannot validate its records: every scan stays inside [0, ngrains), the source index is clamped into the
 // padded buffer, and nothing is stored outside [0, nsamples) — bad records give wrong samples, never a fault.
 //
+// Two instantiations of the one tile walk, on the record: mx_psola_grain reads the source at i + src_off with the record's
+// fraction; mx_psola_fgrain (the formant shift) at the Q16 position src_idx.src_q + step (i - centre).  Only psola_source —
+// the source index and fraction of a sample — differs; search, staging, order, sums and stores are written once.
+//
 // Built with -ffp-contract=off: x = (1 - f) * a0 + f * a1 is the resampler's form (resynth_kernels.hip), and S += w * x rounds
 // the product before the sum, as the f64 restatement orders it.
 #include <hip/hip_runtime.h>
@@ -32,17 +36,34 @@ constexpr int kPsolaChunk = kPsolaThreads;  // one record per thread and chunk: 
 // a grain's samples lie within kPsolaReach of `centre`, and centre <= centre + centre_frac < centre + 1
 constexpr int kPsolaKeyReach = kPsolaReach + 1;
 
-static_assert(sizeof(mx_psola_grain) == 32, "two 16-byte LDS reads per record");
+static_assert(sizeof(mx_psola_grain) == 32 && sizeof(mx_psola_fgrain) == 32, "two 16-byte LDS reads per record");
 
-__device__ __forceinline__ double psola_key(const mx_psola_grain *g) { return (double)g->centre + (double)g->centre_frac; }
+template <class Rec>
+__device__ __forceinline__ double psola_key(const Rec *g) {
+  return (double)g->centre + (double)g->centre_frac;
+}
+
+// where output sample i of a grain reads the source: index (not yet clamped) and fraction
+__device__ __forceinline__ void psola_source(const mx_psola_grain &g, int i, int64_t &idx, float &f) {
+  idx = (int64_t)i + (int64_t)g.src_off;
+  f = g.src_frac;
+}
+// pos = (src_idx << 16) + src_q + step (i - centre): the low part stays under 2^30 for records that keep the precondition
+// (src_q < 2^16, step <= 2^17, |i - centre| <= 2049); unsigned, so that records that break it wrap instead of overflowing
+__device__ __forceinline__ void psola_source(const mx_psola_fgrain &g, int i, int64_t &idx, float &f) {
+  const unsigned t = g.src_q + g.step * ((unsigned)i - (unsigned)g.centre);
+  idx = (int64_t)g.src_idx + (int64_t)((int)t >> 16);
+  f = (float)(t & 65535u) * (1.f / 65536.f);
+}
 
 __device__ __forceinline__ int16_t psola_pcm16(float v) {
   const float c = v < -1.f ? -1.f : (1.f < v ? 1.f : v);
   return (int16_t)((double)c * 32767.);
 }
 
-__global__ __launch_bounds__(kPsolaThreads) void psola_kernel(const PsolaArgs a) {
-  __shared__ __attribute__((aligned(16))) mx_psola_grain recs[kPsolaChunk];
+template <class Rec>
+__global__ __launch_bounds__(kPsolaThreads) void psola_kernel(const PsolaArgsT<Rec> a) {
+  __shared__ __attribute__((aligned(16))) Rec recs[kPsolaChunk];
   __shared__ int wave_count[kPsolaThreads / 64];
   __shared__ int past_tile;
   const int tid = threadIdx.x;
@@ -78,14 +99,14 @@ __global__ __launch_bounds__(kPsolaThreads) void psola_kernel(const PsolaArgs a)
     const int64_t rest = a.ngrains - base;
     const int cnt = rest < kPsolaChunk ? (int)rest : kPsolaChunk;
     if (tid < cnt) {
-      const mx_psola_grain g = a.grains[base + tid];
+      const Rec g = a.grains[base + tid];
       recs[tid] = g;
       if (psola_key(&g) > key_hi) past_tile = 1;
     }
     __syncthreads();
     const int last = past_tile;
     for (int j = 0; j < cnt; ++j) {
-      const mx_psola_grain g = recs[j];  // (the same address in every lane: a broadcast)
+      const Rec g = recs[j];  // (the same address in every lane: a broadcast)
 #pragma unroll
       for (int q = 0; q < kPsolaPer; ++q) {
         const int i = (int)(i0 + (unsigned)(q * kPsolaThreads));
@@ -93,9 +114,11 @@ __global__ __launch_bounds__(kPsolaThreads) void psola_kernel(const PsolaArgs a)
         const float u = ((float)(int)((unsigned)i - (unsigned)g.centre) - g.centre_frac) * g.inv_half;
         if (!(fabsf(u) < 1.f)) continue;
         const float w = 0.5f + 0.5f * cospif(u);
-        int64_t idx = (int64_t)i + (int64_t)g.src_off;
+        int64_t idx;
+        float f;
+        psola_source(g, i, idx, f);
         idx = idx < -(int64_t)MX_AUDIO_PAD ? -(int64_t)MX_AUDIO_PAD : (idx > idx_max ? idx_max : idx);
-        const float x = (1.f - g.src_frac) * src[idx] + g.src_frac * src[idx + 1];
+        const float x = (1.f - f) * src[idx] + f * src[idx + 1];
         S[q] += w * x;
         W[q] += w;
       }
@@ -114,14 +137,18 @@ __global__ __launch_bounds__(kPsolaThreads) void psola_kernel(const PsolaArgs a)
   }
 }
 
-}  // namespace
-
-hipError_t launch_psola(const PsolaArgs &a, hipStream_t s) {
+template <class Rec>
+hipError_t launch(const PsolaArgsT<Rec> &a, hipStream_t s) {
   if (a.nsamples <= 0) return hipSuccess;
   if (a.nsamples > 0x7fffffffLL || a.ngrains < 0 || a.n < 0) return hipErrorInvalidValue;
   const int64_t blocks = (a.nsamples + kPsolaTile - 1) / kPsolaTile;
-  hipLaunchKernelGGL(psola_kernel, dim3((unsigned)blocks), dim3(kPsolaThreads), 0, s, a);
+  hipLaunchKernelGGL(psola_kernel<Rec>, dim3((unsigned)blocks), dim3(kPsolaThreads), 0, s, a);
   return hipGetLastError();
 }
+
+}  // namespace
+
+hipError_t launch_psola(const PsolaArgs &a, hipStream_t s) { return launch(a, s); }
+hipError_t launch_psola(const PsolaFormantArgs &a, hipStream_t s) { return launch(a, s); }
 
 }  // namespace mx

@@ -1,0 +1,39 @@
+"""The melonix::Resynth::renderPSOLA / exportWavPSOLA overloads that take formant points (the C++ facade of the formant shift)
+from a compiled program: the Python path's bytes, and the WAV file saveWav makes of them."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import SR
+from test_gpu_psola import vowel
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_psola_formant_facade_matches_python(gpu_ctx, mxlib, tmp_path):
+    lib = os.path.join(ROOT, "melonix_amd", "lib")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "melonix_amd", "cpp"), "NO_GL=1"])
+    exe = str(tmp_path / "psola_formant_driver")
+    subprocess.check_call(["g++", "-std=c++20", "-O2", "-DMELONIX_AMD_NO_GL", "-I", os.path.join(ROOT, "melonix_amd", "cpp"), "-I",
+                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "psola_formant_driver.cpp"),
+                           "-o", exe, "-L", lib, "-lmelonix_facade", "-lmelonix_amd", f"-Wl,-rpath,{lib}", "-lpthread"])
+    w = vowel(0.75)
+    src, out, wav = tmp_path / "in.f32", tmp_path / "out.f32", tmp_path / "out.wav"
+    w.astype("<f4").tofile(src)
+    r = subprocess.run([exe, str(src), str(SR), "4", "-3", "5", str(out), str(wav)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    a = gpu_ctx.upload(w)
+    try:
+        tr = gpu_ctx.f0_track(a, SR, 256)
+        mk = [(1, 0, 0.0, 4.0), (len(w) - 1, 0, 0.0, 4.0)]
+        f32, i16 = gpu_ctx.psola_render_formant(a, SR, 256, tr, mk, [(0, -3.0), (len(w) - 1, 5.0)])
+    finally:
+        a.free()
+    assert np.fromfile(out, dtype="<f4").tobytes() == f32.tobytes()
+    ref_wav = tmp_path / "ref.wav"
+    mxlib.save_wav(str(ref_wav), i16, SR)
+    assert wav.read_bytes() == ref_wav.read_bytes() and len(i16) > 30000
