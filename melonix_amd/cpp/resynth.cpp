@@ -81,24 +81,37 @@ std::vector<float> Resynth::phaseVocoder(double semitones) const {
   return pcm;
 }
 
-std::vector<float> Resynth::renderPV(const std::vector<Marker> &markers) const {
-  std::vector<float> pcm;
-  if (!ok()) return pcm;
-  const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
-  const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
-  if (m <= 0) return pcm;
-  pcm.resize((size_t)m);
-  if (mx_pv_render(ctx, audio, sampleRate, mk, (int)markers.size(), pcm.data(), nullptr) != MX_OK) pcm.clear();
-  return pcm;
+// mx_psola_render_formant over a track and a curve, as rendered() calls it
+static auto psolaCall(mx_ctx *ctx, const mx_audio *audio, int sampleRate, const std::vector<mx_f0> &track, int hop,
+                      const std::vector<mx_formant_point> &formant, const mx_psola_params *params) {
+  return [=, &track, &formant](const mx_marker *mk, int n, float *f, int16_t *i) {
+    return mx_psola_render_formant(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, n, formant.data(),
+                                   (int)formant.size(), f, i);
+  };
 }
 
-bool Resynth::exportWavPV(const std::string &fileName, const std::vector<Marker> &markers) const {
+// A marker-driven render (phase vocoder, PSOLA): the warped length, buffers of that length, and one C call
+// (mx_marker *, count, f32 | null, int16 | null) -> status.  False: not ok(), nothing to render, or the call failed.
+template <class Call>
+bool Resynth::rendered(const std::vector<Marker> &markers, std::vector<float> *f32, std::vector<int16_t> *i16, Call call) const {
   if (!ok()) return false;
   const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
   const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
   if (m <= 0) return false;
-  std::vector<int16_t> pcm16((size_t)m);
-  if (mx_pv_render(ctx, audio, sampleRate, mk, (int)markers.size(), nullptr, pcm16.data()) != MX_OK) return false;
+  if (f32) f32->resize((size_t)m);
+  if (i16) i16->resize((size_t)m);
+  return call(mk, (int)markers.size(), f32 ? f32->data() : nullptr, i16 ? i16->data() : nullptr) == MX_OK;
+}
+
+std::vector<float> Resynth::renderPV(const std::vector<Marker> &markers) const {
+  std::vector<float> pcm;
+  if (!rendered(markers, &pcm, nullptr, [&](auto... a) { return mx_pv_render(ctx, audio, sampleRate, a...); })) pcm.clear();
+  return pcm;
+}
+
+bool Resynth::exportWavPV(const std::string &fileName, const std::vector<Marker> &markers) const {
+  std::vector<int16_t> pcm16;
+  if (!rendered(markers, nullptr, &pcm16, [&](auto... a) { return mx_pv_render(ctx, audio, sampleRate, a...); })) return false;
   saveWav(fileName, pcm16, sampleRate);
   return true;
 }
@@ -116,27 +129,14 @@ bool Resynth::exportWavPSOLA(const std::string &fileName, const std::vector<Mark
 std::vector<float> Resynth::renderPSOLA(const std::vector<Marker> &markers, const std::vector<mx_f0> &track, int hop,
                                         const std::vector<mx_formant_point> &formant, const mx_psola_params *params) const {
   std::vector<float> pcm;
-  if (!ok()) return pcm;
-  const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
-  const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
-  if (m <= 0) return pcm;
-  pcm.resize((size_t)m);
-  if (mx_psola_render_formant(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(),
-                              formant.data(), (int)formant.size(), pcm.data(), nullptr) != MX_OK)
-    pcm.clear();
+  if (!rendered(markers, &pcm, nullptr, psolaCall(ctx, audio, sampleRate, track, hop, formant, params))) pcm.clear();
   return pcm;
 }
 
 bool Resynth::exportWavPSOLA(const std::string &fileName, const std::vector<Marker> &markers, const std::vector<mx_f0> &track,
                              int hop, const std::vector<mx_formant_point> &formant, const mx_psola_params *params) const {
-  if (!ok()) return false;
-  const mx_marker *mk = reinterpret_cast<const mx_marker *>(markers.data());
-  const int64_t m = mx_pv_render_length((int64_t)nsrc, sampleRate, mk, (int)markers.size());
-  if (m <= 0) return false;
-  std::vector<int16_t> pcm16((size_t)m);
-  if (mx_psola_render_formant(ctx, audio, sampleRate, hop, track.data(), (int64_t)track.size(), params, mk, (int)markers.size(),
-                              formant.data(), (int)formant.size(), nullptr, pcm16.data()) != MX_OK)
-    return false;
+  std::vector<int16_t> pcm16;
+  if (!rendered(markers, nullptr, &pcm16, psolaCall(ctx, audio, sampleRate, track, hop, formant, params))) return false;
   saveWav(fileName, pcm16, sampleRate);
   return true;
 }

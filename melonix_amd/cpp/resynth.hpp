@@ -82,6 +82,9 @@ private:
   std::vector<float> firsts;  // first sample of every grain: all the export loop reads of the audio (app.cpp:323-328)
   bool run(const std::vector<Marker> &markers, std::vector<float> *f32, std::vector<int16_t> *i16, double cursor0 = 0.,
            int64_t need = -1, double *cursorEnd = nullptr) const;
+  // the marker-driven renders (resynth.cpp): the warped length, buffers of it, one C call
+  template <class Call>
+  bool rendered(const std::vector<Marker> &markers, std::vector<float> *f32, std::vector<int16_t> *i16, Call call) const;
 };
 
 }  // namespace melonix

@@ -19,13 +19,14 @@ int invalid(std::string &err, const char *fmt, long long a = 0, long long b = 0)
   return MX_ERR_INVALID;
 }
 
-// The plan: arguments checked, then the marks, one record per synthesis mark.  mark_pos (may be null) receives a_{m(k)} for
-// every record: what the formant form needs of the analysis marks beyond the record itself.
+// The plan: arguments checked, then the marks, one record per synthesis mark.  The window fields are the same for both record
+// kinds; source(record, a_m, s, m) — the record, its analysis mark, its synthesis mark and the mark's index — then fills in
+// where the grain reads the source.
+template <class Rec, class Source>
 int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
-               const mx_marker *markers, int nmarkers, std::vector<mx_psola_grain> &grains, std::vector<double> *mark_pos,
-               int64_t &nsamples, std::string &err) {
+               const mx_marker *markers, int nmarkers, std::vector<Rec> &grains, int64_t &nsamples, std::string &err,
+               Source source) {
   grains.clear();
-  if (mark_pos) mark_pos->clear();
   nsamples = 0;
   if (n < 0 || n > (int64_t)INT32_MAX - 2 * MX_AUDIO_PAD) return invalid(err, "%lld samples: outside [0, INT32_MAX - 2*MX_AUDIO_PAD]", n);
   if (sampleRate <= 0) return invalid(err, "sample rate %lld", sampleRate);
@@ -86,16 +87,10 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
       r = std::exp2((double)tm.time2pitchbend(t, hint_b) / 12.0);
       r = !(r >= 0.5) ? 0.5 : (r > 2. ? 2. : r);
     }
-    mx_psola_grain g{};
+    Rec g{};
     g.out_lo = (int32_t)std::max(0., std::floor(s - H) + 1.);
     g.out_hi = (int32_t)std::min((double)L, std::ceil(s + H));
-    const double d = a[m] - s, dfl = std::floor(d), cfl = std::floor(s);
-    g.src_off = (int32_t)dfl;
-    g.src_frac = (float)(d - dfl);
-    if (g.src_frac >= 1.f) {
-      g.src_off += 1;
-      g.src_frac = 0.f;
-    }
+    const double cfl = std::floor(s);
     g.centre = (int32_t)cfl;
     g.centre_frac = (float)(s - cfl);
     if (g.centre_frac >= 1.f) {
@@ -103,28 +98,58 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
       g.centre_frac = 0.f;
     }
     g.inv_half = (float)(1. / H);
-    g.mark = (int32_t)m;
+    source(g, a[m], s, (int32_t)m);
     grains.push_back(g);
-    if (mark_pos) mark_pos->push_back(a[m]);
     s = s + H / r;
   }
   return MX_OK;
 }
 
-// the checks the two record kinds share: `prev` carries the last key
+// The record's own fields, beyond the window ...
+int check_fields(const mx_psola_grain &r, int64_t k, std::string &err) {
+  if (!(r.src_frac >= 0.f && r.src_frac < 1.f)) return invalid(err, "grain %lld: a fraction outside [0, 1)", k);
+  return MX_OK;
+}
+int check_fields(const mx_psola_fgrain &r, int64_t k, std::string &err) {
+  if (r.step < kPsolaStepMin || r.step > kPsolaStepMax) return invalid(err, "grain %lld: step outside [32768, 131072]", k);
+  if (r.src_q >= kPsolaStepOne) return invalid(err, "grain %lld: src_q is not below 65536", k);
+  return MX_OK;
+}
+
+// ... and the lowest and highest source index its (non-empty) window reads: psola_kernels.hip's psola_source, which takes
+// the samples at idx and idx + 1, at the window's first and last output
+void source_span(const mx_psola_grain &r, int64_t &lo, int64_t &hi) {
+  lo = (int64_t)r.out_lo + r.src_off;
+  hi = (int64_t)r.out_hi + r.src_off;
+}
+// (pos rises with i)
+void source_span(const mx_psola_fgrain &r, int64_t &lo, int64_t &hi) {
+  auto idx = [&](int64_t i) { return ((int64_t)r.src_idx * 65536 + (int64_t)r.src_q + (int64_t)r.step * (i - (int64_t)r.centre)) >> 16; };
+  lo = idx(r.out_lo);
+  hi = idx((int64_t)r.out_hi - 1) + 1;
+}
+
 template <class Rec>
-int check_window(const Rec &r, int64_t k, int64_t nsamples, double &prev, std::string &err) {
-  if (!(r.centre_frac >= 0.f && r.centre_frac < 1.f)) return invalid(err, "grain %lld: a fraction outside [0, 1)", k);
-  const double key = (double)r.centre + (double)r.centre_frac;
-  if (!(key > prev)) return invalid(err, "grain %lld: centre + centre_frac does not increase", k);
-  prev = key;
-  if (r.out_lo < 0 || r.out_lo > r.out_hi || (int64_t)r.out_hi > nsamples)
-    return invalid(err, "grain %lld: window outside the %lld output samples", k, nsamples);
-  if (!std::isfinite(r.inv_half) || !(r.inv_half >= 1.f / (float)MX_PSOLA_MAX_HALF))
-    return invalid(err, "grain %lld: inv_half is not finite or below 1/%lld", k, MX_PSOLA_MAX_HALF);
-  if (r.out_lo == r.out_hi) return MX_OK;  // (no output reads it)
-  if ((int64_t)r.out_lo < (int64_t)r.centre - kPsolaReach || (int64_t)r.out_hi - 1 > (int64_t)r.centre + kPsolaReach)
-    return invalid(err, "grain %lld: window beyond centre +- %lld", k, kPsolaReach);
+int check_grains(const Rec *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err) {
+  double prev = -HUGE_VAL;  // the last key
+  for (int64_t k = 0; k < ngrains; ++k) {
+    const Rec &r = g[k];
+    if (const int rc = check_fields(r, k, err)) return rc;
+    if (!(r.centre_frac >= 0.f && r.centre_frac < 1.f)) return invalid(err, "grain %lld: a fraction outside [0, 1)", k);
+    const double key = (double)r.centre + (double)r.centre_frac;
+    if (!(key > prev)) return invalid(err, "grain %lld: centre + centre_frac does not increase", k);
+    prev = key;
+    if (r.out_lo < 0 || r.out_lo > r.out_hi || (int64_t)r.out_hi > nsamples)
+      return invalid(err, "grain %lld: window outside the %lld output samples", k, nsamples);
+    if (!std::isfinite(r.inv_half) || !(r.inv_half >= 1.f / (float)MX_PSOLA_MAX_HALF))
+      return invalid(err, "grain %lld: inv_half is not finite or below 1/%lld", k, MX_PSOLA_MAX_HALF);
+    if (r.out_lo == r.out_hi) continue;  // (no output reads it)
+    if ((int64_t)r.out_lo < (int64_t)r.centre - kPsolaReach || (int64_t)r.out_hi - 1 > (int64_t)r.centre + kPsolaReach)
+      return invalid(err, "grain %lld: window beyond centre +- %lld", k, kPsolaReach);
+    int64_t lo, hi;
+    source_span(r, lo, hi);
+    if (lo < -(int64_t)MX_AUDIO_PAD || hi > n + (int64_t)MX_AUDIO_PAD - 1) return invalid(err, "grain %lld: reads the source outside its pads", k);
+  }
   return MX_OK;
 }
 
@@ -133,12 +158,22 @@ int check_window(const Rec &r, int64_t k, int64_t nsamples, double &prev, std::s
 int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
                      const mx_marker *markers, int nmarkers, std::vector<mx_psola_grain> &grains, int64_t &nsamples,
                      std::string &err) {
-  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, grains, nullptr, nsamples, err);
+  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, grains, nsamples, err,
+                    [](mx_psola_grain &g, double am, double s, int32_t m) {
+                      const double d = am - s, dfl = std::floor(d);
+                      g.src_off = (int32_t)dfl;
+                      g.src_frac = (float)(d - dfl);
+                      if (g.src_frac >= 1.f) {
+                        g.src_off += 1;
+                        g.src_frac = 0.f;
+                      }
+                      g.mark = m;
+                    });
 }
 
-int build_psola_fplan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
-                      const mx_marker *markers, int nmarkers, const mx_formant_point *points, int npoints,
-                      std::vector<mx_psola_fgrain> &fgrains, int64_t &nsamples, std::string &err) {
+int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
+                     const mx_marker *markers, int nmarkers, const mx_formant_point *points, int npoints,
+                     std::vector<mx_psola_fgrain> &fgrains, int64_t &nsamples, std::string &err) {
   fgrains.clear();
   nsamples = 0;
   if (npoints < 0 || (npoints > 0 && !points)) return invalid(err, "bad formant curve: %lld points", npoints);
@@ -146,10 +181,6 @@ int build_psola_fplan(int64_t n, int sampleRate, int hop, const mx_f0 *track, in
     if (!std::isfinite(points[j].semitones)) return invalid(err, "formant point %lld: semitones not finite", j);
     if (j > 0 && !(points[j].sample > points[j - 1].sample)) return invalid(err, "formant point %lld: samples do not increase", j);
   }
-  std::vector<mx_psola_grain> grains;
-  std::vector<double> mark_pos;
-  if (const int rc = plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, grains, &mark_pos, nsamples, err)) return rc;
-
   // F(x): piecewise linear between the points, constant outside them
   auto curve = [&](double x) {
     if (npoints == 0) return 0.;
@@ -161,56 +192,23 @@ int build_psola_fplan(int64_t n, int sampleRate, int hop, const mx_f0 *track, in
     return (double)q0.semitones +
            (x - (double)q0.sample) * ((double)q1.semitones - (double)q0.semitones) / ((double)q1.sample - (double)q0.sample);
   };
-
-  fgrains.reserve(grains.size());
-  for (size_t k = 0; k < grains.size(); ++k) {
-    const mx_psola_grain &g = grains[k];
-    const double am = mark_pos[k];
-    double phi = std::exp2(curve(am) / 12.0);
-    phi = !(phi >= 0.5) ? 0.5 : (phi > 2. ? 2. : phi);
-    mx_psola_fgrain f{};
-    f.out_lo = g.out_lo;
-    f.out_hi = g.out_hi;
-    f.centre = g.centre;
-    f.centre_frac = g.centre_frac;
-    f.inv_half = g.inv_half;
-    f.step = (uint32_t)(int)std::floor(phi * 65536.0 + 0.5);
-    const double p0 = am - ((double)f.step / 65536.0) * (double)g.centre_frac;
-    const int64_t q = (int64_t)std::floor(p0 * 65536.0 + 0.5);
-    f.src_idx = (int32_t)(q >> 16);
-    f.src_q = (uint32_t)(q & 65535);
-    fgrains.push_back(f);
-  }
-  return MX_OK;
+  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, fgrains, nsamples, err,
+                    [&](mx_psola_fgrain &f, double am, double, int32_t) {
+                      double phi = std::exp2(curve(am) / 12.0);
+                      phi = !(phi >= 0.5) ? 0.5 : (phi > 2. ? 2. : phi);
+                      f.step = (uint32_t)(int)std::floor(phi * 65536.0 + 0.5);
+                      const double p0 = am - ((double)f.step / 65536.0) * (double)f.centre_frac;
+                      const int64_t q = (int64_t)std::floor(p0 * 65536.0 + 0.5);
+                      f.src_idx = (int32_t)(q >> 16);
+                      f.src_q = (uint32_t)(q & 65535);
+                    });
 }
 
 int check_psola_grains(const mx_psola_grain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err) {
-  double prev = -HUGE_VAL;
-  for (int64_t k = 0; k < ngrains; ++k) {
-    const mx_psola_grain &r = g[k];
-    if (!(r.src_frac >= 0.f && r.src_frac < 1.f)) return invalid(err, "grain %lld: a fraction outside [0, 1)", k);
-    if (const int rc = check_window(r, k, nsamples, prev, err)) return rc;
-    if (r.out_lo == r.out_hi) continue;
-    if ((int64_t)r.out_lo + r.src_off < -(int64_t)MX_AUDIO_PAD || (int64_t)r.out_hi + r.src_off > n + (int64_t)MX_AUDIO_PAD - 1)
-      return invalid(err, "grain %lld: reads the source outside its pads", k);
-  }
-  return MX_OK;
+  return check_grains(g, ngrains, nsamples, n, err);
 }
-
-int check_psola_fgrains(const mx_psola_fgrain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err) {
-  double prev = -HUGE_VAL;
-  for (int64_t k = 0; k < ngrains; ++k) {
-    const mx_psola_fgrain &r = g[k];
-    if (r.step < kPsolaStepMin || r.step > kPsolaStepMax) return invalid(err, "grain %lld: step outside [32768, 131072]", k);
-    if (r.src_q >= kPsolaStepOne) return invalid(err, "grain %lld: src_q is not below 65536", k);
-    if (const int rc = check_window(r, k, nsamples, prev, err)) return rc;
-    if (r.out_lo == r.out_hi) continue;
-    // pos rises with i: the window's first and last outputs read the lowest and the highest source index
-    auto idx = [&](int64_t i) { return ((int64_t)r.src_idx * 65536 + (int64_t)r.src_q + (int64_t)r.step * (i - (int64_t)r.centre)) >> 16; };
-    if (idx(r.out_lo) < -(int64_t)MX_AUDIO_PAD || idx((int64_t)r.out_hi - 1) + 1 > n + (int64_t)MX_AUDIO_PAD - 1)
-      return invalid(err, "grain %lld: reads the source outside its pads", k);
-  }
-  return MX_OK;
+int check_psola_grains(const mx_psola_fgrain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err) {
+  return check_grains(g, ngrains, nsamples, n, err);
 }
 
 }  // namespace mx

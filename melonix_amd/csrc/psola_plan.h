@@ -17,19 +17,20 @@ constexpr int kPsolaReach = MX_PSOLA_MAX_HALF + 1;
 // the Q16 source step of a formant record: an octave either way
 constexpr uint32_t kPsolaStepOne = 65536, kPsolaStepMin = kPsolaStepOne / 2, kPsolaStepMax = kPsolaStepOne * 2;
 
-// Arguments checked (the f0 family's conventions), then the plan.  MX_OK, or MX_ERR_INVALID with `err` set.
+// Arguments checked (the f0 family's conventions), then the plan, one record per synthesis mark.  MX_OK, or MX_ERR_INVALID
+// with `err` set.
 int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
                      const mx_marker *markers, int nmarkers, std::vector<mx_psola_grain> &grains, int64_t &nsamples,
                      std::string &err);
-// The same plan with the formant curve (definition: "Independent formant shift"): the plain plan's records, each with the Q16
+// The same plan with the formant curve (definition: "Independent formant shift"): the same marks, each record with the Q16
 // step of its analysis mark and the source position of its centre.  The curve is checked first.
-int build_psola_fplan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
-                      const mx_marker *markers, int nmarkers, const mx_formant_point *points, int npoints,
-                      std::vector<mx_psola_fgrain> &fgrains, int64_t &nsamples, std::string &err);
+int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
+                     const mx_marker *markers, int nmarkers, const mx_formant_point *points, int npoints,
+                     std::vector<mx_psola_fgrain> &fgrains, int64_t &nsamples, std::string &err);
 
-// The precondition of mx_psola_synth_dev on `ngrains` records for an audio of n samples.  MX_OK, or MX_ERR_INVALID with `err`.
+// The precondition of mx_psola_synth_dev / mx_psola_synth_formant_dev on `ngrains` records for an audio of n samples.  MX_OK,
+// or MX_ERR_INVALID with `err`.
 int check_psola_grains(const mx_psola_grain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err);
-// ... and of mx_psola_synth_formant_dev.
-int check_psola_fgrains(const mx_psola_fgrain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err);
+int check_psola_grains(const mx_psola_fgrain *g, int64_t ngrains, int64_t nsamples, int64_t n, std::string &err);
 
 }  // namespace mx

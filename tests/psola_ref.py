@@ -1,6 +1,6 @@
 """The PSOLA renderer's definition (include/melonix_amd.h, "Formant-preserving PSOLA rendering") restated in binary64:
-plan() makes the grain records from an f0 track and the markers, render() adds grains up.  render() takes RECORDS, so the GPU
-is compared on the plan it was actually given.  The marker maps are the editor's piecewise-linear ones (the same the
+plan() makes the grain records from an f0 track and the markers, render() adds grains up.  render() takes RECORDS — plain ones,
+or the formant shift's (tests/psola_formant_ref.py) —, so the GPU is compared on the plan it was actually given.  The marker maps are the editor's piecewise-linear ones (the same the
 marker-driven phase vocoder follows), written out here once more so that this file depends on nothing but numpy and the C
 library's exp2 (the product's host code calls std::exp2; numpy's own differs in the last bit)."""
 import ctypes
@@ -89,15 +89,12 @@ def voicing(track, params):
     return v, per.astype(np.float64)
 
 
-def plan(n, sr, hop, track, markers, **params):
-    """-> (GRAIN_DTYPE records, nsamples)."""
+def marks(n, hop, track, **params):
+    """The analysis marks of a file of n > 0 samples -> (a_m, the period at a_m, voiced at a_m), a list each."""
     p = dict(DEFAULTS)
     p.update(params)
     count = (n + hop - 1) // hop
     assert len(track) == count
-    L = render_length(n, sr, markers)
-    if n == 0 or L == 0:
-        return np.zeros(0, GRAIN_DTYPE), L
     U = float(np.float32(p["unvoiced_period"]))
     voiced, period = voicing(track, p)
 
@@ -115,6 +112,16 @@ def plan(n, sr, hop, track, markers, **params):
         per.append(pm)
         vo.append(v)
         am = am + pm
+    return a, per, vo
+
+
+def plan(n, sr, hop, track, markers, **params):
+    """-> (GRAIN_DTYPE records, nsamples)."""
+    assert len(track) == (n + hop - 1) // hop
+    L = render_length(n, sr, markers)
+    if n == 0 or L == 0:
+        return np.zeros(0, GRAIN_DTYPE), L
+    a, per, vo = marks(n, hop, track, **params)
     a_arr = np.array(a, dtype=np.float64)
 
     tm = TimeMap(markers, sr, n)
@@ -145,8 +152,19 @@ def plan(n, sr, hop, track, markers, **params):
     return np.array(out, dtype=GRAIN_DTYPE), L
 
 
+def _source(g, i):
+    """Where outputs i of record g read the source -> (index, fraction).  A plain record: i + src_off and src_frac; a formant
+    record: the Q16 position src_idx.src_q + step (i - centre) in integer arithmetic (the Q16 step is the definition: nothing
+    about a position is rounded here or on the device)."""
+    if "step" not in g.dtype.names:
+        return i + int(g["src_off"]), float(g["src_frac"])
+    pos = (int(g["src_idx"]) << 16) + int(g["src_q"]) + int(g["step"]) * (i - int(g["centre"]))
+    return pos >> 16, (pos & 65535).astype(np.float64) / 65536.0
+
+
 def render(wav, grains, nsamples):
-    """-> f64[nsamples]: the overlap-add of the records over `wav` (zeros outside the file), sums in ascending k."""
+    """-> f64[nsamples]: the overlap-add of the records (either kind) over `wav` (zeros outside the file), sums in ascending
+    k, interpolation and sums in binary64."""
     n = len(wav)
     x = np.zeros(n + 2 * PAD, dtype=np.float64)
     x[PAD:PAD + n] = wav
@@ -161,8 +179,8 @@ def render(wav, grains, nsamples):
         keep = np.abs(u) < 1.0
         i, u = i[keep], u[keep]
         w = 0.5 + 0.5 * np.cos(np.pi * u)
-        j = i + int(g["src_off"]) + PAD
-        f = float(g["src_frac"])
+        j, f = _source(g, i)
+        j = j + PAD
         S[i] += w * ((1.0 - f) * x[j] + f * x[j + 1])
         W[i] += w
     return np.where(W > 0, S / np.maximum(W, 0.25), 0.0)

@@ -51,6 +51,20 @@ def check(g32, g16, ref, label):
     assert err <= tol and lsb <= 1, label
 
 
+def _sfx(g):
+    """The record kind of g as the entry points spell it: "" for plain records, "_formant" for the formant shift's (this file's
+    helpers below serve tests/test_gpu_psola_formant.py as well)."""
+    return "_formant" if "step" in g.dtype.names else ""
+
+
+def _synth(gpu_ctx, g):
+    return getattr(gpu_ctx, "psola_synth" + _sfx(g))
+
+
+def _synth_dev(gpu_ctx, g):
+    return getattr(gpu_ctx, f"psola_synth{_sfx(g)}_dev")
+
+
 @pytest.fixture(scope="module")
 def takes(gpu_ctx):
     """name -> (samples, audio handle, f0 track): the vowel, white noise, and the two one after the other."""
@@ -190,6 +204,24 @@ def _shape_cases():
     return out
 
 
+def _run_shape(gpu_ctx, hip, w, g, L, label):  # noqa: F811
+    """The device form on records g (either kind) between guard bands, twice, against the reference; and the host form on the
+    same records (its record check passes them): the same bytes."""
+    a = gpu_ctx.upload(w)
+    d_g = _to_device(hip, g)
+    try:
+        def call(p):
+            _synth_dev(gpu_ctx, g)(a, d_g.value, len(g), L, p[0], p[1])
+        f32, i16 = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call)
+        f32, i16 = f32.view(np.float32), i16.view(np.int16)
+        check(f32, i16, psola_ref.render(w, g, L), label)
+        hf, hi16 = _synth(gpu_ctx, g)(a, g, L)
+        assert hf.tobytes() == f32.tobytes() and hi16.tobytes() == i16.tobytes()
+    finally:
+        hip.hipFree(d_g)
+        a.free()
+
+
 @pytest.mark.parametrize("name", ["n=1, hand-made", "n=255, hand-made, two grains to a centre",
                                   "hand-made, 2048-sample windows 27 apart", "L=254", f"L={TILE - 1}", f"L={TILE}",
                                   f"L={TILE + 1}", f"L={2 * TILE}", "period 2 at r = 2", "period 2, shared centres", "period 2048",
@@ -202,20 +234,45 @@ def test_shapes_inside_guard_bands(gpu_ctx, hip, name):  # noqa: F811
         np.add.at(cover, g["out_lo"], 1)
         np.add.at(cover, g["out_hi"], -1)
         assert np.cumsum(cover).max() >= 150  # (the widest windows at a short period's spacing: the longest walk per sample)
-    a = gpu_ctx.upload(w)
+    _run_shape(gpu_ctx, hip, w, g, L, name)
+
+
+def _device_and_empty_forms(gpu_ctx, hip, a, g, L, f32, i16):  # noqa: F811
+    """The device form of records g (either kind) gives the host form's f32 / i16, with both outputs and with either alone; and
+    the empty calls: no samples — nothing is touched; no grains — zeros."""
+    dev, host = _synth_dev(gpu_ctx, g), _synth(gpu_ctx, g)
     d_g = _to_device(hip, g)
     try:
         def call(p):
-            gpu_ctx.psola_synth_dev(a, d_g.value, len(g), L, p[0], p[1])
-        f32, i16 = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call)
-        f32, i16 = f32.view(np.float32), i16.view(np.int16)
-        check(f32, i16, psola_ref.render(w, g, L), name)
-        # the host form on the same records: the same bytes
-        hf, hi16 = gpu_ctx.psola_synth(a, g, L)
-        assert hf.tobytes() == f32.tobytes() and hi16.tobytes() == i16.tobytes()
+            dev(a, d_g.value, len(g), L, p[0], p[1])
+        df, di = _twice(hip, [L * 4, L * 2], [4 * 3, 2 * 3], call)
+        assert df.tobytes() == f32.tobytes() and di.tobytes() == i16.tobytes()
+
+        def call_f(p):
+            dev(a, d_g.value, len(g), L, p[0], None)
+        (df_only,) = _twice(hip, [L * 4], [4 * 1], call_f)
+        assert df_only.tobytes() == f32.tobytes()
+
+        def call_i(p):
+            dev(a, d_g.value, len(g), L, None, p[0])
+        (di_only,) = _twice(hip, [L * 2], [2 * 1], call_i)
+        assert di_only.tobytes() == i16.tobytes()
+
+        def call_0(p):
+            dev(a, d_g.value, len(g), 0, p[0], p[1])
+        e0 = _twice(hip, [64, 64], [4, 2], call_0)
+        assert (e0[0] == 0xA5).all() and (e0[1] == 0xA5).all()
+
+        def call_z(p):
+            dev(a, None, 0, 1000, p[0], p[1])
+        z = _twice(hip, [4000, 2000], [4, 2], call_z)
+        assert not z[0].any() and not z[1].any()
     finally:
         hip.hipFree(d_g)
-        a.free()
+    zf, zi = host(a, g[:0], 1000)
+    assert zf.shape == (1000,) and not zf.any() and not zi.any()
+    ef, ei = host(a, g[:0], 0)
+    assert len(ef) == 0 and len(ei) == 0
 
 
 def test_forms(gpu_ctx, mxlib, hip, takes):  # noqa: F811
@@ -230,58 +287,30 @@ def test_forms(gpu_ctx, mxlib, hip, takes):  # noqa: F811
     assert none_i is None and none_f is None and only_f.tobytes() == f32.tobytes() and only_i.tobytes() == i16.tobytes()
     rf, ri = gpu_ctx.psola_render(a, SR, HOP, tr, mk)                                            # plan + synth in one call
     assert rf.tobytes() == f32.tobytes() and ri.tobytes() == i16.tobytes()
-    d_g = _to_device(hip, g)
-    try:
-        def call(p):
-            gpu_ctx.psola_synth_dev(a, d_g.value, len(g), L, p[0], p[1])
-        df, di = _twice(hip, [L * 4, L * 2], [4 * 3, 2 * 3], call)                               # the device form
-        assert df.tobytes() == f32.tobytes() and di.tobytes() == i16.tobytes()
+    _device_and_empty_forms(gpu_ctx, hip, a, g, L, f32, i16)
 
-        def call_f(p):
-            gpu_ctx.psola_synth_dev(a, d_g.value, len(g), L, p[0], None)
-        (df_only,) = _twice(hip, [L * 4], [4 * 1], call_f)
-        assert df_only.tobytes() == f32.tobytes()
-
-        def call_i(p):
-            gpu_ctx.psola_synth_dev(a, d_g.value, len(g), L, None, p[0])
-        (di_only,) = _twice(hip, [L * 2], [2 * 1], call_i)
-        assert di_only.tobytes() == i16.tobytes()
-
-        def call_r(p):  # mx_psola_render_dev: host track and markers, device PCM
-            m = mxlib._capi.markers_array(mk)
-            mxlib._capi.check(mxlib._capi.lib().mx_psola_render_dev(gpu_ctx.handle, a.handle, SR, HOP, C.c_void_p(tr.ctypes.data), len(tr),
-                                                                    None, m, len(mk), C.c_void_p(p[0]), C.c_void_p(p[1])))
-        rdf, rdi = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call_r)
-        assert rdf.tobytes() == f32.tobytes() and rdi.tobytes() == i16.tobytes()
-
-        # empty calls: no samples — nothing is touched; no grains — zeros
-        def call_0(p):
-            gpu_ctx.psola_synth_dev(a, d_g.value, len(g), 0, p[0], p[1])
-        e0 = _twice(hip, [64, 64], [4, 2], call_0)
-        assert (e0[0] == 0xA5).all() and (e0[1] == 0xA5).all()
-
-        def call_z(p):
-            gpu_ctx.psola_synth_dev(a, None, 0, 1000, p[0], p[1])
-        z = _twice(hip, [4000, 2000], [4, 2], call_z)
-        assert not z[0].any() and not z[1].any()
-    finally:
-        hip.hipFree(d_g)
-    zf, zi = gpu_ctx.psola_synth(a, g[:0], 1000)
-    assert zf.shape == (1000,) and not zf.any() and not zi.any()
-    ef, ei = gpu_ctx.psola_synth(a, g[:0], 0)
-    assert len(ef) == 0 and len(ei) == 0
+    def call_r(p):  # mx_psola_render_dev: host track and markers, device PCM
+        m = mxlib._capi.markers_array(mk)
+        mxlib._capi.check(mxlib._capi.lib().mx_psola_render_dev(gpu_ctx.handle, a.handle, SR, HOP, C.c_void_p(tr.ctypes.data), len(tr),
+                                                                None, m, len(mk), C.c_void_p(p[0]), C.c_void_p(p[1])))
+    rdf, rdi = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call_r)
+    assert rdf.tobytes() == f32.tobytes() and rdi.tobytes() == i16.tobytes()
 
 
-def _bad_records(g, L, n):
-    """name -> records with one of them broken, one kind of mx_psola_synth's checks each."""
-    k = len(g) // 2
-    out = {}
-
-    def put(name, field, value, at=k):
+def _putter(g, out):
+    """put(name, field, value, at=the middle record): `out[name]` = g with that one field broken."""
+    def put(name, field, value, at=len(g) // 2):
         b = g.copy()
         b[field][at] = value
         out[name] = b
+    return put
 
+
+def _bad_windows(g, L):
+    """name -> records (either kind) with one of them broken: the 14 kinds of the record check that both kinds share."""
+    k = len(g) // 2
+    out = {}
+    put = _putter(g, out)
     b = g.copy()
     b["centre"][k], b["centre_frac"][k] = g["centre"][k - 1], g["centre_frac"][k - 1]
     out["centre + centre_frac repeats"] = b
@@ -297,34 +326,50 @@ def _bad_records(g, L, n):
     put("inv_half inf", "inv_half", np.inf)
     put("inv_half < 1/2048", "inv_half", np.float32(1 / 2049.0))
     put("inv_half negative", "inv_half", -0.01)
-    for f in ("src_frac", "centre_frac"):
-        put(f"{f} = 1", f, 1.0)
-        put(f"{f} < 0", f, -0.25)
-        put(f"{f} NaN", f, np.nan)
+    put("centre_frac = 1", "centre_frac", 1.0)
+    put("centre_frac < 0", "centre_frac", -0.25)
+    put("centre_frac NaN", "centre_frac", np.nan)
+    assert len(out) == 14
+    return out
+
+
+def _bad_records(g, L, n):
+    """name -> records with one of them broken, one kind of mx_psola_synth's checks each."""
+    k = len(g) // 2
+    out = _bad_windows(g, L)
+    put = _putter(g, out)
+    put("src_frac = 1", "src_frac", 1.0)
+    put("src_frac < 0", "src_frac", -0.25)
+    put("src_frac NaN", "src_frac", np.nan)
     put("source left of the pad", "src_off", -int(g["out_lo"][k]) - 32768 - 1)
     put("source right of the pad", "src_off", n + 32768 - int(g["out_hi"][k]))
     return out
 
 
-def test_bad_records_are_refused_by_the_host_form(gpu_ctx, mxlib, takes):
-    w, a, tr = takes["vowel"]
-    g, L = mxlib.psola_plan(len(w), SR, HOP, tr, bend(len(w), 4.0))
-    lib = mxlib._capi.lib()
-    bads = _bad_records(g, L, len(w))
-    assert len(bads) == 19
+def _refused(gpu_ctx, lib, a, g, L, bads):
+    """The host form of g's kind refuses every one of `bads` before anything is written, and counts out of range and null
+    records (the device form too)."""
+    host, dev = getattr(lib, "mx_psola_synth" + _sfx(g)), getattr(lib, f"mx_psola_synth{_sfx(g)}_dev")
     for name, b in bads.items():
         f32 = np.full(L, 7.0, dtype=np.float32)
         i16 = np.full(L, 77, dtype=np.int16)
-        rc = lib.mx_psola_synth(gpu_ctx.handle, a.handle, C.c_void_p(b.ctypes.data), len(b), L, C.c_void_p(f32.ctypes.data),
-                                C.c_void_p(i16.ctypes.data))
+        rc = host(gpu_ctx.handle, a.handle, C.c_void_p(b.ctypes.data), len(b), L, C.c_void_p(f32.ctypes.data), C.c_void_p(i16.ctypes.data))
         assert rc == -1 and b"grain" in lib.mx_last_error(), (name, rc, lib.mx_last_error())
         assert (f32 == 7.0).all() and (i16 == 77).all(), name
-    # counts out of range, null records
-    assert lib.mx_psola_synth(gpu_ctx.handle, a.handle, C.c_void_p(g.ctypes.data), -1, L, None, None) == -1
-    assert lib.mx_psola_synth(gpu_ctx.handle, a.handle, C.c_void_p(g.ctypes.data), len(g), -1, None, None) == -1
-    assert lib.mx_psola_synth(gpu_ctx.handle, a.handle, C.c_void_p(g.ctypes.data), len(g), 2 ** 31, None, None) == -1
-    assert lib.mx_psola_synth(gpu_ctx.handle, a.handle, None, len(g), L, None, None) == -1
-    assert lib.mx_psola_synth_dev(gpu_ctx.handle, a.handle, None, len(g), L, None, None) == -1
+    gp = C.c_void_p(g.ctypes.data)
+    assert host(gpu_ctx.handle, a.handle, gp, -1, L, None, None) == -1
+    assert host(gpu_ctx.handle, a.handle, gp, len(g), -1, None, None) == -1
+    assert host(gpu_ctx.handle, a.handle, gp, len(g), 2 ** 31, None, None) == -1
+    assert host(gpu_ctx.handle, a.handle, None, len(g), L, None, None) == -1
+    assert dev(gpu_ctx.handle, a.handle, None, len(g), L, None, None) == -1
+
+
+def test_bad_records_are_refused_by_the_host_form(gpu_ctx, mxlib, takes):
+    w, a, tr = takes["vowel"]
+    g, L = mxlib.psola_plan(len(w), SR, HOP, tr, bend(len(w), 4.0))
+    bads = _bad_records(g, L, len(w))
+    assert len(bads) == 19
+    _refused(gpu_ctx, mxlib._capi.lib(), a, g, L, bads)
     # ... and a track that does not fit the file, through the one-call form
     with pytest.raises(mxlib.MxError) as e:
         gpu_ctx.psola_render(a, SR, HOP, tr[:-1], [])

@@ -26,7 +26,7 @@ def test_psola_facade_matches_python(gpu_ctx, mxlib, tmp_path, decoded):
     w = vowel(0.75)
     src, out, wav = tmp_path / "in.f32", tmp_path / "out.f32", tmp_path / "out.wav"
     w.astype("<f4").tofile(src)
-    r = subprocess.run([exe, str(src), str(SR), "4", str(decoded), str(out), str(wav)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, "plain", str(src), str(SR), "4", str(decoded), str(out), str(wav)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert f"threshold {0.3 if decoded else 0.15:g}" in r.stdout, r.stdout
     a = gpu_ctx.upload(w)

@@ -15,9 +15,9 @@ import pytest
 
 import psola_formant_ref as FR
 from conftest import SR
-from test_gpu_guard import _to_device, _twice, hip  # noqa: F401  (hip: the module's HIP runtime fixture)
-from test_gpu_psola import (HOP, TILE, _gpu_note, _hand_plan, _markers, _ref_note, _strongest_harmonic, bend, check,  # noqa: F401
-                            input_notes, takes)
+from test_gpu_guard import _twice, hip  # noqa: F401  (hip: the module's HIP runtime fixture)
+from test_gpu_psola import (HOP, TILE, _bad_windows, _device_and_empty_forms, _gpu_note, _hand_plan, _markers, _putter,  # noqa: F401
+                            _ref_note, _refused, _run_shape, _strongest_harmonic, bend, check, input_notes, takes)
 from test_psola_host import tracks
 
 pytestmark = pytest.mark.gpu
@@ -103,34 +103,16 @@ def test_forms(gpu_ctx, mxlib, hip, takes):  # noqa: F811
     assert none_i is None and none_f is None and only_f.tobytes() == f32.tobytes() and only_i.tobytes() == i16.tobytes()
     rf, ri = gpu_ctx.psola_render_formant(a, SR, HOP, tr, mk, pts)                                # plan + synth in one call
     assert rf.tobytes() == f32.tobytes() and ri.tobytes() == i16.tobytes()
-    d_g = _to_device(hip, fg)
-    try:
-        def call(p):
-            gpu_ctx.psola_synth_formant_dev(a, d_g.value, len(fg), L, p[0], p[1])
-        df, di = _twice(hip, [L * 4, L * 2], [4 * 3, 2 * 3], call)                                # the device form
-        assert df.tobytes() == f32.tobytes() and di.tobytes() == i16.tobytes()
+    _device_and_empty_forms(gpu_ctx, hip, a, fg, L, f32, i16)
 
-        def call_r(p):  # mx_psola_render_formant_dev
-            m = mxlib._capi.markers_array(mk)
-            pa = mxlib._formant_points(pts)
-            mxlib._capi.check(mxlib._capi.lib().mx_psola_render_formant_dev(
-                gpu_ctx.handle, a.handle, SR, HOP, C.c_void_p(tr.ctypes.data), len(tr), None, m, len(mk), C.c_void_p(pa.ctypes.data),
-                len(pa), C.c_void_p(p[0]), C.c_void_p(p[1])))
-        rdf, rdi = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call_r)
-        assert rdf.tobytes() == f32.tobytes() and rdi.tobytes() == i16.tobytes()
-
-        # empty calls: no samples — nothing is touched; no grains — zeros
-        def call_0(p):
-            gpu_ctx.psola_synth_formant_dev(a, d_g.value, len(fg), 0, p[0], p[1])
-        e0 = _twice(hip, [64, 64], [4, 2], call_0)
-        assert (e0[0] == 0xA5).all() and (e0[1] == 0xA5).all()
-
-        def call_z(p):
-            gpu_ctx.psola_synth_formant_dev(a, None, 0, 1000, p[0], p[1])
-        z = _twice(hip, [4000, 2000], [4, 2], call_z)
-        assert not z[0].any() and not z[1].any()
-    finally:
-        hip.hipFree(d_g)
+    def call_r(p):  # mx_psola_render_formant_dev
+        m = mxlib._capi.markers_array(mk)
+        pa = mxlib._formant_points(pts)
+        mxlib._capi.check(mxlib._capi.lib().mx_psola_render_formant_dev(
+            gpu_ctx.handle, a.handle, SR, HOP, C.c_void_p(tr.ctypes.data), len(tr), None, m, len(mk), C.c_void_p(pa.ctypes.data),
+            len(pa), C.c_void_p(p[0]), C.c_void_p(p[1])))
+    rdf, rdi = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call_r)
+    assert rdf.tobytes() == f32.tobytes() and rdi.tobytes() == i16.tobytes()
     # every record 1023 outputs later: the same samples 1023 outputs later, whatever tile they fall into
     sh = fg.copy()
     for f in ("out_lo", "out_hi", "centre"):
@@ -199,20 +181,7 @@ def _shape_cases():
 def test_shapes_inside_guard_bands(gpu_ctx, hip, name):  # noqa: F811
     n, g, L = _shape_cases()[name]
     w = np.random.default_rng(n).uniform(-0.9, 0.9, n).astype(np.float32)
-    a = gpu_ctx.upload(w)
-    d_g = _to_device(hip, g)
-    try:
-        def call(p):
-            gpu_ctx.psola_synth_formant_dev(a, d_g.value, len(g), L, p[0], p[1])
-        f32, i16 = _twice(hip, [L * 4, L * 2], [4 * 1, 2 * 1], call)
-        f32, i16 = f32.view(np.float32), i16.view(np.int16)
-        check(f32, i16, FR.render_formant(w, g, L), f"formant, {name}")
-        # the host form on the same records (its record check passes them): the same bytes
-        hf, hi16 = gpu_ctx.psola_synth_formant(a, g, L)
-        assert hf.tobytes() == f32.tobytes() and hi16.tobytes() == i16.tobytes()
-    finally:
-        hip.hipFree(d_g)
-        a.free()
+    _run_shape(gpu_ctx, hip, w, g, L, f"formant, {name}")
 
 
 @pytest.mark.parametrize("st,formant", [(0.0, 4.0), (0.0, -3.0), (4.0, 4.0)])
@@ -238,12 +207,7 @@ def _bad_records(g, L, n):
     """name -> records with one of them broken, one kind of mx_psola_synth_formant's checks each."""
     k = len(g) // 2
     out = {}
-
-    def put(name, field, value, at=k):
-        b = g.copy()
-        b[field][at] = value
-        out[name] = b
-
+    put = _putter(g, out)
     put("step 32767", "step", 32767)
     put("step 131073", "step", 131073)
     put("step 0", "step", 0)
@@ -253,25 +217,7 @@ def _bad_records(g, L, n):
     hi_off = (int(g["src_q"][k]) + int(g["step"][k]) * (int(g["out_hi"][k]) - 1 - int(g["centre"][k]))) >> 16
     put("source left of the pad", "src_idx", -PAD - 1 - lo_off)
     put("source right of the pad", "src_idx", n + PAD - 1 - hi_off)
-    # the plain kinds that still apply
-    b = g.copy()
-    b["centre"][k], b["centre_frac"][k] = g["centre"][k - 1], g["centre_frac"][k - 1]
-    out["centre + centre_frac repeats"] = b
-    b = g.copy()
-    b[k - 1], b[k] = g[k], g[k - 1]
-    out["centre + centre_frac falls"] = b
-    put("out_lo < 0", "out_lo", -1, at=0)
-    put("out_lo > out_hi", "out_lo", g["out_hi"][k] + 1)
-    put("out_hi > nsamples", "out_hi", L + 1, at=len(g) - 1)
-    put("window left of centre - 2049", "out_lo", g["centre"][k] - 2050)
-    put("window right of centre + 2049", "out_hi", g["centre"][k] + 2051)
-    put("inv_half NaN", "inv_half", np.nan)
-    put("inv_half inf", "inv_half", np.inf)
-    put("inv_half < 1/2048", "inv_half", np.float32(1 / 2049.0))
-    put("inv_half negative", "inv_half", -0.01)
-    put("centre_frac = 1", "centre_frac", 1.0)
-    put("centre_frac < 0", "centre_frac", -0.25)
-    put("centre_frac NaN", "centre_frac", np.nan)
+    out.update(_bad_windows(g, L))  # (the plain kinds that still apply)
     return out, (lo_off, hi_off)
 
 
@@ -279,23 +225,9 @@ def test_bad_records_are_refused_by_the_host_form(gpu_ctx, mxlib, takes):  # noq
     w, a, tr = takes["vowel"]
     n = len(w)
     g, L = mxlib.psola_plan_formant(n, SR, HOP, tr, bend(n, 4.0), const(4.0))
-    lib = mxlib._capi.lib()
     bads, (lo_off, hi_off) = _bad_records(g, L, n)
     assert len(bads) == 20
-    for name, b in bads.items():
-        f32 = np.full(L, 7.0, dtype=np.float32)
-        i16 = np.full(L, 77, dtype=np.int16)
-        rc = lib.mx_psola_synth_formant(gpu_ctx.handle, a.handle, C.c_void_p(b.ctypes.data), len(b), L, C.c_void_p(f32.ctypes.data),
-                                        C.c_void_p(i16.ctypes.data))
-        assert rc == -1 and b"grain" in lib.mx_last_error(), (name, rc, lib.mx_last_error())
-        assert (f32 == 7.0).all() and (i16 == 77).all(), name
-    # counts out of range, null records
-    gp = C.c_void_p(g.ctypes.data)
-    assert lib.mx_psola_synth_formant(gpu_ctx.handle, a.handle, gp, -1, L, None, None) == -1
-    assert lib.mx_psola_synth_formant(gpu_ctx.handle, a.handle, gp, len(g), -1, None, None) == -1
-    assert lib.mx_psola_synth_formant(gpu_ctx.handle, a.handle, gp, len(g), 2 ** 31, None, None) == -1
-    assert lib.mx_psola_synth_formant(gpu_ctx.handle, a.handle, None, len(g), L, None, None) == -1
-    assert lib.mx_psola_synth_formant_dev(gpu_ctx.handle, a.handle, None, len(g), L, None, None) == -1
+    _refused(gpu_ctx, mxlib._capi.lib(), a, g, L, bads)
     # ... a bad curve and a track that does not fit the file, through the one-call form
     for tr_, pts in ((tr, [(5, 1.0), (5, 2.0)]), (tr[:-1], const(1.0))):
         with pytest.raises(mxlib.MxError) as e:

@@ -17,14 +17,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_psola_formant_facade_matches_python(gpu_ctx, mxlib, tmp_path):
     lib = os.path.join(ROOT, "melonix_amd", "lib")
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "melonix_amd", "cpp"), "NO_GL=1"])
-    exe = str(tmp_path / "psola_formant_driver")
+    exe = str(tmp_path / "psola_driver")
     subprocess.check_call(["g++", "-std=c++20", "-O2", "-DMELONIX_AMD_NO_GL", "-I", os.path.join(ROOT, "melonix_amd", "cpp"), "-I",
-                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "psola_formant_driver.cpp"),
+                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "psola_driver.cpp"),
                            "-o", exe, "-L", lib, "-lmelonix_facade", "-lmelonix_amd", f"-Wl,-rpath,{lib}", "-lpthread"])
     w = vowel(0.75)
     src, out, wav = tmp_path / "in.f32", tmp_path / "out.f32", tmp_path / "out.wav"
     w.astype("<f4").tofile(src)
-    r = subprocess.run([exe, str(src), str(SR), "4", "-3", "5", str(out), str(wav)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, "formant", str(src), str(SR), "4", "-3", "5", str(out), str(wav)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     a = gpu_ctx.upload(w)
     try:

@@ -43,7 +43,7 @@ def _cases():
 def test_plan_matches_reference(mxlib, n, tn, mn):
     track, markers = tracks(n, HOP)[tn], marker_sets(n, SR)[mn]
     g, L = psola_ref.plan(n, SR, HOP, track, markers)
-    marks = FR.analysis_marks(n, HOP, track) if len(g) else []
+    marks = psola_ref.marks(n, HOP, track)[0] if len(g) else []
     pg, pL = mxlib.psola_plan(n, SR, HOP, track, markers)
     assert pL == L
     for cn, pts in curves(n).items():
@@ -75,6 +75,11 @@ def test_plan_formant_is_the_reference_plan_formant(mxlib):
     fg, L = mxlib.psola_plan_formant(n, SR, HOP, track, markers, pts, unvoiced_period=100.0)
     ref, rL = FR.plan_formant(n, SR, HOP, track, markers, pts, unvoiced_period=100.0)
     assert L == rL and fg.tobytes() == ref.tobytes()
+    # ... and with a long curve handed in as a list of pairs: the wrapper's own array of the points has to outlive the call
+    pts = [(40 * j - 2000, float(7.0 * np.sin(0.37 * j))) for j in range(1000)]
+    fg, L = mxlib.psola_plan_formant(n, SR, HOP, track, markers, pts)
+    ref, rL = FR.plan_formant(n, SR, HOP, track, markers, pts)
+    assert L == rL and fg.tobytes() == ref.tobytes() and np.unique(fg["step"]).size > 10
 
 
 def test_no_points_is_step_one(mxlib):

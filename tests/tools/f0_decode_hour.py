@@ -19,34 +19,28 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 
 import melonix_amd as mx  # noqa: E402
 from conftest import SR, DevBuf, accum_sweep, loaded_hip  # noqa: E402
+from hip_timing import EventTimer, TimedLib, device_image, libraries, same_bytes  # noqa: E402
 
 HOP, WARM, RUNS = 256, 5, 20
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 TRACK_ARGS = [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f]
 
 
-class Lib:
+class Lib(TimedLib):
     """One library's context, its handle on the shared device image and its own output buffers; the table's calls."""
 
     def __init__(self, path, d_img, n, frames):
-        self.so = so = C.CDLL(os.path.abspath(path))
-        so.mx_ctx_create.argtypes = [_i, C.POINTER(_vp)]
-        so.mx_ctx_set_stream.argtypes = [_vp, _vp]
-        so.mx_audio_wrap_device.argtypes = [_vp, _vp, _i64, C.POINTER(_vp)]
+        super().__init__(path, d_img, n)
+        so, self.frames = self.so, frames
         so.mx_f0_track_dev.argtypes = TRACK_ARGS + [_vp]
         so.mx_f0_candidates_dev.argtypes = TRACK_ARGS + [_vp, _vp]
         so.mx_f0_decode_dev.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp, _vp]
         so.mx_f0_decode_set_chunk.argtypes = [_vp, _i64]
-        so.mx_version.restype = C.c_char_p
-        self.version = so.mx_version().decode()
-        self.ctx, self.audio, self.frames = _vp(), _vp(), frames
-        assert so.mx_ctx_create(0, C.byref(self.ctx)) == 0
-        assert so.mx_ctx_set_stream(self.ctx, None) == 0  # the null stream: the events bracket exactly the launches
-        assert so.mx_audio_wrap_device(self.ctx, _vp(d_img.ptr), n, C.byref(self.audio)) == 0
         self.track, self.cands, self.out, self.state = (DevBuf(frames * k) for k in (16, 64, 16, 1))
 
     def range_args(self, first, count):
@@ -69,20 +63,6 @@ class Lib:
                                         _vp(self.out.ptr), _vp(self.state.ptr)) == 0
 
 
-def device_image(w):
-    """The padded device image of the samples that every library wraps."""
-    d_img = DevBuf((len(w) + 2 * mx.MX_AUDIO_PAD) * 4)
-    d_img.write(w, offset=mx.MX_AUDIO_PAD * 4)
-    return d_img
-
-
-def same_bytes(libs, *names):
-    """Asserts the named output buffers equal, byte for byte, across the libraries; -> the first library's."""
-    got = [[getattr(L, k).read(np.uint8).tobytes() for k in names] for L in libs.values()]
-    assert all(g == got[0] for g in got[1:]), names
-    return got[0]
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib")
@@ -92,35 +72,12 @@ def main():
     n = int(args.seconds * SR)
     F = mx.frame_count(n, HOP)
     d_img = device_image(accum_sweep(n))
-    libs = {"new": Lib(mx._capi.lib()._name, d_img, n, F)}
-    if args.parent_lib:
-        libs["parent"] = Lib(args.parent_lib, d_img, n, F)
-        libs["parent_again"] = Lib(args.parent_lib, d_img, n, F)
-    hip = loaded_hip()
-    hip.hipEventCreate.argtypes = [C.POINTER(_vp)]
-    hip.hipEventRecord.argtypes = [_vp, _vp]
-    hip.hipEventSynchronize.argtypes = [_vp]
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), _vp, _vp]
-    e0, e1 = _vp(), _vp()
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
-
-    def once(call):
-        assert hip.hipEventRecord(e0, None) == 0
-        call()
-        assert hip.hipEventRecord(e1, None) == 0 and hip.hipEventSynchronize(e1) == 0
-        ms = C.c_float()
-        assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-        return ms.value
+    libs = libraries(Lib, args.parent_lib, d_img, n, F)
+    timer = EventTimer(loaded_hip())
 
     def timed(call):
         """{library: (median, min, max) ms} of Lib.call, the libraries in turn (interleaved) WARM + RUNS times each."""
-        ts = {k: [] for k in libs}
-        for it in range(WARM + RUNS):
-            for k, L in libs.items():
-                t = once(lambda: call(L))
-                if it >= WARM:
-                    ts[k].append(t)
-        return {k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()}
+        return timer.timed({k: (lambda L=L: call(L)) for k, L in libs.items()}, WARM, RUNS)
 
     # the table: (row, what to do before it, the call, the buffers whose bytes the libraries must share)
     table = [("track", None, Lib.f0_track, ("track",)), ("candidates", None, Lib.f0_candidates, ("track", "cands"))]
