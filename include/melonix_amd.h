@@ -652,6 +652,100 @@ int mx_psola_render_formant_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, 
                                 const mx_psola_params *params, const mx_marker *markers, int nmarkers,
                                 const mx_formant_point *points, int npoints, float *d_pcm_f32, int16_t *d_pcm_i16);
 
+/* ---- Onset detection and tempo-grid timing markers (BUILD-DEFINED; restated in f64 by tests/onset_ref.py) ----
+ * mx_marker.dTime is the editor's time-warp handle and every renderer follows it; this finds where events start and
+ * computes the dTime values that put them on a tempo grid.  The reference has no detector.
+ *
+ * Onset strength.  The detector has a transform of its own (the reference window of the magnitude rows is rectangular with
+ * an exponential tail: a steady tone's bins ripple from frame to frame, and spectral flux over them peaks every ~11 frames
+ * on a held note).  For frame h of the bulk indexing (h < mx_frame_count(n, hop)), centred on sample h*hop:
+ *   x_j = audio[h*hop - 512 + j], j < 1024, zeros outside the file;  w_j = 0.5 - 0.5 cos(2 pi j / 1024);
+ *   X_k = the 1024-point DFT of w x;  m_k = |X_k| / 512;  c_h[k] = log1pf(compress * m_k), in f32;
+ *   flux_h = sum_{k = kmin..kmax} max(0, c_h[k] - c_{h-lag}[k]), with c_h = 0 for h < 0;
+ *   kmin = max(1, ceil(fmin * 1024 / sr)), kmax = min(511, floor(fmax * 1024 / sr)); fmax = 0 means sr / 2.
+ * The level matters by design: log1p(compress * m) is linear in m for a quiet take, so a quiet take has small flux (at a
+ * tenth of the level the curve is not a tenth, and the picker's additive term delta does not scale).  A frame of zeros has
+ * c = 0; silence has flux exactly 0.  A sample that is Inf or NaN makes its frames' values Inf or NaN; the picker counts
+ * those as 0.
+ * The per-frame reduction has one fixed order, so frame h's value depends on nothing but its samples and frame h-lag's:
+ * the same bytes whatever the launch split (first_frame, count) or the run length a walker takes.  No spectrum goes to HBM:
+ * the launch writes 4 bytes per frame. */
+typedef struct mx_onset_flux_params {
+  float compress; /* finite, in (0, 1e6] */
+  int32_t lag;    /* in [1, 4] */
+  float fmin, fmax; /* Hz, finite, >= 0; fmax == 0: sr / 2 */
+} mx_onset_flux_params;
+/* {100.f, 1, 0.f, 0.f} */
+void mx_onset_flux_params_default(mx_onset_flux_params *p);
+/* Frames [first_frame, first_frame + count) -> d_flux (count floats in HBM).  Asynchronous on the context's stream.
+ * params NULL: the defaults.  MX_ERR_INVALID, before any launch, for sr <= 0, hop outside [1, 16384], frames outside the
+ * file, a parameter out of range or an empty band. */
+int mx_onset_flux_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                      const mx_onset_flux_params *params, float *d_flux);
+/* Same, host output through the context's staging buffers.  Blocks. */
+int mx_onset_flux(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                  const mx_onset_flux_params *params, float *flux_out);
+
+/* Peak picking (host, binary64, exact).  o_i = flux[i] as a double, 0 where it is not finite; windows are clipped to
+ * [0, count).  Index f, taken in ascending order, is an onset when all three hold:
+ *   o_f > o_g for every g in [f - pre_max, f) and o_f >= o_g for every g in (f, f + post_max] (a plateau: its first index);
+ *   o_f >= ratio * mean(o over [f - pre_avg, f + post_avg]) + delta, the mean summed in ascending order and divided by the
+ *   clipped window's length;
+ *   f - (the previous accepted index) > wait.
+ * Defaults {3, 3, 25, 1, 8, 2.0, 1.0}: values that separate tests/onset_ref.py's synthetic signals (notes with 5 and 30 ms
+ * attacks, a legato, a vibrato, steady noise, clicks) with every decision at least 0.9 flux units from its threshold.  Nobody
+ * has tuned them on recordings.  The multiplicative term is what keeps steady noise quiet; delta what keeps a near-silent
+ * take quiet. */
+typedef struct mx_onset_pick_params {
+  int32_t pre_max, post_max, pre_avg, post_avg, wait; /* each in [0, 4096] */
+  double ratio, delta;                                /* finite, >= 0 */
+} mx_onset_pick_params;
+typedef struct mx_onset {
+  int32_t sample; /* frame * hop, absolute */
+  int32_t frame;  /* first_frame + f */
+  float strength; /* o_f */
+  float margin;   /* o_f - threshold */
+} mx_onset;
+void mx_onset_pick_params_default(mx_onset_pick_params *p);
+/* flux[i] is frame first_frame + i.  params NULL: the defaults.  *out is library-allocated (free with mx_free).
+ * MX_ERR_INVALID for a parameter out of range, hop < 1 or frame centres beyond int32 samples. */
+int mx_onset_pick(const float *flux, int64_t count, int hop, int64_t first_frame, const mx_onset_pick_params *params,
+                  mx_onset **out, int64_t *nout);
+/* Flux over the whole file and the picks from it.  Either params may be NULL.  Blocks. */
+int mx_onsets_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_onset_flux_params *flux_params,
+                     const mx_onset_pick_params *pick_params, mx_onset **out, int64_t *nout);
+
+/* Timing markers (host, binary64, exact).  Anchors (source samples, e.g. mx_onset.sample) move towards the lines of a
+ * tempo grid; the markers returned make every renderer play them there.
+ *   anchors   strictly increasing, in [0, n); anchors at sample <= 0 are dropped (a marker at sample 0 has no span).
+ *   targets   g = 60 / (bpm * division), t_i = a_i / sr;  q_i = floor((t_i - offset) / g + 0.5);
+ *             d_i = offset + q_i * g - t_i, 0 where |d_i| > max_shift (such an anchor still pins its time);
+ *             U_i = t_i + strength * d_i.
+ *   monotone  T_{-1} = 0, a_{-1} = 0;  span = (a_i - a_{i-1}) / sr;
+ *             T_i = T_{i-1} + clamp(U_i - T_{i-1}, span / max_stretch, span * max_stretch).
+ *   warp      W(s): piecewise linear through (0, 0) and (a_i, T_i), in sample2Time's form
+ *             T_{i-1} + (s - a_{i-1}) * (T_i - T_{i-1}) / (a_i - a_{i-1}); the natural rate behind the last anchor.
+ *   output    one marker per sample in anchors U base samples, sorted, with
+ *             dTime_j = (W(s_j) - W(s_{j-1})) - (s_j - s_{j-1}) / sr  (s_{-1} = 0);  |dTime_j| < 1e-10 s is written as 0: the
+ *             rounding residue of the two differences, not a shift — strength 0 gives the identity map exactly.
+ * base (may be NULL) is what mx_correction_markers gives: samples strictly increasing in [1, n), every dTime == 0.  A
+ * marker on a base sample keeps that marker's note and pitchBend.  An inserted marker gets pitchBend by linear interpolation
+ * in source samples through (0, 0), the base points and (n - 1, 0) — time2PitchBend's own curve, so the bend over the source
+ * is unchanged — and note interpolated between its neighbours, the nearer end's note outside them, 0 with no base.
+ * *out is library-allocated (free with mx_free).  MX_ERR_INVALID for anchors or base out of order or range, a base dTime
+ * != 0 or a bend / note that is not finite, a parameter outside its range below, sr <= 0 or n outside [1, INT32_MAX]. */
+typedef struct mx_timing_params {
+  double bpm;         /* [30, 250], the reference's Tempo slider; default 120 */
+  int32_t division;   /* grid lines per beat, [1, 64]; default 4 */
+  double offset;      /* time of a grid line, seconds, finite; default 0 */
+  double strength;    /* [0, 1]; default 1 */
+  double max_shift;   /* seconds, >= 0, finite; default 0.1 */
+  double max_stretch; /* [1, 4]; default 2 */
+} mx_timing_params;
+void mx_timing_params_default(mx_timing_params *p);
+int mx_timing_markers(const int32_t *anchors, int64_t nanchors, int64_t n, int sampleRate, const mx_timing_params *params,
+                      const mx_marker *base, int nbase, mx_marker **out, int64_t *nout);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

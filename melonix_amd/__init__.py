@@ -14,14 +14,16 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, PITCH_DTYPE,  # noqa: F401
+from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, ONSET_DTYPE, PITCH_DTYPE,  # noqa: F401
                     PSOLA_FGRAIN_DTYPE, PSOLA_GRAIN_DTYPE, STEP_DTYPE, MxError)
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
            "F0_DTYPE", "F0_CAND_DTYPE", "f0_decode_params_default", "NOTE_DTYPE", "MARKER_DTYPE", "note_params_default", "detect_notes", "correction_markers",
            "PSOLA_GRAIN_DTYPE", "psola_params_default", "psola_plan",
-           "PSOLA_FGRAIN_DTYPE", "FORMANT_POINT_DTYPE", "psola_plan_formant"]
+           "PSOLA_FGRAIN_DTYPE", "FORMANT_POINT_DTYPE", "psola_plan_formant",
+           "ONSET_DTYPE", "onset_flux_params_default", "onset_pick_params_default", "onset_pick", "timing_params_default",
+           "timing_markers"]
 
 
 def _ptr(a):
@@ -328,6 +330,27 @@ class Context:
     def f0_decode_set_chunk(self, frames: int):
         """Frames per chunk of the decode's scans (0 = the default); for tests: the output does not depend on it."""
         _capi.check(_capi.lib().mx_f0_decode_set_chunk(self.handle, int(frames)))
+
+    # ---- onset strength and onsets (build-defined; include/melonix_amd.h) ----
+    def onset_flux(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, **params):
+        """-> float32 onset strength of frames [first, first + count) (frame h centred on sample h*hop).  params: fields of
+        onset_flux_params_default()."""
+        count = _frames_from(audio, hop, first, count)
+        out = np.empty(max(count, 0), dtype=np.float32)
+        _capi.check(_capi.lib().mx_onset_flux(self.handle, audio.handle, sr, hop, first, count, _flux_params(params), _ptr(out)))
+        return out
+
+    def onset_flux_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_flux: int, **params):
+        """The values stay in HBM at d_flux (count x 4 bytes); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_onset_flux_dev(self.handle, audio.handle, sr, hop, first, count, _flux_params(params),
+                                                  C.c_void_p(d_flux or 0)))
+
+    def onsets_detect(self, audio: Audio, sr: int, hop: int = 256, flux_params: dict | None = None, pick_params: dict | None = None):
+        """Flux over the whole file and the picks from it -> ONSET_DTYPE array."""
+        out, cnt = C.c_void_p(), C.c_int64()
+        _capi.check(_capi.lib().mx_onsets_detect(self.handle, audio.handle, sr, hop, _flux_params(flux_params or {}),
+                                                 _pick_params(pick_params or {}), C.byref(out), C.byref(cnt)))
+        return _take_records(out, cnt.value, ONSET_DTYPE)
 
     # ---- grains / resynthesis ----
     def grains_dev(self, audio: Audio):
@@ -744,3 +767,71 @@ def psola_plan_formant(n: int, sr: int, hop: int, track, markers, points, **para
     """psola_plan with a formant curve -> (PSOLA_FGRAIN_DTYPE array, nsamples).  points: (source sample, semitones) pairs,
     samples strictly increasing; none: every record's step is 65536."""
     return _psola_plan(True, n, sr, hop, track, markers, points, params)
+
+
+# ---- onsets and timing markers (host; build-defined) ----
+def _params_default(kind, fn: str) -> dict:
+    p = kind()
+    getattr(_capi.lib(), fn)(C.byref(p))
+    return {k: getattr(p, k) for k, _ in kind._fields_}
+
+
+def _params_arg(kind, fn: str, params: dict):
+    """The defaults with `params` over them, for the C-ABI; nothing given: NULL (the library's defaults)."""
+    if not params:
+        return None
+    d = _params_default(kind, fn)
+    unknown = set(params) - set(d)
+    if unknown:
+        raise TypeError(f"unknown parameters {sorted(unknown)}")
+    d.update(params)
+    return C.byref(kind(**d))
+
+
+def onset_flux_params_default() -> dict:
+    return _params_default(_capi.OnsetFluxParams, "mx_onset_flux_params_default")
+
+
+def onset_pick_params_default() -> dict:
+    return _params_default(_capi.OnsetPickParams, "mx_onset_pick_params_default")
+
+
+def timing_params_default() -> dict:
+    return _params_default(_capi.TimingParams, "mx_timing_params_default")
+
+
+def _flux_params(params: dict):
+    return _params_arg(_capi.OnsetFluxParams, "mx_onset_flux_params_default", params)
+
+
+def _pick_params(params: dict):
+    return _params_arg(_capi.OnsetPickParams, "mx_onset_pick_params_default", params)
+
+
+def onset_pick(flux, hop: int, first: int = 0, **params):
+    """Onsets of an onset-strength curve (flux[0] = frame `first`) -> ONSET_DTYPE array.  params: fields of
+    onset_pick_params_default()."""
+    flux = np.ascontiguousarray(flux, dtype=np.float32)
+    out, cnt = C.c_void_p(), C.c_int64()
+    _capi.check(_capi.lib().mx_onset_pick(_ptr(flux) if len(flux) else None, len(flux), hop, first, _pick_params(params),
+                                          C.byref(out), C.byref(cnt)))
+    return _take_records(out, cnt.value, ONSET_DTYPE)
+
+
+def timing_markers(anchors, n: int, sr: int, base=None, **params):
+    """The markers that move `anchors` (source samples) onto the tempo grid -> MARKER_DTYPE array.  base: a MARKER_DTYPE
+    array (correction_markers) or (sample, note, dTime, pitchBend) tuples to merge; params: fields of timing_params_default()."""
+    anchors = np.ascontiguousarray(anchors, dtype=np.int32)
+    if base is None:
+        base = np.zeros(0, dtype=MARKER_DTYPE)
+    elif not (isinstance(base, np.ndarray) and base.dtype == MARKER_DTYPE):
+        b = np.zeros(len(base), dtype=MARKER_DTYPE)
+        for i, m in enumerate(base):
+            b[i] = (int(m[0]), float(m[1]), float(m[2]), float(m[3]))
+        base = b
+    base = np.ascontiguousarray(base)
+    out, cnt = C.c_void_p(), C.c_int64()
+    _capi.check(_capi.lib().mx_timing_markers(_ptr(anchors) if len(anchors) else None, len(anchors), int(n), sr,
+                                              _params_arg(_capi.TimingParams, "mx_timing_params_default", params),
+                                              _ptr(base) if len(base) else None, len(base), C.byref(out), C.byref(cnt)))
+    return _take_records(out, cnt.value, MARKER_DTYPE)

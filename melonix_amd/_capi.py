@@ -80,6 +80,24 @@ class PsolaFGrain(C.Structure):
                 ("centre", C.c_int32), ("centre_frac", C.c_float), ("inv_half", C.c_float), ("step", C.c_uint32)]
 
 
+class OnsetFluxParams(C.Structure):
+    _fields_ = [("compress", C.c_float), ("lag", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
+
+
+class OnsetPickParams(C.Structure):
+    _fields_ = [("pre_max", C.c_int32), ("post_max", C.c_int32), ("pre_avg", C.c_int32), ("post_avg", C.c_int32),
+                ("wait", C.c_int32), ("ratio", C.c_double), ("delta", C.c_double)]
+
+
+class Onset(C.Structure):
+    _fields_ = [("sample", C.c_int32), ("frame", C.c_int32), ("strength", C.c_float), ("margin", C.c_float)]
+
+
+class TimingParams(C.Structure):
+    _fields_ = [("bpm", C.c_double), ("division", C.c_int32), ("offset", C.c_double), ("strength", C.c_double),
+                ("max_shift", C.c_double), ("max_stretch", C.c_double)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -97,6 +115,8 @@ FORMANT_POINT_DTYPE = np.dtype([("sample", "<i4"), ("semitones", "<f4")])
 PSOLA_FGRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_idx", "<i4"), ("src_q", "<u4"), ("centre", "<i4"),
                                ("centre_frac", "<f4"), ("inv_half", "<f4"), ("step", "<u4")])
 assert PSOLA_FGRAIN_DTYPE.itemsize == C.sizeof(PsolaFGrain) == 32 and FORMANT_POINT_DTYPE.itemsize == C.sizeof(FormantPoint) == 8
+ONSET_DTYPE = np.dtype([("sample", "<i4"), ("frame", "<i4"), ("strength", "<f4"), ("margin", "<f4")])
+assert ONSET_DTYPE.itemsize == C.sizeof(Onset) == 16 and C.sizeof(OnsetPickParams) == 40 and C.sizeof(TimingParams) == 48
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -204,6 +224,15 @@ SIGNATURES = {
     "mx_psola_synth_formant": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "mx_psola_render_formant": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, _vp]),
     "mx_psola_render_formant_dev": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, _vp]),
+    "mx_onset_flux_params_default": (None, [C.POINTER(OnsetFluxParams)]),
+    "mx_onset_flux_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, C.POINTER(OnsetFluxParams), _vp]),
+    "mx_onset_flux": (_i, [_vp, _vp, _i, _i, _i64, _i64, C.POINTER(OnsetFluxParams), _vp]),
+    "mx_onset_pick_params_default": (None, [C.POINTER(OnsetPickParams)]),
+    "mx_onset_pick": (_i, [_vp, _i64, _i, _i64, C.POINTER(OnsetPickParams), C.POINTER(_vp), C.POINTER(_i64)]),
+    "mx_onsets_detect": (_i, [_vp, _vp, _i, _i, C.POINTER(OnsetFluxParams), C.POINTER(OnsetPickParams), C.POINTER(_vp),
+                              C.POINTER(_i64)]),
+    "mx_timing_params_default": (None, [C.POINTER(TimingParams)]),
+    "mx_timing_markers": (_i, [_vp, _i64, _i64, _i, C.POINTER(TimingParams), _vp, _i, C.POINTER(_vp), C.POINTER(_i64)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

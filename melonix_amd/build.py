@@ -43,6 +43,8 @@ UNITS = [
     ("f0_decode.hip", "hip", ["-ffp-contract=off"]),
     # build-defined PSOLA overlap-add: the resampler's interpolation form, products rounded before the sums
     ("psola_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined onset strength: a 1024-point transform of its own on one wavefront (onset_core.h), every rounding as written
+    ("onset_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -53,10 +55,12 @@ UNITS = [
     ("capi_pyramid.cpp", "hip", []),
     ("capi_f0.cpp", "hip", []),
     ("capi_psola.cpp", "hip", []),
+    ("capi_onset.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
     ("psola_plan.cpp", "cxx", ["-ffp-contract=off"]),
+    ("onset_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

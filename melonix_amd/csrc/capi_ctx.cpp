@@ -209,6 +209,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
       hipFree(kv.second.wext);
     }
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
+    hipFree(ctx->onset_tw);
     for (auto &st : ctx->stage) st.drop();
     for (auto &st : ctx->chain) st.drop();
     for (auto &st : ctx->f0dec) st.drop();

@@ -207,13 +207,14 @@ struct mx_ctx {
   std::map<int, mx::NTables> tables;
   std::map<std::pair<int, int>, float *> wtabs;  // (N, hop) -> forward weights
   int frames_per_block = 0;  // 0 = per-N default
+  float2 *onset_tw = nullptr;  // the onset transform's twiddles (capi_onset.cpp), built on first use under mu
   std::mutex mu;
   // host landing zone of the zero-crossing bitmaps (mx_grains_dev), kept between calls: a copy into
   // pages that are already mapped runs at PCIe rate, a fresh 2 x n/8-byte buffer pays ~3 ms of faults
   std::mutex zc_mu;
   mx::ZcBitmaps zc_scratch;
   // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
-  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded), kept between calls.  One host-staged call per context at a time.
+  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux), kept between calls.  One host-staged call per context at a time.
   std::mutex stage_mu;
   mx::GrowBuf stage[mx::kStageSlots];
   // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)

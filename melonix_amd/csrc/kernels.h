@@ -198,6 +198,21 @@ using PsolaArgs = PsolaArgsT<mx_psola_grain>;
 using PsolaFormantArgs = PsolaArgsT<mx_psola_fgrain>;
 hipError_t launch_psola(const PsolaArgs &a, hipStream_t s);
 hipError_t launch_psola(const PsolaFormantArgs &a, hipStream_t s);
+// Build-defined onset strength (onset_kernels.hip; definition: include/melonix_amd.h).  Frame first_frame + f (f < count) is
+// centred on sample (first_frame + f) * hop; flux[f] its value.  lag in [1, 4], 1 <= kmin <= kmax <= 511: checked by the caller.
+struct OnsetArgs {
+  const float *audio;  // padded image (zeros in the pads)
+  int hop;
+  int64_t first_frame;
+  int64_t count;
+  int lag, kmin, kmax;
+  float compress;
+  const float2 *tw;  // W1024^j = e^{-2 pi i j/1024}, j < 1024
+  float *flux;
+  int run;  // consecutive frames per wavefront; 0: the default.  The output does not depend on it
+};
+int onset_default_run(int64_t count);
+hipError_t launch_onset_flux(const OnsetArgs &a, hipStream_t s);
 // spec-cache.cpp:77-96 colormap: nbins_total magnitudes -> 3*nbins_total bytes (both device).
 hipError_t launch_colormap(const float *mags, uint8_t *rgb, int64_t nbins_total, float k, hipStream_t s);
 

@@ -1,0 +1,198 @@
+"""mx_onset_flux / mx_onset_flux_dev / mx_onsets_detect on the GPU against tests/onset_ref.py (include/melonix_amd.h "Onset
+detection and tempo-grid timing markers"): the onset strength within the project's f32-versus-f64 yardstick, the same bytes
+whatever the launch split or the run length, the edges of n, hop, lag and band, the picks, and what a bad call may touch."""
+import numpy as np
+import pytest
+
+import onset_ref as R
+from conftest import DevBuf
+
+pytestmark = pytest.mark.gpu
+
+SR, HOP = R.SR, R.HOP
+
+
+def flux_tol(ref):
+    """The project's f32-versus-f64 yardstick (conftest.mag_tol), on the curve's own maximum."""
+    return 2e-5 * np.abs(ref).max() + 1e-9
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """name -> (samples, expected onset samples, reference flux): computed once, read by every test."""
+    out = {}
+    for name, (w, exp) in R.signals().items():
+        ref = R.flux(w, SR, HOP)
+        ref.setflags(write=False)
+        out[name] = (w, exp, ref)
+    return out
+
+
+@pytest.fixture(scope="module")
+def gpu_flux(gpu_ctx, cases):
+    """name -> the GPU's flux of the whole signal (host form, defaults)."""
+    out = {}
+    for name, (w, _, _) in cases.items():
+        a = gpu_ctx.upload(w)
+        try:
+            out[name] = gpu_ctx.onset_flux(a, SR, HOP)
+        finally:
+            a.free()
+    return out
+
+
+def _dev_flux(ctx, a, sr, hop, first, count, **params):
+    buf = DevBuf(max(count, 1) * 4, fill=0xA5)
+    try:
+        ctx.onset_flux_dev(a, sr, hop, first, count, buf.ptr, **params)
+        ctx.synchronize()
+        return buf.read(np.float32, count=count)
+    finally:
+        buf.free()
+
+
+def test_flux_against_the_reference(mxlib, cases, gpu_flux):
+    assert mxlib.onset_flux_params_default() == R.FLUX_DEFAULTS
+    worst = 0.0
+    for name, (w, _, ref) in cases.items():
+        got = gpu_flux[name]
+        assert got.shape == ref.shape and np.all(np.isfinite(got)) and np.all(got >= 0)
+        err, tol = np.abs(got - ref).max(), flux_tol(ref)
+        worst = max(worst, err / tol)
+        print(f"{name}: max|flux| {ref.max():.3f}  worst error {err:.3e}  bound {tol:.3e}")
+        assert err <= tol, name
+    print(f"worst error / bound over the six signals: {worst:.4f}")
+
+
+def test_same_bytes_whatever_the_split_or_the_run(gpu_ctx, cases, gpu_flux):
+    w = cases["notes5"][0]
+    whole = gpu_flux["notes5"]
+    count = len(whole)
+    a = gpu_ctx.upload(w)
+    try:
+        one = _dev_flux(gpu_ctx, a, SR, HOP, 0, count)
+        assert one.tobytes() == whole.tobytes()  # the host form is the device form
+        head, tail = _dev_flux(gpu_ctx, a, SR, HOP, 0, 37), _dev_flux(gpu_ctx, a, SR, HOP, 37, count - 37)
+        assert np.concatenate([head, tail]).tobytes() == whole.tobytes()  # split at 37: no multiple of any run length
+        assert _dev_flux(gpu_ctx, a, SR, HOP, 5, 1).tobytes() == whole[5:6].tobytes()
+        assert gpu_ctx.onset_flux(a, SR, HOP, 5, 1).tobytes() == whole[5:6].tobytes()
+        for lag in (2, 4):
+            ref = gpu_ctx.onset_flux(a, SR, HOP, lag=lag)
+            try:
+                for run in (1, 5, 32):
+                    gpu_ctx.set_frames_per_block(run)
+                    assert gpu_ctx.onset_flux(a, SR, HOP, lag=lag).tobytes() == ref.tobytes(), (lag, run)
+                    assert gpu_ctx.onset_flux(a, SR, HOP, 41, 23, lag=lag).tobytes() == ref[41:64].tobytes(), (lag, run)
+            finally:
+                gpu_ctx.set_frames_per_block(0)
+    finally:
+        a.free()
+
+
+def test_silence_gives_exact_zeros(gpu_ctx):
+    a = gpu_ctx.upload(np.zeros(20000, dtype=np.float32))
+    try:
+        for lag in (1, 4):
+            got = gpu_ctx.onset_flux(a, SR, HOP, lag=lag)
+            assert len(got) == 79 and got.tobytes() == bytes(4 * 79)
+        on = gpu_ctx.onsets_detect(a, SR, HOP)
+        assert len(on) == 0
+    finally:
+        a.free()
+
+
+@pytest.mark.parametrize("n,hop", [(1, 256), (255, 256), (3 * 256 - 1, 256), (3 * 256 + 1, 256), (300, 1), (2000, 255),
+                                   (16384 * 2 + 1, 16384), (40000, 16384)])
+def test_short_inputs_and_hops(gpu_ctx, n, hop):
+    rng = np.random.default_rng(n + hop)
+    t = np.arange(n)
+    w = (0.3 * np.sin(2 * np.pi * 440.0 * t / SR) * (t > n // 2) + 0.01 * rng.standard_normal(n)).astype(np.float32)
+    ref = R.flux(w, SR, hop)
+    a = gpu_ctx.upload(w)
+    try:
+        got = gpu_ctx.onset_flux(a, SR, hop)
+        assert len(got) == len(ref) == -(-n // hop)
+        assert np.abs(got - ref).max() <= flux_tol(ref)
+        if len(got) > 2:
+            assert gpu_ctx.onset_flux(a, SR, hop, len(got) - 2, 2).tobytes() == got[-2:].tobytes()
+    finally:
+        a.free()
+
+
+@pytest.mark.parametrize("lag", [1, 2, 3, 4])
+def test_lags_and_a_band_at_44100(gpu_ctx, cases, lag):
+    w = cases["notes30"][0][:SR]
+    a = gpu_ctx.upload(w)
+    try:
+        for sr, fmin, fmax in ((SR, 0.0, 0.0), (44100, 100.0, 5000.0)):
+            ref = R.flux(w, sr, HOP, lag=lag, fmin=fmin, fmax=fmax)
+            got = gpu_ctx.onset_flux(a, sr, HOP, lag=lag, fmin=fmin, fmax=fmax)
+            assert np.abs(got - ref).max() <= flux_tol(ref), (sr, lag)
+        assert R.band(44100, 100.0, 5000.0) == (3, 116)
+        # another compression: the curve scales with it, the bound with the curve
+        ref = R.flux(w, SR, HOP, lag=lag, compress=7.5)
+        assert np.abs(gpu_ctx.onset_flux(a, SR, HOP, lag=lag, compress=7.5) - ref).max() <= flux_tol(ref)
+    finally:
+        a.free()
+
+
+def test_picks(mxlib, gpu_ctx, cases, gpu_flux):
+    for name, (w, exp, ref) in cases.items():
+        # the guard — a condition on the reference alone: no decision of the picker lies close enough to its threshold for an
+        # error of the size the flux test allows to flip it
+        frames, margins = R.candidate_margins(ref)
+        assert len(margins) and np.abs(margins).min() > 100 * flux_tol(ref), (name, np.abs(margins).min())
+        want = R.pick(ref, HOP)
+        got = mxlib.onset_pick(gpu_flux[name], HOP)
+        assert [int(o["frame"]) for o in got] == [p[1] for p in want], name
+        assert [int(o["sample"]) for o in got] == [p[1] * HOP for p in want]
+        picked = [int(o["frame"]) for o in got]
+        assert len(picked) == len(exp), (name, picked)
+        if name == "clicks":
+            assert picked == [c // HOP for c in exp]
+        for f, s in zip(picked, exp):
+            assert abs(f - round(s / HOP)) <= 2, (name, f, s)
+        # flux and picks in one call
+        a = gpu_ctx.upload(w)
+        try:
+            assert gpu_ctx.onsets_detect(a, SR, HOP).tobytes() == got.tobytes()
+        finally:
+            a.free()
+    assert all(len(cases[k][1]) == 0 for k in ("vibrato", "noise")) and len(cases["notes5"][1]) == 6
+
+
+def test_guard_bands_and_refusals(mxlib, gpu_ctx, cases):
+    w = cases["clicks"][0]
+    count, G = 200, 64
+    a = gpu_ctx.upload(w)
+    buf = DevBuf((count + 2 * G) * 4, fill=0xA5)
+    try:
+        for first, cnt in ((0, count), (363, count), (100, 1)):
+            gpu_ctx.onset_flux_dev(a, SR, HOP, first, cnt, buf.ptr + G * 4, lag=4)
+            gpu_ctx.synchronize()
+            raw = buf.read(np.uint8)
+            assert np.all(raw[:G * 4] == 0xA5) and np.all(raw[(G + cnt) * 4:] == 0xA5), (first, cnt)
+            assert np.all(np.isfinite(raw[G * 4:(G + cnt) * 4].view(np.float32)))
+            buf.write(np.full(buf.nbytes, 0xA5, dtype=np.uint8))
+        frames = mxlib.frame_count(len(w), HOP)
+        bad = [dict(sr=0), dict(hop=0), dict(hop=16385), dict(first=-1), dict(count=-1), dict(first=frames, count=1),
+               dict(first=0, count=frames + 1), dict(compress=0.0), dict(compress=-1.0), dict(compress=float("nan")),
+               dict(compress=2e6), dict(lag=0), dict(lag=5), dict(fmin=-1.0), dict(fmax=float("inf")), dict(fmin=5000.0, fmax=100.0),
+               dict(fmin=1.0, fmax=40.0), dict(fmin=30000.0)]
+        for kw in bad:
+            kw = dict(kw)
+            args = dict(sr=kw.pop("sr", SR), hop=kw.pop("hop", HOP), first=kw.pop("first", 0), count=kw.pop("count", 10))
+            with pytest.raises(mxlib.MxError) as e:
+                gpu_ctx.onset_flux_dev(a, args["sr"], args["hop"], args["first"], args["count"], buf.ptr + G * 4, **kw)
+            assert e.value.code == -1, (kw, e.value)
+        with pytest.raises(mxlib.MxError) as e:
+            gpu_ctx.onset_flux_dev(a, SR, HOP, 0, 10, 0)  # a null output
+        assert e.value.code == -1
+        with pytest.raises(mxlib.MxError):
+            gpu_ctx.onsets_detect(a, SR, HOP, pick_params=dict(wait=-1))
+        gpu_ctx.synchronize()
+        assert np.all(buf.read(np.uint8) == 0xA5)  # refused before any launch
+        gpu_ctx.onset_flux_dev(a, SR, HOP, 0, 0, 0)  # no frames: nothing to do, nothing to write
+    finally:
+        buf.free()
+        a.free()
