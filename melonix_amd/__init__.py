@@ -50,6 +50,57 @@ def _take_records(p, count: int, dtype):
     return out
 
 
+# the parameter blocks of the build-defined entry points: kind -> (its ctypes struct, the entry point that writes its defaults)
+_PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "note": (_capi.NoteParams, "mx_note_params_default"),
+           "psola": (_capi.PsolaParams, "mx_psola_params_default"), "flux": (_capi.OnsetFluxParams, "mx_onset_flux_params_default"),
+           "pick": (_capi.OnsetPickParams, "mx_onset_pick_params_default"), "timing": (_capi.TimingParams, "mx_timing_params_default")}
+
+
+def _params_default(kind: str) -> dict:
+    struct, fn = _PARAMS[kind]
+    p = struct()
+    getattr(_capi.lib(), fn)(C.byref(p))
+    return {k: getattr(p, k) for k, _ in struct._fields_}
+
+
+def _params_arg(kind: str, params: dict, never_null: bool = False):
+    """The defaults with `params` over them, each value as its field's type (int or float), for the C-ABI; nothing given:
+    NULL, the library's defaults (never_null: the defaults as a struct, for an entry point that refuses NULL)."""
+    if not params and not never_null:
+        return None
+    d = _params_default(kind)
+    unknown = set(params) - set(d)
+    if unknown:
+        raise TypeError(f"unknown {kind} parameters {sorted(unknown)}")
+    d.update(params)
+    struct = _PARAMS[kind][0]
+    return C.byref(struct(**{k: (float if t in (C.c_float, C.c_double) else int)(d[k]) for k, t in struct._fields_}))
+
+
+def f0_decode_params_default() -> dict:
+    return _params_default("decode")
+
+
+def note_params_default() -> dict:
+    return _params_default("note")
+
+
+def psola_params_default() -> dict:
+    return _params_default("psola")
+
+
+def onset_flux_params_default() -> dict:
+    return _params_default("flux")
+
+
+def onset_pick_params_default() -> dict:
+    return _params_default("pick")
+
+
+def timing_params_default() -> dict:
+    return _params_default("timing")
+
+
 def pitch_band(N: int, sr: int = 48000):
     a, b = C.c_int(), C.c_int()
     _capi.lib().mx_pitch_band(N, sr, C.byref(a), C.byref(b))
@@ -309,14 +360,14 @@ class Context:
             raise ValueError("one row of candidates per frame of the track")
         out = np.empty(len(track), dtype=F0_DTYPE)
         state = np.empty(len(track), dtype=np.uint8)
-        _capi.check(_capi.lib().mx_f0_decode(self.handle, _ptr(track), _ptr(cands), len(track), _decode_params(params),
+        _capi.check(_capi.lib().mx_f0_decode(self.handle, _ptr(track), _ptr(cands), len(track), _params_arg("decode", params),
                                              _ptr(out), _ptr(state)))
         return out, state
 
     def f0_decode_dev(self, d_track: int, d_cands: int, count: int, d_out: int, d_state: int | None = None, **params):
         """Device pointers (d_out may be d_track; d_state None: not wanted); asynchronous on the context's stream."""
         _capi.check(_capi.lib().mx_f0_decode_dev(self.handle, C.c_void_p(d_track or 0), C.c_void_p(d_cands or 0), count,
-                                                 _decode_params(params), C.c_void_p(d_out or 0), C.c_void_p(d_state or 0)))
+                                                 _params_arg("decode", params), C.c_void_p(d_out or 0), C.c_void_p(d_state or 0)))
 
     def f0_track_decoded(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
                          fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD, **params):
@@ -324,7 +375,7 @@ class Context:
         count = _frames_from(audio, hop, first, count)
         out = np.empty(max(count, 0), dtype=F0_DTYPE)
         _capi.check(_capi.lib().mx_f0_track_decoded(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
-                                                    _decode_params(params), _ptr(out)))
+                                                    _params_arg("decode", params), _ptr(out)))
         return out
 
     def f0_decode_set_chunk(self, frames: int):
@@ -337,19 +388,19 @@ class Context:
         onset_flux_params_default()."""
         count = _frames_from(audio, hop, first, count)
         out = np.empty(max(count, 0), dtype=np.float32)
-        _capi.check(_capi.lib().mx_onset_flux(self.handle, audio.handle, sr, hop, first, count, _flux_params(params), _ptr(out)))
+        _capi.check(_capi.lib().mx_onset_flux(self.handle, audio.handle, sr, hop, first, count, _params_arg("flux", params), _ptr(out)))
         return out
 
     def onset_flux_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_flux: int, **params):
         """The values stay in HBM at d_flux (count x 4 bytes); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_onset_flux_dev(self.handle, audio.handle, sr, hop, first, count, _flux_params(params),
+        _capi.check(_capi.lib().mx_onset_flux_dev(self.handle, audio.handle, sr, hop, first, count, _params_arg("flux", params),
                                                   C.c_void_p(d_flux or 0)))
 
     def onsets_detect(self, audio: Audio, sr: int, hop: int = 256, flux_params: dict | None = None, pick_params: dict | None = None):
         """Flux over the whole file and the picks from it -> ONSET_DTYPE array."""
         out, cnt = C.c_void_p(), C.c_int64()
-        _capi.check(_capi.lib().mx_onsets_detect(self.handle, audio.handle, sr, hop, _flux_params(flux_params or {}),
-                                                 _pick_params(pick_params or {}), C.byref(out), C.byref(cnt)))
+        _capi.check(_capi.lib().mx_onsets_detect(self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
+                                                 _params_arg("pick", pick_params or {}), C.byref(out), C.byref(cnt)))
         return _take_records(out, cnt.value, ONSET_DTYPE)
 
     # ---- grains / resynthesis ----
@@ -441,7 +492,7 @@ class Context:
         sfx, _, pts = _psola_kind(formant, points)
         f32, i16 = _pcm_pair(_render_length(audio.n, sr, m, len(markers)), want_f32, want_i16)
         _capi.check(getattr(_capi.lib(), "mx_psola_render" + sfx)(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
-                                                                  len(track), _psola_params(params), m, len(markers),
+                                                                  len(track), _params_arg("psola", params), m, len(markers),
                                                                   *_points_args(pts), _ptr(f32), _ptr(i16)))
         return f32, i16
 
@@ -645,51 +696,14 @@ def column_range(markers, sr, time, width, range_time):
 
 
 # ---- notes and correction markers (host; build-defined) ----
-def f0_decode_params_default() -> dict:
-    p = _capi.F0DecodeParams()
-    _capi.lib().mx_f0_decode_params_default(C.byref(p))
-    return {k: getattr(p, k) for k, _ in _capi.F0DecodeParams._fields_}
-
-
-def _decode_params(params: dict):
-    """The defaults with `params` over them, for the C-ABI; nothing given: NULL (the library's defaults)."""
-    if not params:
-        return None
-    d = f0_decode_params_default()
-    unknown = set(params) - set(d)
-    if unknown:
-        raise TypeError(f"unknown decode parameters {sorted(unknown)}")
-    d.update(params)
-    return C.byref(_capi.F0DecodeParams(float(d["unvoiced_cost"]), float(d["jump_cost"]), float(d["switch_cost"]),
-                                        int(d["max_jump_cents"])))
-
-
-def note_params_default() -> dict:
-    p = _capi.NoteParams()
-    _capi.lib().mx_note_params_default(C.byref(p))
-    return {k: getattr(p, k) for k, _ in _capi.NoteParams._fields_}
-
-
 def detect_notes(track, sr: int, hop: int, first: int = 0, **params):
     """Notes of an F0_DTYPE track (track[0] = frame `first`) -> NOTE_DTYPE array.  params: threshold, rms_floor, max_jump,
     max_dev, min_frames (defaults: note_params_default())."""
     track = np.ascontiguousarray(track, dtype=F0_DTYPE)
-    p = _capi.NoteParams()
-    _capi.lib().mx_note_params_default(C.byref(p))
-    for k, v in params.items():
-        if k not in dict(_capi.NoteParams._fields_):
-            raise TypeError(f"unknown note parameter {k!r}")
-        setattr(p, k, v)
     out, cnt = C.POINTER(_capi.Note)(), C.c_int64()
-    _capi.check(_capi.lib().mx_detect_notes(_ptr(track) if len(track) else None, len(track), sr, hop, first, C.byref(p),
-                                            C.byref(out), C.byref(cnt)))
-    if not cnt.value:
-        _capi.lib().mx_free(out)
-        return np.zeros(0, NOTE_DTYPE)
-    buf = (C.c_char * (cnt.value * NOTE_DTYPE.itemsize)).from_address(C.addressof(out.contents))
-    notes = np.frombuffer(bytes(buf), dtype=NOTE_DTYPE).copy()
-    _capi.lib().mx_free(out)
-    return notes
+    _capi.check(_capi.lib().mx_detect_notes(_ptr(track) if len(track) else None, len(track), sr, hop, first,
+                                            _params_arg("note", params, never_null=True), C.byref(out), C.byref(cnt)))
+    return _take_records(C.cast(out, C.c_void_p), cnt.value, NOTE_DTYPE)  # (no notes: a null array)
 
 
 def correction_markers(notes, strength: float = 1.0, scale_mask: int = 0):
@@ -702,24 +716,6 @@ def correction_markers(notes, strength: float = 1.0, scale_mask: int = 0):
 
 
 # ---- PSOLA planning (host; build-defined) ----
-def psola_params_default() -> dict:
-    p = _capi.PsolaParams()
-    _capi.lib().mx_psola_params_default(C.byref(p))
-    return {k: getattr(p, k) for k, _ in _capi.PsolaParams._fields_}
-
-
-def _psola_params(params: dict):
-    """The defaults with `params` over them, for the C-ABI; nothing given: NULL (the library's defaults)."""
-    if not params:
-        return None
-    d = psola_params_default()
-    unknown = set(params) - set(d)
-    if unknown:
-        raise TypeError(f"unknown PSOLA parameters {sorted(unknown)}")
-    d.update(params)
-    return C.byref(_capi.PsolaParams(float(d["threshold"]), float(d["rms_floor"]), float(d["unvoiced_period"])))
-
-
 def _formant_points(points):
     """(sample, semitones) pairs, or a FORMANT_POINT_DTYPE array -> a contiguous FORMANT_POINT_DTYPE array."""
     if isinstance(points, np.ndarray) and points.dtype == FORMANT_POINT_DTYPE:
@@ -752,7 +748,7 @@ def _psola_plan(formant: bool, n: int, sr: int, hop: int, track, markers, points
     sfx, dtype, pts = _psola_kind(formant, points)
     out, cnt, ns = C.c_void_p(), C.c_int64(), C.c_int64()
     _capi.check(getattr(_capi.lib(), "mx_psola_plan" + sfx)(n, sr, hop, _ptr(track) if len(track) else None, len(track),
-                                                            _psola_params(params), m, len(markers), *_points_args(pts),
+                                                            _params_arg("psola", params), m, len(markers), *_points_args(pts),
                                                             C.byref(out), C.byref(cnt), C.byref(ns)))
     return _take_records(out, cnt.value, dtype), ns.value
 
@@ -770,50 +766,12 @@ def psola_plan_formant(n: int, sr: int, hop: int, track, markers, points, **para
 
 
 # ---- onsets and timing markers (host; build-defined) ----
-def _params_default(kind, fn: str) -> dict:
-    p = kind()
-    getattr(_capi.lib(), fn)(C.byref(p))
-    return {k: getattr(p, k) for k, _ in kind._fields_}
-
-
-def _params_arg(kind, fn: str, params: dict):
-    """The defaults with `params` over them, for the C-ABI; nothing given: NULL (the library's defaults)."""
-    if not params:
-        return None
-    d = _params_default(kind, fn)
-    unknown = set(params) - set(d)
-    if unknown:
-        raise TypeError(f"unknown parameters {sorted(unknown)}")
-    d.update(params)
-    return C.byref(kind(**d))
-
-
-def onset_flux_params_default() -> dict:
-    return _params_default(_capi.OnsetFluxParams, "mx_onset_flux_params_default")
-
-
-def onset_pick_params_default() -> dict:
-    return _params_default(_capi.OnsetPickParams, "mx_onset_pick_params_default")
-
-
-def timing_params_default() -> dict:
-    return _params_default(_capi.TimingParams, "mx_timing_params_default")
-
-
-def _flux_params(params: dict):
-    return _params_arg(_capi.OnsetFluxParams, "mx_onset_flux_params_default", params)
-
-
-def _pick_params(params: dict):
-    return _params_arg(_capi.OnsetPickParams, "mx_onset_pick_params_default", params)
-
-
 def onset_pick(flux, hop: int, first: int = 0, **params):
     """Onsets of an onset-strength curve (flux[0] = frame `first`) -> ONSET_DTYPE array.  params: fields of
     onset_pick_params_default()."""
     flux = np.ascontiguousarray(flux, dtype=np.float32)
     out, cnt = C.c_void_p(), C.c_int64()
-    _capi.check(_capi.lib().mx_onset_pick(_ptr(flux) if len(flux) else None, len(flux), hop, first, _pick_params(params),
+    _capi.check(_capi.lib().mx_onset_pick(_ptr(flux) if len(flux) else None, len(flux), hop, first, _params_arg("pick", params),
                                           C.byref(out), C.byref(cnt)))
     return _take_records(out, cnt.value, ONSET_DTYPE)
 
@@ -832,6 +790,6 @@ def timing_markers(anchors, n: int, sr: int, base=None, **params):
     base = np.ascontiguousarray(base)
     out, cnt = C.c_void_p(), C.c_int64()
     _capi.check(_capi.lib().mx_timing_markers(_ptr(anchors) if len(anchors) else None, len(anchors), int(n), sr,
-                                              _params_arg(_capi.TimingParams, "mx_timing_params_default", params),
+                                              _params_arg("timing", params),
                                               _ptr(base) if len(base) else None, len(base), C.byref(out), C.byref(cnt)))
     return _take_records(out, cnt.value, MARKER_DTYPE)

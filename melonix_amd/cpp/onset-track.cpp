@@ -2,46 +2,26 @@
 // vectors, the way the rest of the facade maps errors.
 #include "onset-track.hpp"
 
-namespace melonix {
+#include "capi-glue.hpp"
 
-static_assert(sizeof(Marker) == sizeof(mx_marker), "Marker must stay layout-compatible with mx_marker");
+namespace melonix {
 
 OnsetTrack::OnsetTrack(std::span<const float> wav, int sampleRate, int hop, int device)
     : sampleRate(sampleRate), hop_(hop), n_((int64_t)wav.size()) {
-  mx_ctx *ctx = nullptr;
-  if (mx_ctx_create(device, &ctx) != MX_OK) return;
-  mx_audio *audio = nullptr;
-  if (mx_audio_upload(ctx, wav.data(), (int64_t)wav.size(), &audio) == MX_OK) {
-    const int64_t frames = mx_frame_count((int64_t)wav.size(), hop);
-    if (frames >= 0) {
-      flux_.resize((size_t)frames);
-      good = mx_onset_flux(ctx, audio, sampleRate, hop, 0, frames, nullptr, flux_.data()) == MX_OK;
-      if (!good) flux_.clear();
-    }
-    mx_audio_free(ctx, audio);
-  }
-  mx_ctx_destroy(ctx);
+  good = glue::fileTrack(wav, hop, device, flux_, [&](mx_ctx *ctx, const mx_audio *audio, int64_t frames, float *out) {
+    return mx_onset_flux(ctx, audio, sampleRate, hop, 0, frames, nullptr, out);
+  });
 }
 
-mx_onset_pick_params OnsetTrack::pickParams() {
-  mx_onset_pick_params p;
-  mx_onset_pick_params_default(&p);
-  return p;
-}
+mx_onset_pick_params OnsetTrack::pickParams() { return glue::defaults(mx_onset_pick_params_default); }
 
-mx_timing_params OnsetTrack::timingParams() {
-  mx_timing_params p;
-  mx_timing_params_default(&p);
-  return p;
-}
+mx_timing_params OnsetTrack::timingParams() { return glue::defaults(mx_timing_params_default); }
 
 std::vector<mx_onset> OnsetTrack::onsets(const mx_onset_pick_params &p) const {
   mx_onset *v = nullptr;
   int64_t n = 0;
   if (!good || mx_onset_pick(flux_.data(), (int64_t)flux_.size(), hop_, 0, &p, &v, &n) != MX_OK) return {};
-  std::vector<mx_onset> out(v, v + n);
-  mx_free(v);
-  return out;
+  return glue::taken<mx_onset>(v, n);
 }
 
 std::vector<Marker> OnsetTrack::timingMarkers(const mx_timing_params &p, const std::vector<Marker> &baseMarkers) const {
@@ -53,10 +33,7 @@ std::vector<Marker> OnsetTrack::timingMarkers(const mx_timing_params &p, const s
   if (mx_timing_markers(anchors.data(), (int64_t)anchors.size(), n_, sampleRate, &p,
                         reinterpret_cast<const mx_marker *>(baseMarkers.data()), (int)baseMarkers.size(), &v, &n) != MX_OK)
     return {};
-  const Marker *m = reinterpret_cast<const Marker *>(v);
-  std::vector<Marker> out(m, m + n);
-  mx_free(v);
-  return out;
+  return glue::taken<Marker>(v, n);
 }
 
 }  // namespace melonix

@@ -1,11 +1,7 @@
 #include "resynth.hpp"
 
-#include <cstring>
-
-#include "melonix_amd.h"
+#include "capi-glue.hpp"
 #include "save-wav.hpp"
-
-static_assert(sizeof(Marker) == sizeof(mx_marker), "Marker must stay layout-compatible with mx_marker");
 
 namespace melonix {
 
@@ -24,12 +20,9 @@ Resynth::Resynth(std::span<const float> wav, int sampleRate, int device)
   float *f = nullptr;
   int64_t n = 0;
   if (mx_grain_table_dev(ctx, audio, &s, &l, &f, &n) == MX_OK) {
-    starts.assign(s, s + n);
-    lens.assign(l, l + n);
-    firsts.assign(f, f + n);
-    mx_free(s);
-    mx_free(l);
-    mx_free(f);
+    starts = glue::taken<int32_t>(s, n);
+    lens = glue::taken<int32_t>(l, n);
+    firsts = glue::taken<float>(f, n);
   }
 }
 

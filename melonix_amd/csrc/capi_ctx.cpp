@@ -38,22 +38,21 @@ int default_frames_per_block(int N, int mode, int hop, int64_t count) {
   return g;
 }
 
+void free_tables(NTables &t) {
+  for (void *p : {(void *)t.tw2, (void *)t.tw3, (void *)t.ubase, (void *)t.wext}) hipFree(p);
+  t = NTables{};
+}
+
+// all four tables of a plan, or none of them
 template <class P>
 int build_tables(NTables &t) {
-  constexpr int N = P::N;
-  const auto tw2 = make_tw2<P>();
-  const auto tw3 = make_tw3<P>();
-  const auto ub = make_ubase<P>();
-  HIP_TRY(hipMalloc(&t.tw2, tw2.size() * sizeof(float2)));
-  HIP_TRY(hipMalloc(&t.tw3, tw3.size() * sizeof(float2)));
-  HIP_TRY(hipMalloc(&t.ubase, ub.size() * sizeof(float2)));
-  HIP_TRY(hipMemcpy(t.tw2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t.tw3, tw3.data(), tw3.size() * sizeof(float2), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t.ubase, ub.data(), ub.size() * sizeof(float2), hipMemcpyHostToDevice));
-  t.wext_host = make_wext(fold_scale(N));
-  HIP_TRY(hipMalloc(&t.wext, t.wext_host.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(t.wext, t.wext_host.data(), t.wext_host.size() * sizeof(float), hipMemcpyHostToDevice));
-  return MX_OK;
+  t.wext_host = make_wext(fold_scale(P::N));
+  int rc = upload_table(make_tw2<P>(), &t.tw2);
+  if (rc == MX_OK) rc = upload_table(make_tw3<P>(), &t.tw3);
+  if (rc == MX_OK) rc = upload_table(make_ubase<P>(), &t.ubase);
+  if (rc == MX_OK) rc = upload_table(t.wext_host, &t.wext);
+  if (rc) free_tables(t);
+  return rc;
 }
 
 int get_tables(mx_ctx *ctx, int N, NTables &out) {
@@ -85,10 +84,8 @@ int get_wtab(mx_ctx *ctx, int N, int hop, const NTables &nt, const float **out) 
     *out = it->second;
     return MX_OK;
   }
-  const std::vector<float> w = make_wtab(N, hop, nt.wext_host);
   float *d = nullptr;
-  HIP_TRY(hipMalloc(&d, w.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(d, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (const int rc = upload_table(make_wtab(N, hop, nt.wext_host), &d)) return rc;
   ctx->wtabs[key] = d;
   *out = d;
   return MX_OK;
@@ -103,6 +100,24 @@ int check_common(mx_ctx *ctx, const mx_audio *a, int N, int64_t count, int &kmin
   kmin = std::max(kmin, 0);
   kmax = std::min(kmax, N / 2 - 1);
   if (kmin > kmax) return fail(MX_ERR_INVALID, "empty pitch band [%d,%d]", kmin, kmax);
+  return MX_OK;
+}
+
+int file_frames(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t &frames) {
+  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+  frames = (a->n + hop - 1) / hop;
+  return MX_OK;
+}
+
+int frame_span(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_frame, int64_t count, const void *out) {
+  int64_t frames = 0;
+  if (const int rc = file_frames(ctx, a, hop, frames)) return rc;
+  if (first_frame < 0 || count < 0) return fail(MX_ERR_INVALID, "negative frame range");
+  if (first_frame > frames || count > frames - first_frame)
+    return fail(MX_ERR_INVALID, "frames [%lld, %lld) outside the %lld frames of the file", (long long)first_frame,
+                (long long)(first_frame + count), (long long)frames);
+  if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
   return MX_OK;
 }
 
@@ -202,12 +217,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    for (auto &kv : ctx->tables) {
-      hipFree(kv.second.tw2);
-      hipFree(kv.second.tw3);
-      hipFree(kv.second.ubase);
-      hipFree(kv.second.wext);
-    }
+    for (auto &kv : ctx->tables) free_tables(kv.second);
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
     hipFree(ctx->onset_tw);
     for (auto &st : ctx->stage) st.drop();

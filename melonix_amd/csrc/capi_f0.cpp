@@ -33,21 +33,13 @@ struct F0Call {
   float threshold;
 };
 
-// out: the output the entry point cannot do without (null only where count is 0)
+// the frame span (frame_span: `out`) and what is the tracker's own: the threshold and the lag range
 int f0_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
              float fmax, float threshold, const void *out, F0Call &q) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-  if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
   if (!std::isfinite(threshold)) return fail(MX_ERR_INVALID, "threshold is not finite");
-  if (first_frame < 0 || count < 0) return fail(MX_ERR_INVALID, "negative frame range");
-  const int64_t frames = (a->n + hop - 1) / hop;
-  if (first_frame > frames || count > frames - first_frame)
-    return fail(MX_ERR_INVALID, "frames [%lld, %lld) outside the %lld frames of the file", (long long)first_frame,
-                (long long)(first_frame + count), (long long)frames);
   q = F0Call{ctx, a, sampleRate, hop, first_frame, count, 0, 0, threshold};
-  if (const int rc = f0_range(sampleRate, fmin, fmax, q.tmin, q.tmax)) return rc;
-  if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
-  return MX_OK;
+  return f0_range(sampleRate, fmin, fmax, q.tmin, q.tmax);
 }
 
 // d_cands set: the ladder instantiation (d_out may then be null)
@@ -75,10 +67,11 @@ int f0_launch(const F0Call &q, mx_f0 *d_out, mx_f0_cand *d_cands) {
 }
 
 const mx_f0_decode_params kDecodeDefaults{0.3f, 0.1f, 0.5f, 1200};
+const mx_note_params kNoteDefaults{0.15f, 1e-3f, 0.5, 0.75, 8};
 
 // the parameters in force (p null: the defaults), checked
 int decode_params(const mx_f0_decode_params *p, mx_f0_decode_params &out) {
-  out = p ? *p : kDecodeDefaults;
+  out = params_or(p, kDecodeDefaults);
   for (const float c : {out.unvoiced_cost, out.jump_cost, out.switch_cost})
     if (!std::isfinite(c) || c < 0.f || c > 16.f) return fail(MX_ERR_INVALID, "decode cost %g outside [0, 16]", (double)c);
   if (out.max_jump_cents < 0 || out.max_jump_cents > 12000)
@@ -124,41 +117,19 @@ int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, 
   return MX_OK;
 }
 
-// The host-pointer forms: the records pass through the context's staging buffers (the track — decoded in place — in the pitch
-// records', states in the texels' and, where the call has candidates (`ladder`), those in the magnitude rows').  `in`: upload
-// the caller's track and candidates; `run(d_track, d_cands, d_state)` queues the device form; the outputs that are set come
-// back.  Blocks.
+// The host-pointer forms (staged_records): the track — decoded in place — passes through the staging buffer of the pitch
+// records, the states through the texels' and, where the call has candidates (`ladder`), those through the magnitude rows'.
+// `in`: upload the caller's track and candidates; `run(d_track, d_cands, d_state)` queues the device form; the outputs that
+// are set come back.
 template <class F>
 int f0_staged(mx_ctx *ctx, int64_t count, bool ladder, const mx_f0 *track_in, const mx_f0_cand *cands_in, mx_f0 *track_out,
               mx_f0_cand *cands_out, uint8_t *state_out, F &&run) {
-  if (count == 0) return MX_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  const size_t n = (size_t)count;
-  std::lock_guard<std::mutex> lk(ctx->stage_mu);
-  mx_f0_cand *d_cands = nullptr;
-  mx_f0 *d_track = nullptr;
-  uint8_t *d_state = nullptr;
-  hipError_t e = ctx->stage[kStagePitch].get(n * sizeof(mx_f0), &d_track);
-  if (e == hipSuccess && ladder) e = ctx->stage[kStageMags].get(n * MX_F0_CANDS * sizeof(mx_f0_cand), &d_cands);
-  if (e == hipSuccess && state_out) e = ctx->stage[kStageTexels].get(n, &d_state);
-  int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
-  if (rc == MX_OK && track_in) e = hipMemcpyAsync(d_track, track_in, n * sizeof(mx_f0), hipMemcpyHostToDevice, ctx->stream);
-  if (rc == MX_OK && e == hipSuccess && cands_in)
-    e = hipMemcpyAsync(d_cands, cands_in, n * MX_F0_CANDS * sizeof(mx_f0_cand), hipMemcpyHostToDevice, ctx->stream);
-  if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "f0 upload: %s", hipGetErrorString(e));
-  if (rc == MX_OK) rc = run(d_track, d_cands, d_state);
-  if (rc == MX_OK) {
-    if (track_out) e = hipMemcpyAsync(track_out, d_track, n * sizeof(mx_f0), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && cands_out)
-      e = hipMemcpyAsync(cands_out, d_cands, n * MX_F0_CANDS * sizeof(mx_f0_cand), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && state_out) e = hipMemcpyAsync(state_out, d_state, n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "f0 download: %s", hipGetErrorString(e));
-  } else {
-    hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's memory: done before the call returns)
-  }
-  stage_trim(ctx);
-  return rc;
+  const StagedSlot slots[] = {{kStagePitch, sizeof(mx_f0), track_in, track_out},
+                              {kStageMags, ladder ? MX_F0_CANDS * sizeof(mx_f0_cand) : 0, cands_in, cands_out},
+                              {kStageTexels, state_out ? 1u : 0u, nullptr, state_out}};
+  return staged_records(ctx, count, slots, "f0", [&](void *const *d) {
+    return run(static_cast<mx_f0 *>(d[0]), static_cast<mx_f0_cand *>(d[1]), static_cast<uint8_t *>(d[2]));
+  });
 }
 
 }  // namespace
@@ -204,9 +175,7 @@ int mx_f0_candidates(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, in
 }
 
 void mx_f0_decode_params_default(mx_f0_decode_params *p) {
-  mx_guard_void([&] {
-    if (p) *p = kDecodeDefaults;
-  });
+  mx_guard_void([&] { params_default(p, kDecodeDefaults); });
 }
 
 int mx_f0_decode_dev(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, int64_t count,
@@ -253,9 +222,7 @@ int mx_f0_decode_set_chunk(mx_ctx *ctx, int64_t frames) {
 }
 
 void mx_note_params_default(mx_note_params *p) {
-  mx_guard_void([&] {
-    if (p) *p = mx_note_params{0.15f, 1e-3f, 0.5, 0.75, 8};
-  });
+  mx_guard_void([&] { params_default(p, kNoteDefaults); });
 }
 
 int mx_detect_notes(const mx_f0 *track, int64_t count, int sampleRate, int hop, int64_t first_frame,
@@ -269,13 +236,7 @@ int mx_detect_notes(const mx_f0 *track, int64_t count, int sampleRate, int hop, 
     if (p.min_frames < 2) return fail(MX_ERR_INVALID, "min_frames %d < 2", p.min_frames);
     if (!std::isfinite(p.threshold) || !std::isfinite(p.rms_floor) || !(p.max_jump >= 0.0) || !(p.max_dev >= 0.0))
       return fail(MX_ERR_INVALID, "note parameters must be finite, the deviations >= 0");
-    const std::vector<mx_note> v = detect_notes(track, count, sampleRate, hop, first_frame, p);
-    HandOver h;
-    if (v.empty()) *notes = nullptr;  // (no notes: no array)
-    else h.add(notes, v.data(), v.size());
-    if (const int rc = h.give()) return rc;
-    *nnotes = (int64_t)v.size();
-    return MX_OK;
+    return hand_over(detect_notes(track, count, sampleRate, hop, first_frame, p), notes, nnotes, /*null_if_empty=*/true);
   });
 }
 

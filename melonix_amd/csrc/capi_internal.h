@@ -1,7 +1,9 @@
 // capi_internal.h — what the units of the C-ABI implementation (capi_*.cpp) share: the context and audio handle
 // types, the error slot behind mx_last_error, the per-N table cache, and the sequences written once: the owners of device
 // memory (DeviceArray for a call, GrowBuf for a context), the chunked host-staged loop (staged_batch), the PCM download
-// (pcm_to_host), the arrays handed out for mx_free (HandOver), the MELONIX_TIMING phase clock (PhaseClock).
+// (pcm_to_host), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING phase clock (PhaseClock); and for
+// the per-frame tracks (f0, onset strength): the frame-span check (frame_span), the staged host form (staged_records), the
+// parameters in force and their defaults (params_or, params_default), the device tables built on the host (upload_table).
 // Not installed; include/melonix_amd.h is the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -178,6 +180,38 @@ class HandOver {
     return MX_OK;
   }
 };
+// the records of `v` as one such array at *out, their number at *nout (`null_if_empty`: no records, no array)
+template <class T>
+int hand_over(const std::vector<T> &v, T **out, int64_t *nout, bool null_if_empty = false) {
+  HandOver h;
+  if (null_if_empty && v.empty()) *out = nullptr;
+  else h.add(out, v.data(), v.size());
+  if (const int rc = h.give()) return rc;
+  *nout = (int64_t)v.size();
+  return MX_OK;
+}
+
+// the parameters in force: the caller's or, p null, the defaults; and the body of every mx_*_params_default
+template <class P>
+P params_or(const P *p, const P &defaults) { return p ? *p : defaults; }
+template <class P>
+void params_default(P *p, const P &defaults) { if (p) *p = defaults; }
+
+// A table built on the host as device memory at *out (D: the device's name for T, float2 for cpx_h); nothing is left allocated
+// where it fails.
+template <class T, class D>
+int upload_table(const std::vector<T> &host, D **out) {
+  static_assert(sizeof(T) == sizeof(D), "the device reads the host's elements as they are");
+  D *d = nullptr;
+  hipError_t e = hipMalloc(&d, host.size() * sizeof(T));
+  if (e == hipSuccess) e = hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    hipFree(d);
+    return fail(MX_ERR_DEVICE, "table upload: %s", hipGetErrorString(e));
+  }
+  *out = d;
+  return MX_OK;
+}
 
 // MELONIX_TIMING: the phases of one call, for the one line it prints on stderr.  mark() ends a phase; ms(i) is the length of
 // phase i — up to now for the one still running, 0 for one the call never reached.
@@ -249,6 +283,11 @@ int default_frames_per_block(int N, int mode, int hop, int64_t count);
 int get_tables(mx_ctx *ctx, int N, NTables &out);
 int get_wtab(mx_ctx *ctx, int N, int hop, const NTables &nt, const float **out);
 int check_common(mx_ctx *ctx, const mx_audio *a, int N, int64_t count, int &kmin, int &kmax);
+// What the per-frame track entry points (f0, onset strength) check of a frame span: the handles, hop in [1, 16384] — file_frames,
+// which gives the ceil(n / hop) frames of the file —, [first_frame, first_frame + count) inside them, and `out`, the output the
+// entry point cannot do without, null only where count is 0.  (The STFT's hop mode keeps stft_hop_check: other rules.)
+int file_frames(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t &frames);
+int frame_span(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_frame, int64_t count, const void *out);
 int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_t first_frame, const int32_t *d_ranges,
                 int64_t count, int kmin, int kmax, float *d_mags, mx_pitch *d_pitch, uint8_t *d_rgb, float cmap_k,
                 int run_length = 0);
@@ -328,6 +367,43 @@ int pcm_to_host(mx_ctx *ctx, int64_t n, float *f_out, int16_t *i_out, F &&to_dev
   if (e == hipSuccess) e = i.download(i_out);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "PCM download: %s", hipGetErrorString(e));
+}
+
+// One kind of per-frame record of a staged call: the staging buffer it passes through, its bytes per frame (0: the call has no
+// such records, the device pointer is null), the caller's records to upload and the caller's room for the result, each or null.
+struct StagedSlot {
+  StageSlot slot;
+  size_t frame_bytes;
+  const void *in;
+  void *out;
+};
+// The host-pointer form of a per-frame track entry point: `count` frames of every slot pass through the context's staging
+// buffers, held (stage_mu) for the whole call.  `run(d) -> status` queues the device form on the context's stream, d[i] the
+// device records of slot i; the results come back only if it succeeded.  `what` names the call in a device error.  Blocks, on
+// the failure path too: the uploads read the caller's memory.
+template <size_t K, class F>
+int staged_records(mx_ctx *ctx, int64_t count, const StagedSlot (&slots)[K], const char *what, F &&run) {
+  if (count == 0) return MX_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> lk(ctx->stage_mu);
+  void *d[K] = {};
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; i < K && e == hipSuccess; ++i)
+    if (slots[i].frame_bytes) e = ctx->stage[slots[i].slot].get((size_t)count * slots[i].frame_bytes, &d[i]);
+  int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
+  for (size_t i = 0; i < K && rc == MX_OK && e == hipSuccess; ++i)
+    if (d[i] && slots[i].in)
+      e = hipMemcpyAsync(d[i], slots[i].in, (size_t)count * slots[i].frame_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "%s upload: %s", what, hipGetErrorString(e));
+  if (rc == MX_OK) rc = run(d);
+  for (size_t i = 0; i < K && rc == MX_OK && e == hipSuccess; ++i)
+    if (d[i] && slots[i].out)
+      e = hipMemcpyAsync(slots[i].out, d[i], (size_t)count * slots[i].frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (rc == MX_OK && e == hipSuccess) e = es;
+  if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "%s download: %s", what, hipGetErrorString(e));
+  stage_trim(ctx);
+  return rc;
 }
 
 }  // namespace mx

@@ -22,18 +22,12 @@ struct FluxCall {
   int kmin, kmax;
 };
 
-// out: the output the entry point cannot do without (null only where count is 0)
+// the frame span (frame_span: `out`) and what is the detector's own: the sample rate, the flux parameters and their band
 int flux_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                const mx_onset_flux_params *params, const void *out, FluxCall &q) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
   if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
-  if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
-  if (first_frame < 0 || count < 0) return fail(MX_ERR_INVALID, "negative frame range");
-  const int64_t frames = (a->n + hop - 1) / hop;
-  if (first_frame > frames || count > frames - first_frame)
-    return fail(MX_ERR_INVALID, "frames [%lld, %lld) outside the %lld frames of the file", (long long)first_frame,
-                (long long)(first_frame + count), (long long)frames);
-  q = FluxCall{ctx, a, hop, first_frame, count, params ? *params : kFluxDefaults, 0, 0};
+  q = FluxCall{ctx, a, hop, first_frame, count, params_or(params, kFluxDefaults), 0, 0};
   const mx_onset_flux_params &p = q.p;
   if (!std::isfinite(p.compress) || !(p.compress > 0.f) || p.compress > 1e6f)
     return fail(MX_ERR_INVALID, "compress %g outside (0, 1e6]", (double)p.compress);
@@ -45,7 +39,6 @@ int flux_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t 
   q.kmax = (int)std::min(511.0, std::floor(fmax * 1024.0 / sr));
   if (q.kmin > q.kmax)
     return fail(MX_ERR_INVALID, "empty band [%d, %d] for %g..%g Hz at %d Hz", q.kmin, q.kmax, (double)p.fmin, fmax, sampleRate);
-  if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
   return MX_OK;
 }
 
@@ -58,14 +51,7 @@ int onset_table(mx_ctx *ctx, const float2 **out) {
       const double ang = -2.0 * M_PI * (double)j / 1024.0;
       tw[(size_t)j] = make_float2((float)std::cos(ang), (float)std::sin(ang));
     }
-    float2 *d = nullptr;
-    HIP_TRY(hipMalloc(&d, tw.size() * sizeof(float2)));
-    const hipError_t e = hipMemcpy(d, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      hipFree(d);
-      return fail(MX_ERR_DEVICE, "onset table upload: %s", hipGetErrorString(e));
-    }
-    ctx->onset_tw = d;
+    if (const int rc = upload_table(tw, &ctx->onset_tw)) return rc;
   }
   *out = ctx->onset_tw;
   return MX_OK;
@@ -90,42 +76,19 @@ int flux_launch(const FluxCall &q, float *d_flux) {
   return MX_OK;
 }
 
-// the host form: the values pass through the context's staging buffer of the pitch records.  Blocks.
+// the host form (staged_records): the values pass through the context's staging buffer of the pitch records
 int flux_host(const FluxCall &q, float *flux_out) {
-  if (q.count == 0) return MX_OK;
-  mx_ctx *ctx = q.ctx;
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> lk(ctx->stage_mu);
-  float *d_flux = nullptr;
-  hipError_t e = ctx->stage[kStagePitch].get((size_t)q.count * sizeof(float), &d_flux);
-  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
-  int rc = flux_launch(q, d_flux);
-  if (rc == MX_OK) {
-    e = hipMemcpyAsync(flux_out, d_flux, (size_t)q.count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "flux download: %s", hipGetErrorString(e));
-  }
-  stage_trim(ctx);
-  return rc;
+  const StagedSlot slots[] = {{kStagePitch, sizeof(float), nullptr, flux_out}};
+  return staged_records(q.ctx, q.count, slots, "flux", [&](void *const *d) { return flux_launch(q, static_cast<float *>(d[0])); });
 }
 
 // the parameters in force (p null: the defaults), checked
 int pick_params(const mx_onset_pick_params *p, mx_onset_pick_params &out) {
-  out = p ? *p : kPickDefaults;
+  out = params_or(p, kPickDefaults);
   for (const int32_t v : {out.pre_max, out.post_max, out.pre_avg, out.post_avg, out.wait})
     if (v < 0 || v > 4096) return fail(MX_ERR_INVALID, "pick window %d outside [0, 4096]", v);
   if (!std::isfinite(out.ratio) || !std::isfinite(out.delta) || out.ratio < 0.0 || out.delta < 0.0)
     return fail(MX_ERR_INVALID, "pick ratio %g / delta %g must be finite and >= 0", out.ratio, out.delta);
-  return MX_OK;
-}
-
-int pick_give(const float *flux, int64_t count, int hop, int64_t first_frame, const mx_onset_pick_params &p, mx_onset **out,
-              int64_t *nout) {
-  const std::vector<mx_onset> v = pick_onsets(flux, count, hop, first_frame, p);
-  HandOver h;
-  h.add(out, v.data(), v.size());
-  if (const int rc = h.give()) return rc;
-  *nout = (int64_t)v.size();
   return MX_OK;
 }
 
@@ -134,9 +97,7 @@ int pick_give(const float *flux, int64_t count, int hop, int64_t first_frame, co
 extern "C" {
 
 void mx_onset_flux_params_default(mx_onset_flux_params *p) {
-  mx_guard_void([&] {
-    if (p) *p = kFluxDefaults;
-  });
+  mx_guard_void([&] { params_default(p, kFluxDefaults); });
 }
 
 int mx_onset_flux_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
@@ -158,9 +119,7 @@ int mx_onset_flux(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64
 }
 
 void mx_onset_pick_params_default(mx_onset_pick_params *p) {
-  mx_guard_void([&] {
-    if (p) *p = kPickDefaults;
-  });
+  mx_guard_void([&] { params_default(p, kPickDefaults); });
 }
 
 int mx_onset_pick(const float *flux, int64_t count, int hop, int64_t first_frame, const mx_onset_pick_params *params,
@@ -173,7 +132,7 @@ int mx_onset_pick(const float *flux, int64_t count, int hop, int64_t first_frame
     if (hop < 1) return fail(MX_ERR_INVALID, "hop %d", hop);
     if (first_frame > INT32_MAX || count > INT32_MAX || (first_frame + count) * (int64_t)hop > INT32_MAX)
       return fail(MX_ERR_INVALID, "frame centres beyond int32 samples");
-    return pick_give(flux, count, hop, first_frame, p, out, nout);
+    return hand_over(pick_onsets(flux, count, hop, first_frame, p), out, nout);
   });
 }
 
@@ -183,22 +142,19 @@ int mx_onsets_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, co
     mx_onset_pick_params p;
     if (const int rc = pick_params(pick_params_in, p)) return rc;
     if (!out || !nout) return fail(MX_ERR_INVALID, "null argument");
-    if (!a) return fail(MX_ERR_INVALID, "null context or audio handle");
-    if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
-    const int64_t count = (a->n + hop - 1) / hop;
+    int64_t count = 0;  // (the whole file)
+    if (const int rc = file_frames(ctx, a, hop, count)) return rc;
     if (count * (int64_t)hop > INT32_MAX) return fail(MX_ERR_INVALID, "frame centres beyond int32 samples");
     std::vector<float> flux((size_t)std::max<int64_t>(count, 1));
     FluxCall q;
     if (const int rc = flux_parse(ctx, a, sampleRate, hop, 0, count, flux_params, flux.data(), q)) return rc;
     if (const int rc = flux_host(q, flux.data())) return rc;
-    return pick_give(flux.data(), count, hop, 0, p, out, nout);
+    return hand_over(pick_onsets(flux.data(), count, hop, 0, p), out, nout);
   });
 }
 
 void mx_timing_params_default(mx_timing_params *p) {
-  mx_guard_void([&] {
-    if (p) *p = kTimingDefaults;
-  });
+  mx_guard_void([&] { params_default(p, kTimingDefaults); });
 }
 
 int mx_timing_markers(const int32_t *anchors, int64_t nanchors, int64_t n, int sampleRate, const mx_timing_params *params,
@@ -208,7 +164,7 @@ int mx_timing_markers(const int32_t *anchors, int64_t nanchors, int64_t n, int s
     if (nanchors < 0 || nbase < 0) return fail(MX_ERR_INVALID, "negative count");
     if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
     if (n < 1 || n > INT32_MAX) return fail(MX_ERR_INVALID, "%lld samples outside [1, INT32_MAX]", (long long)n);
-    const mx_timing_params p = params ? *params : kTimingDefaults;
+    const mx_timing_params p = params_or(params, kTimingDefaults);
     if (!(p.bpm >= 30.0 && p.bpm <= 250.0)) return fail(MX_ERR_INVALID, "bpm %g outside [30, 250]", p.bpm);
     if (p.division < 1 || p.division > 64) return fail(MX_ERR_INVALID, "division %d outside [1, 64]", p.division);
     if (!std::isfinite(p.offset)) return fail(MX_ERR_INVALID, "offset is not finite");
@@ -224,12 +180,7 @@ int mx_timing_markers(const int32_t *anchors, int64_t nanchors, int64_t n, int s
       if (base[i].dTime != 0.0) return fail(MX_ERR_INVALID, "base marker %d has a time shift of its own (dTime %g)", i, base[i].dTime);
       if (!std::isfinite(base[i].pitchBend) || !std::isfinite(base[i].note)) return fail(MX_ERR_INVALID, "base marker %d is not finite", i);
     }
-    const std::vector<mx_marker> v = timing_markers(anchors, nanchors, n, sampleRate, p, base, nbase);
-    HandOver h;
-    h.add(out, v.data(), v.size());
-    if (const int rc = h.give()) return rc;
-    *nout = (int64_t)v.size();
-    return MX_OK;
+    return hand_over(timing_markers(anchors, nanchors, n, sampleRate, p, base, nbase), out, nout);
   });
 }
 

@@ -32,7 +32,7 @@ template <class Rec>
 int psola_plan(const PsolaCall &c, std::vector<Rec> &v, int64_t &m) {
   if (c.nmarkers < 0 || (c.nmarkers > 0 && !c.markers)) return fail(MX_ERR_INVALID, "bad marker list");
   std::string err;
-  const int rc = psola_build(c, c.params ? *c.params : kPsolaDefaults, v, m, err);
+  const int rc = psola_build(c, params_or(c.params, kPsolaDefaults), v, m, err);
   return rc ? fail(rc, "%s", err.c_str()) : MX_OK;
 }
 
@@ -43,10 +43,7 @@ int psola_plan_out(const PsolaCall &c, Rec **grains, int64_t *ngrains, int64_t *
   std::vector<Rec> v;
   int64_t m = 0;
   if (const int rc = psola_plan(c, v, m)) return rc;
-  HandOver h;
-  h.add(grains, v.data(), v.size());
-  if (const int rc = h.give()) return rc;
-  *ngrains = (int64_t)v.size();
+  if (const int rc = hand_over(v, grains, ngrains)) return rc;
   *nsamples = m;
   return MX_OK;
 }
@@ -147,9 +144,7 @@ int psola_render(mx_ctx *ctx, const mx_audio *a, PsolaCall c, float *pcm_f32, in
 extern "C" {
 
 void mx_psola_params_default(mx_psola_params *p) {
-  mx_guard_void([&] {
-    if (p) *p = kPsolaDefaults;
-  });
+  mx_guard_void([&] { params_default(p, kPsolaDefaults); });
 }
 
 int mx_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params *params,

@@ -6,36 +6,14 @@
 #include <cstdlib>
 #include <vector>
 
-#include "gl_sink.hpp"
+#include "driver_common.hpp"
 #include "melonix_amd.h"
 #include "onset-track.hpp"
 
-// the headless facade (NO_GL) leaves its few GL calls to the embedding program; this one makes no texture
-extern "C" {
-void glGenTextures(GLsizei, GLuint *) {}
-void glDeleteTextures(GLsizei, const GLuint *) {}
-void glBindTexture(GLenum, GLuint) {}
-void glTexParameteri(GLenum, GLenum, GLint) {}
-void glTexImage1D(GLenum, GLint, GLint, GLsizei, GLint, GLenum, GLenum, const void *) {}
-}
-
-template <class T>
-static bool dump(const char *path, const std::vector<T> &v) {
-  FILE *o = std::fopen(path, "wb");
-  if (!o) return false;
-  const bool ok = std::fwrite(v.data(), sizeof(T), v.size(), o) == v.size();
-  return std::fclose(o) == 0 && ok;
-}
-
 int main(int argc, char **argv) {
   if (argc != 9) return 2;
-  FILE *f = std::fopen(argv[1], "rb");
-  if (!f) return 3;
   std::vector<float> wav;
-  float buf[4096];
-  size_t k;
-  while ((k = std::fread(buf, sizeof(float), 4096, f)) > 0) wav.insert(wav.end(), buf, buf + k);
-  std::fclose(f);
+  if (!read_f32(argv[1], wav)) return 3;
   const int sr = std::atoi(argv[2]);
   melonix::OnsetTrack track(wav, sr);
   if (!track.ok()) return 4;

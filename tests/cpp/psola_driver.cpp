@@ -10,30 +10,16 @@
 #include <cstring>
 #include <vector>
 
-#include "gl_sink.hpp"
+#include "driver_common.hpp"
 #include "melonix_amd.h"
 #include "pitch-track.hpp"
 #include "resynth.hpp"
 
-// the headless facade (NO_GL) leaves its few GL calls to the embedding program; this one makes no texture
-extern "C" {
-void glGenTextures(GLsizei, GLuint *) {}
-void glDeleteTextures(GLsizei, const GLuint *) {}
-void glBindTexture(GLenum, GLuint) {}
-void glTexParameteri(GLenum, GLenum, GLint) {}
-void glTexImage1D(GLenum, GLint, GLint, GLsizei, GLint, GLenum, GLenum, const void *) {}
-}
-
 int main(int argc, char **argv) {
   const bool formant = argc == 9 && !std::strcmp(argv[1], "formant");
   if (!formant && !(argc == 8 && !std::strcmp(argv[1], "plain"))) return 2;
-  FILE *f = std::fopen(argv[2], "rb");
-  if (!f) return 3;
   std::vector<float> wav;
-  float buf[4096];
-  size_t k;
-  while ((k = std::fread(buf, sizeof(float), 4096, f)) > 0) wav.insert(wav.end(), buf, buf + k);
-  std::fclose(f);
+  if (!read_f32(argv[2], wav)) return 3;
   const int sr = std::atoi(argv[3]);
   const double bend = std::atof(argv[4]);
   melonix::PitchTrack track(wav, sr, 256, 55.f, 1760.f, 0.15f, 0, !formant && std::atoi(argv[5]) != 0);
@@ -47,10 +33,7 @@ int main(int argc, char **argv) {
   const std::vector<float> pcm =
       formant ? rs.renderPSOLA(mk, track.frames(), track.hop(), pts) : rs.renderPSOLA(mk, track.frames(), track.hop(), &p);
   if (pcm.empty()) return 6;
-  FILE *o = std::fopen(argv[argc - 2], "wb");
-  if (!o) return 7;
-  std::fwrite(pcm.data(), sizeof(float), pcm.size(), o);
-  std::fclose(o);
+  if (!dump(argv[argc - 2], pcm)) return 7;
   if (!(formant ? rs.exportWavPSOLA(argv[argc - 1], mk, track.frames(), track.hop(), pts)
                 : rs.exportWavPSOLA(argv[argc - 1], mk, track.frames(), track.hop(), &p)))
     return 8;

@@ -1,6 +1,6 @@
-"""tests/tools/hip_timing.py — what the hour tools share: the libraries under test on one device image of the samples, and the
-timed-launch loop: launches on the null stream between two HIP events, the candidates in turn (interleaved launch by launch,
-so that drift of the clocks hits all alike), warm-ups first.  (The tools put the repository and tests/ on the path.)"""
+"""tests/hip_timing.py — what the hour tools (tests/tools) and the suite's timed test share: the libraries under test on one device
+image of the samples, and the timed-launch loop: launches on the null stream between two HIP events, the candidates in turn
+(interleaved launch by launch, so that drift of the clocks hits all alike), warm-ups first."""
 import ctypes as C
 import os
 

@@ -6,6 +6,7 @@ import pytest
 
 import yin_ref as Y
 from conftest import SR, DevBuf, accum_sweep, loaded_hip, noisy
+from hip_timing import EventTimer
 
 pytestmark = pytest.mark.gpu
 
@@ -151,31 +152,12 @@ def test_the_hour(gpu_ctx, mxlib):
     F = mxlib.frame_count(n, HOP)
     assert F == 675000
     d = DevBuf(F * 16)
-    hip = loaded_hip()
-    hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventDestroy.argtypes = [C.c_void_p]
-    e0, e1 = C.c_void_p(), C.c_void_p()
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
-    gpu_ctx.set_stream(None)  # the null stream: the events below bracket exactly the launch
+    gpu_ctx.set_stream(None)  # the null stream: the timer's events bracket exactly the launch
     try:
-        times = []
-        for it in range(7):
-            assert hip.hipEventRecord(e0, None) == 0
-            gpu_ctx.f0_track_dev(a, SR, HOP, 0, F, d.ptr)
-            assert hip.hipEventRecord(e1, None) == 0
-            assert hip.hipEventSynchronize(e1) == 0
-            ms = C.c_float()
-            assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-            if it >= 2:
-                times.append(ms.value)
+        t = EventTimer(loaded_hip()).timed({"f0": lambda: gpu_ctx.f0_track_dev(a, SR, HOP, 0, F, d.ptr)}, warm=2, runs=5)["f0"]
     finally:
         gpu_ctx.use_own_stream()
-        hip.hipEventDestroy(e0)
-        hip.hipEventDestroy(e1)
-    med = float(np.median(times))
+    med = t["median"]
     tr = d.read(np.uint8).view(mxlib.F0_DTYPE)
     d.free()
     a.free()
@@ -183,7 +165,7 @@ def test_the_hour(gpu_ctx, mxlib):
     inner = (h * HOP >= 4096) & (h * HOP <= n - 4096)
     f_inst = 110.0 + (1760.0 - 110.0) * (h * HOP) / n
     cents = 1200 * np.log2(SR / tr["period"][inner] / f_inst[inner])
-    print(f"f0 hour: {F} frames, median of 5 timed calls {med:.3f} ms (all: {', '.join(f'{t:.3f}' for t in times)}); "
+    print(f"f0 hour: {F} frames, median of 5 timed calls {med:.3f} ms ({t['min']:.3f} to {t['max']:.3f}); "
           f"analytic f0 within {np.abs(cents).max():.3f} cents (mean {cents.mean():+.4f})")
     assert np.abs(cents).max() <= 2.0
     assert med < 20.0

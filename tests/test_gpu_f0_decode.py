@@ -2,7 +2,6 @@
 (tests/f0_decode_ref.py), the track of the same launch against f0_track, the decode against the integer reference byte for byte
 at every chunk length and at the counts where a chunked scan goes wrong, GLITCH end to end, guard bands, bad samples, and
 melonix::PitchTrack's `decoded` option."""
-import os
 import subprocess
 
 import numpy as np
@@ -11,12 +10,12 @@ import pytest
 import f0_decode_ref as D
 import yin_ref as Y
 from conftest import SR, DevBuf, accum_sweep, noisy
+from facade_build import build_driver
 from test_gpu_f0 import _signals
 
 pytestmark = pytest.mark.gpu
 
 HOP = 256
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNKS = (2, 7, 64, 0)  # 0: the default
 ZERO = dict(unvoiced_cost=0.0, jump_cost=0.0, switch_cost=0.0, max_jump_cents=0)
 STIFF = dict(unvoiced_cost=1.25, jump_cost=16.0, switch_cost=0.0, max_jump_cents=12000)
@@ -246,12 +245,7 @@ def test_bad_samples(gpu_ctx):
 
 # ---- 11. the facade ----
 def test_pitch_track_facade_decoded(gpu_ctx, mxlib, tmp_path):
-    lib = os.path.join(ROOT, "melonix_amd", "lib")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "melonix_amd", "cpp"), "NO_GL=1"])
-    exe = str(tmp_path / "pitch_track_decoded_driver")
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-DMELONIX_AMD_NO_GL", "-I", os.path.join(ROOT, "melonix_amd", "cpp"), "-I",
-                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "pitch_track_decoded_driver.cpp"),
-                           "-o", exe, "-L", lib, "-lmelonix_facade", "-lmelonix_amd", f"-Wl,-rpath,{lib}", "-lpthread"])
+    exe = build_driver(tmp_path, "pitch_track_decoded_driver")
     w = D.glitch()
     src = tmp_path / "in.f32"
     w.astype("<f4").tofile(src)

@@ -7,21 +7,14 @@ import numpy as np
 import pytest
 
 from conftest import SR, accum_sweep, mag_tol
+from facade_build import build_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def driver(mxlib, tmp_path_factory):
-    cpp = os.path.join(ROOT, "melonix_amd", "cpp")
-    subprocess.check_call(["make", "-s", "-C", cpp, "NO_GL=1"])
-    exe = str(tmp_path_factory.mktemp("facade") / "facade_driver")
-    lib = os.path.join(ROOT, "melonix_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-DMELONIX_AMD_NO_GL", "-I", cpp, "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "facade_driver.cpp"), "-o", exe, "-L", lib,
-                           "-lmelonix_facade", "-lmelonix_amd", f"-Wl,-rpath,{lib}", "-lpthread"])
-    return exe
+    return build_driver(tmp_path_factory.mktemp("facade"), "facade_driver", opt="-O1")
 
 
 @pytest.mark.parametrize("N", [32768, 4096])

@@ -1,6 +1,8 @@
 """mx_onset_flux / mx_onset_flux_dev / mx_onsets_detect on the GPU against tests/onset_ref.py (include/melonix_amd.h "Onset
 detection and tempo-grid timing markers"): the onset strength within the project's f32-versus-f64 yardstick, the same bytes
 whatever the launch split or the run length, the edges of n, hop, lag and band, the picks, and what a bad call may touch."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -179,12 +181,27 @@ def test_guard_bands_and_refusals(mxlib, gpu_ctx, cases):
                dict(first=0, count=frames + 1), dict(compress=0.0), dict(compress=-1.0), dict(compress=float("nan")),
                dict(compress=2e6), dict(lag=0), dict(lag=5), dict(fmin=-1.0), dict(fmax=float("inf")), dict(fmin=5000.0, fmax=100.0),
                dict(fmin=1.0, fmax=40.0), dict(fmin=30000.0)]
+        # every context entry point turns each of them down the same way and writes nothing: raw calls, ten frames
+        from melonix_amd import _capi
+        lib, ctx = _capi.lib(), gpu_ctx.handle
+        host = np.full(10 * 4, 0xA5, dtype=np.uint8)
+
+        def detect_refuses(flux_p, pick_p, sr=SR, hop=HOP):
+            out, nout = C.c_void_p(0x1234), C.c_int64(-77)
+            rc = lib.mx_onsets_detect(ctx, a.handle, sr, hop, flux_p, pick_p, C.byref(out), C.byref(nout))
+            return rc == _capi.MX_ERR_INVALID and out.value == 0x1234 and nout.value == -77
+
         for kw in bad:
             kw = dict(kw)
-            args = dict(sr=kw.pop("sr", SR), hop=kw.pop("hop", HOP), first=kw.pop("first", 0), count=kw.pop("count", 10))
-            with pytest.raises(mxlib.MxError) as e:
-                gpu_ctx.onset_flux_dev(a, args["sr"], args["hop"], args["first"], args["count"], buf.ptr + G * 4, **kw)
-            assert e.value.code == -1, (kw, e.value)
+            sr, hop, first, cnt = kw.pop("sr", SR), kw.pop("hop", HOP), kw.pop("first", 0), kw.pop("count", 10)
+            p = C.byref(_capi.OnsetFluxParams(**{**mxlib.onset_flux_params_default(), **kw}))
+            assert lib.mx_onset_flux(ctx, a.handle, sr, hop, first, cnt, p, host.ctypes.data) == _capi.MX_ERR_INVALID, kw
+            assert lib.mx_onset_flux_dev(ctx, a.handle, sr, hop, first, cnt, p, buf.ptr + G * 4) == _capi.MX_ERR_INVALID, kw
+            if (first, cnt) == (0, 10):  # (mx_onsets_detect has no frame span of its own: the whole file)
+                assert detect_refuses(p, None, sr, hop), kw
+            assert np.all(host == 0xA5), kw
+        for kw in (dict(wait=-1), dict(pre_max=4097), dict(post_avg=-1), dict(ratio=float("nan")), dict(delta=-1.0)):
+            assert detect_refuses(None, C.byref(_capi.OnsetPickParams(**{**mxlib.onset_pick_params_default(), **kw}))), kw
         with pytest.raises(mxlib.MxError) as e:
             gpu_ctx.onset_flux_dev(a, SR, HOP, 0, 10, 0)  # a null output
         assert e.value.code == -1

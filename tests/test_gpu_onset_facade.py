@@ -1,28 +1,22 @@
 """melonix::OnsetTrack (the C++ facade of the onset detector and the timing markers) from a compiled program: the C-ABI's
 onsets and markers; and one end-to-end check — a take whose notes are off the grid, its timing markers, a render, and the
 onsets of the render where the markers sent them."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import onset_ref as R
+from facade_build import build_driver
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SR, HOP = R.SR, R.HOP
 
 
 @pytest.mark.parametrize("with_base", [0, 1])
 def test_onset_facade_matches_the_c_abi(gpu_ctx, mxlib, tmp_path, with_base):
-    lib = os.path.join(ROOT, "melonix_amd", "lib")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "melonix_amd", "cpp"), "NO_GL=1"])
-    exe = str(tmp_path / "onset_driver")
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-DMELONIX_AMD_NO_GL", "-I", os.path.join(ROOT, "melonix_amd", "cpp"), "-I",
-                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "onset_driver.cpp"),
-                           "-o", exe, "-L", lib, "-lmelonix_facade", "-lmelonix_amd", f"-Wl,-rpath,{lib}", "-lpthread"])
+    exe = build_driver(tmp_path, "onset_driver")
     w = R.notes(0.005)
     src, fl, on, mk = (tmp_path / k for k in ("in.f32", "flux.f32", "onsets.bin", "markers.bin"))
     w.astype("<f4").tofile(src)

@@ -1,28 +1,21 @@
 """melonix::Resynth::renderPSOLA / exportWavPSOLA over a melonix::PitchTrack (the C++ facade of the PSOLA renderer) from a
 compiled program: the Python path's bytes, and the WAV file saveWav makes of them.  On a decoded track the facade's default
 threshold is twice the tracker's."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import SR
+from facade_build import build_driver
 from test_gpu_psola import vowel
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.mark.parametrize("decoded", [0, 1])
 def test_psola_facade_matches_python(gpu_ctx, mxlib, tmp_path, decoded):
-    lib = os.path.join(ROOT, "melonix_amd", "lib")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "melonix_amd", "cpp"), "NO_GL=1"])
-    exe = str(tmp_path / "psola_driver")
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-DMELONIX_AMD_NO_GL", "-I", os.path.join(ROOT, "melonix_amd", "cpp"), "-I",
-                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "psola_driver.cpp"),
-                           "-o", exe, "-L", lib, "-lmelonix_facade", "-lmelonix_amd", f"-Wl,-rpath,{lib}", "-lpthread"])
+    exe = build_driver(tmp_path, "psola_driver")
     w = vowel(0.75)
     src, out, wav = tmp_path / "in.f32", tmp_path / "out.f32", tmp_path / "out.wav"
     w.astype("<f4").tofile(src)
