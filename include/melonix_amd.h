@@ -746,6 +746,110 @@ void mx_timing_params_default(mx_timing_params *p);
 int mx_timing_markers(const int32_t *anchors, int64_t nanchors, int64_t n, int sampleRate, const mx_timing_params *params,
                       const mx_marker *base, int nbase, mx_marker **out, int64_t *nout);
 
+/* ---- Tempo and grid-offset estimation (BUILD-DEFINED; restated by tests/tempo_ref.py) ----
+ * mx_timing_params.bpm and .offset from the onset-strength curve itself: the one link of the timing chain (flux -> onsets ->
+ * markers -> render) that was fed by hand.  The reference has a Tempo slider and no estimator.  The definition is
+ * tolerance-free — f32 products, a binary64 running sum, integer positions — so the device, the host and numpy give the same
+ * bytes.
+ *
+ * Smoothed curve.  Input: count flux values o_f.  z_f = o_f, 0 where o_f is not finite, 0 outside [0, count).  Half-width W
+ * in [0, 32]; h_d = (float)(0.5 + 0.5 cos(pi d / (W + 1))), the cosine in binary64.
+ *   e_f = sum_{d = -W..W} h_|d| * z_{f+d}, in f32, from 0.f in ascending d, each product rounded before it is added.
+ * W = 0 is the sanitising copy.  The output must not overlap the input.
+ *
+ * Comb job {first, frames, period_q16}: frames >= 1, [first, first + frames) inside [0, count), period_q16 a beat period in
+ * frames as Q16 in [2 * 65536, 4096 * 65536] — the Q16 value is the definition.  Phases phi = 0 .. nph - 1,
+ * nph = ceil(period_q16 / 65536).  For a phase, positions in int64:
+ *   start = (first + phi) << 16, lim = (first + frames - 1) << 16;  J = 0 if start > lim, else (lim - start) / period_q16 + 1;
+ *   for j = 0 .. J - 1 ascending: pos = start + j * period_q16, idx = pos >> 16, fr = (float)(pos & 65535) * 2^-16 (exact),
+ *     x = (1 - fr) * e[idx] + fr * e[min(idx + 1, count - 1)] in f32 (the resampler's form, products rounded before the sum),
+ *     S += (double)x;
+ *   score_phi = (float)(S / (double)J), 0.f when J = 0.
+ * The record: score = the maximum over the phases, phase = the lowest phi that attains it, prev / next = the scores of phases
+ * (phi -+ 1) mod nph.  A record depends on nothing but the curve and its job: the same bytes whatever the job list, its order,
+ * the launch split or the thread mapping.  (The curve is meant to be finite — mx_tempo_smooth's output is; with a NaN in a
+ * job's reach its record is some phase's, not a fault.) */
+typedef struct mx_comb_job {
+  int32_t first, frames;
+  uint32_t period_q16;
+} mx_comb_job;
+typedef struct mx_comb {
+  float score;
+  int32_t phase;
+  float prev, next;
+} mx_comb;
+/* Estimate (host, binary64, libm, no contraction).  fr = sr / hop frames per second.
+ *   candidates  bpm_c = bpm_max * exp2(-c / per_octave), c = 0, 1, .. while bpm_c >= bpm_min;
+ *               period_c = (uint32)floor(60 * fr / bpm_c * 65536 + 0.5); MX_ERR_INVALID if one leaves the Q16 range.
+ *   windows     [w * stride_frames, w * stride_frames + window_frames) for every w that fits; count < window_frames: [0, count).
+ *   coarse      one job per (window, candidate), T[w][c] its score;  prior_c = exp(-0.5 (log2(bpm_c / prior_bpm) / prior_octaves)^2);
+ *               A_c = (sum_w T[w][c], binary64, ascending w) * prior_c;  c* = the lowest c that attains max A;  the anchor =
+ *               the lowest w that attains max T[w][c*].  The window curve: per window the candidate that is the lowest argmax of
+ *               T[w][c] * prior_c, as {first_frame + w * stride_frames, frames, (float)(60 * fr * 65536 / period), T[w][c]}.
+ *   refinement  the grid must hold over ever longer stretches: segment and resolution grow together.  p = period_c*,
+ *               step = max(1, (int)(p * (exp2(1 / per_octave) - 1) / 8)), L = the anchor's length, centre = its first + L / 2.
+ *               Per level: len = min(L, count), first = clamp(centre - L / 2, 0, count - len); jobs over [first, first + len)
+ *               with periods p + k * step, k = -12 .. 12, those outside the Q16 range dropped; best = the highest score, then
+ *               the smallest |k|, then the lower k.  The first level's best score is the base.  A later level whose best score
+ *               < lock_ratio * base ends the refinement with the previous level's result.  Otherwise p = the best period and
+ *               {first, len, record} are kept; the refinement ends if len == count, else L = 8 L, step = max(1, step / 8).
+ *   result      from the last kept level: g = (p / 65536) / fr, bpm = 60 / g;  delta = 0.5 (prev - next) / (prev - 2 score + next)
+ *               clamped to +-0.5, 0 unless that curvature is < 0;  offset = fmod((first_frame + first + phase + delta) / fr, g),
+ *               moved into [0, g);  score = the record's;  clarity = score / the mean of e (summed in binary64, ascending; 0 unless that mean is > 0);
+ *               locked_frames = len;  levels = the number of levels kept.
+ * An empty curve, or one whose every e_f is 0, is not an error: bpm 0, offset 0, score 0, clarity 0, locked_frames 0, levels 0
+ * and an empty window curve.
+ * What follows from the definition (not bugs):
+ *   - the estimate is octave-ambiguous and the prior decides: 85 bpm at division 4 and 170 bpm at division 2 are the same grid
+ *     lines.  The refinement follows the curve, so bpm can end a little outside [bpm_min, bpm_max];
+ *   - clarity ~ 1 means no pulse was found: every phase of a steady curve scores its mean (steady noise gives 1.07 in
+ *     tests/tempo_ref.py, the synthetic takes 7 to 16). */
+typedef struct mx_tempo_params {
+  double bpm_min, bpm_max;  /* inside [30, 250], bpm_min < bpm_max; default 30, 250 */
+  int32_t per_octave;       /* candidates per octave, [8, 128]; default 64 */
+  int32_t smooth;           /* W, [0, 32]; default 4 */
+  int32_t window_frames;    /* coarse window length, [64, 65536]; default 2048 */
+  int32_t stride_frames;    /* window stride, [1, window_frames]; default 512 */
+  double prior_bpm;         /* centre of the tempo prior, finite, > 0; default 120 */
+  double prior_octaves;     /* width of the tempo prior, finite, > 0; default 1 */
+  double lock_ratio;        /* where refinement stops, [0, 1]; default 0.5 */
+} mx_tempo_params;
+typedef struct mx_tempo {
+  double bpm, offset; /* beats per minute; the time of a beat, seconds, in [0, 60 / bpm) */
+  float score, clarity;
+  int64_t locked_frames;
+  int32_t levels;
+} mx_tempo;
+typedef struct mx_tempo_window {
+  int32_t first_frame, frames;
+  float bpm, score;
+} mx_tempo_window;
+void mx_tempo_params_default(mx_tempo_params *p);
+/* d_flux -> d_out (count floats each, in HBM, not overlapping).  Asynchronous on the context's stream.  MX_ERR_INVALID for
+ * width outside [0, 32], count < 0 or beyond INT32_MAX, a null pointer with count > 0, overlapping ranges. */
+int mx_tempo_smooth_dev(mx_ctx *ctx, const float *d_flux, int64_t count, int width, float *d_out);
+/* Same, host pointers through the context's tempo work memory.  Blocks. */
+int mx_tempo_smooth(mx_ctx *ctx, const float *flux, int64_t count, int width, float *out);
+/* One record per job, d_out[i] for d_jobs[i].  Asynchronous on the context's stream.
+ * PRECONDITION (not checked on the device — mx_tempo_comb does check it): every job as defined above.  Jobs that break it
+ * give wrong numbers and nothing worse: every index is clamped into [0, count - 1], nph to 4096, J to count, and nothing is
+ * stored outside the job's own record. */
+int mx_tempo_comb_dev(mx_ctx *ctx, const float *d_curve, int64_t count, const mx_comb_job *d_jobs, int64_t njobs, mx_comb *d_out);
+/* Same, host pointers.  Checks every job and returns MX_ERR_INVALID before any launch, the output untouched.  Blocks. */
+int mx_tempo_comb(mx_ctx *ctx, const float *curve, int64_t count, const mx_comb_job *jobs, int64_t njobs, mx_comb *out);
+/* The estimate from a host flux curve; flux[i] is frame first_frame + i (>= 0, first_frame + count <= INT32_MAX).  p NULL: the
+ * defaults.  windows may be NULL; otherwise *windows is library-allocated (free with mx_free), *nwindows its length.  Every
+ * parameter out of its range, sr <= 0, hop outside [1, 16384] or a candidate period outside the Q16 range: MX_ERR_INVALID
+ * before any launch.  Blocks. */
+int mx_tempo_from_flux(mx_ctx *ctx, const float *flux, int64_t count, int sampleRate, int hop, int64_t first_frame,
+                       const mx_tempo_params *p, mx_tempo *out, mx_tempo_window **windows, int64_t *nwindows);
+/* The whole file: mx_onset_flux_dev into the context's work memory, the smoothing and the comb launches there; what comes back
+ * is the smoothed curve once (4 bytes per frame, for the mean behind clarity) and the job records.  fp / p NULL: the defaults.
+ * The work memory (two curves, jobs, records) is the context's, kept between calls, released by mx_ctx_release_scratch;
+ * MX_ERR_NOMEM when it cannot be had, nothing of it left allocated.  Blocks. */
+int mx_tempo_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_onset_flux_params *fp,
+                    const mx_tempo_params *p, mx_tempo *out, mx_tempo_window **windows, int64_t *nwindows);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

@@ -16,6 +16,7 @@ import numpy as np
 from . import _capi
 from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, ONSET_DTYPE, PITCH_DTYPE,  # noqa: F401
                     PSOLA_FGRAIN_DTYPE, PSOLA_GRAIN_DTYPE, STEP_DTYPE, MxError)
+from ._capi import COMB_DTYPE, COMB_JOB_DTYPE, TEMPO_WINDOW_DTYPE  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
@@ -23,7 +24,7 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "PSOLA_GRAIN_DTYPE", "psola_params_default", "psola_plan",
            "PSOLA_FGRAIN_DTYPE", "FORMANT_POINT_DTYPE", "psola_plan_formant",
            "ONSET_DTYPE", "onset_flux_params_default", "onset_pick_params_default", "onset_pick", "timing_params_default",
-           "timing_markers"]
+           "timing_markers", "COMB_JOB_DTYPE", "COMB_DTYPE", "TEMPO_WINDOW_DTYPE", "tempo_params_default"]
 
 
 def _ptr(a):
@@ -53,7 +54,8 @@ def _take_records(p, count: int, dtype):
 # the parameter blocks of the build-defined entry points: kind -> (its ctypes struct, the entry point that writes its defaults)
 _PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "note": (_capi.NoteParams, "mx_note_params_default"),
            "psola": (_capi.PsolaParams, "mx_psola_params_default"), "flux": (_capi.OnsetFluxParams, "mx_onset_flux_params_default"),
-           "pick": (_capi.OnsetPickParams, "mx_onset_pick_params_default"), "timing": (_capi.TimingParams, "mx_timing_params_default")}
+           "pick": (_capi.OnsetPickParams, "mx_onset_pick_params_default"), "timing": (_capi.TimingParams, "mx_timing_params_default"),
+           "tempo": (_capi.TempoParams, "mx_tempo_params_default")}
 
 
 def _params_default(kind: str) -> dict:
@@ -99,6 +101,10 @@ def onset_pick_params_default() -> dict:
 
 def timing_params_default() -> dict:
     return _params_default("timing")
+
+
+def tempo_params_default() -> dict:
+    return _params_default("tempo")
 
 
 def pitch_band(N: int, sr: int = 48000):
@@ -402,6 +408,58 @@ class Context:
         _capi.check(_capi.lib().mx_onsets_detect(self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
                                                  _params_arg("pick", pick_params or {}), C.byref(out), C.byref(cnt)))
         return _take_records(out, cnt.value, ONSET_DTYPE)
+
+    # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
+    def tempo_smooth(self, flux, width: int = 4):
+        """-> the smoothed float32 curve of a host flux curve (half-width `width`; 0: the sanitising copy)."""
+        flux = np.ascontiguousarray(flux, dtype=np.float32)
+        out = np.empty(len(flux), dtype=np.float32)
+        _capi.check(_capi.lib().mx_tempo_smooth(self.handle, _ptr(flux) if len(flux) else None, len(flux), width,
+                                                _ptr(out) if len(flux) else None))
+        return out
+
+    def tempo_smooth_dev(self, d_flux: int, count: int, width: int, d_out: int):
+        """count floats at d_flux -> d_out, both in HBM; asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_tempo_smooth_dev(self.handle, C.c_void_p(d_flux or 0), count, width, C.c_void_p(d_out or 0)))
+
+    def tempo_comb(self, curve, jobs):
+        """COMB_JOB_DTYPE jobs (or (first, frames, period_q16) tuples) over a host curve -> COMB_DTYPE records, one per job."""
+        curve = np.ascontiguousarray(curve, dtype=np.float32)
+        jobs = np.ascontiguousarray(jobs if isinstance(jobs, np.ndarray) and jobs.dtype == COMB_JOB_DTYPE
+                                    else np.array([tuple(int(v) for v in j) for j in jobs], dtype=COMB_JOB_DTYPE))
+        out = np.empty(len(jobs), dtype=COMB_DTYPE)
+        _capi.check(_capi.lib().mx_tempo_comb(self.handle, _ptr(curve) if len(curve) else None, len(curve),
+                                              _ptr(jobs) if len(jobs) else None, len(jobs), _ptr(out) if len(jobs) else None))
+        return out
+
+    def tempo_comb_dev(self, d_curve: int, count: int, d_jobs: int, njobs: int, d_out: int):
+        """Jobs and curve in HBM -> njobs records at d_out; asynchronous on the context's stream.  The jobs are not checked."""
+        _capi.check(_capi.lib().mx_tempo_comb_dev(self.handle, C.c_void_p(d_curve or 0), count, C.c_void_p(d_jobs or 0), njobs,
+                                                  C.c_void_p(d_out or 0)))
+
+    @staticmethod
+    def _tempo_result(t, win, cnt, want_windows: bool):
+        res = {k: getattr(t, k) for k, _ in _capi.Tempo._fields_}
+        return (res, _take_records(win, cnt.value, TEMPO_WINDOW_DTYPE)) if want_windows else res
+
+    def tempo_from_flux(self, flux, sr: int, hop: int = 256, first_frame: int = 0, want_windows: bool = False, **params):
+        """Tempo and grid offset of a host flux curve (flux[0] = frame first_frame) -> dict of mx_tempo's fields, with
+        want_windows (dict, TEMPO_WINDOW_DTYPE array).  params: fields of tempo_params_default()."""
+        flux = np.ascontiguousarray(flux, dtype=np.float32)
+        t, win, cnt = _capi.Tempo(), C.c_void_p(), C.c_int64()
+        _capi.check(_capi.lib().mx_tempo_from_flux(self.handle, _ptr(flux) if len(flux) else None, len(flux), sr, hop, first_frame,
+                                                   _params_arg("tempo", params), C.byref(t),
+                                                   C.byref(win) if want_windows else None, C.byref(cnt) if want_windows else None))
+        return self._tempo_result(t, win, cnt, want_windows)
+
+    def tempo_detect(self, audio: Audio, sr: int, hop: int = 256, flux_params: dict | None = None, want_windows: bool = False,
+                     **params):
+        """Flux over the whole file, kept in HBM, and the estimate from it; as tempo_from_flux."""
+        t, win, cnt = _capi.Tempo(), C.c_void_p(), C.c_int64()
+        _capi.check(_capi.lib().mx_tempo_detect(self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
+                                                _params_arg("tempo", params), C.byref(t),
+                                                C.byref(win) if want_windows else None, C.byref(cnt) if want_windows else None))
+        return self._tempo_result(t, win, cnt, want_windows)
 
     # ---- grains / resynthesis ----
     def grains_dev(self, audio: Audio):

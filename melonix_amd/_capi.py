@@ -98,6 +98,29 @@ class TimingParams(C.Structure):
                 ("max_shift", C.c_double), ("max_stretch", C.c_double)]
 
 
+class CombJob(C.Structure):
+    _fields_ = [("first", C.c_int32), ("frames", C.c_int32), ("period_q16", C.c_uint32)]
+
+
+class Comb(C.Structure):
+    _fields_ = [("score", C.c_float), ("phase", C.c_int32), ("prev", C.c_float), ("next", C.c_float)]
+
+
+class TempoParams(C.Structure):
+    _fields_ = [("bpm_min", C.c_double), ("bpm_max", C.c_double), ("per_octave", C.c_int32), ("smooth", C.c_int32),
+                ("window_frames", C.c_int32), ("stride_frames", C.c_int32), ("prior_bpm", C.c_double),
+                ("prior_octaves", C.c_double), ("lock_ratio", C.c_double)]
+
+
+class Tempo(C.Structure):
+    _fields_ = [("bpm", C.c_double), ("offset", C.c_double), ("score", C.c_float), ("clarity", C.c_float),
+                ("locked_frames", C.c_int64), ("levels", C.c_int32)]
+
+
+class TempoWindow(C.Structure):
+    _fields_ = [("first_frame", C.c_int32), ("frames", C.c_int32), ("bpm", C.c_float), ("score", C.c_float)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -117,6 +140,11 @@ PSOLA_FGRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_idx",
 assert PSOLA_FGRAIN_DTYPE.itemsize == C.sizeof(PsolaFGrain) == 32 and FORMANT_POINT_DTYPE.itemsize == C.sizeof(FormantPoint) == 8
 ONSET_DTYPE = np.dtype([("sample", "<i4"), ("frame", "<i4"), ("strength", "<f4"), ("margin", "<f4")])
 assert ONSET_DTYPE.itemsize == C.sizeof(Onset) == 16 and C.sizeof(OnsetPickParams) == 40 and C.sizeof(TimingParams) == 48
+COMB_JOB_DTYPE = np.dtype([("first", "<i4"), ("frames", "<i4"), ("period_q16", "<u4")])
+COMB_DTYPE = np.dtype([("score", "<f4"), ("phase", "<i4"), ("prev", "<f4"), ("next", "<f4")])
+TEMPO_WINDOW_DTYPE = np.dtype([("first_frame", "<i4"), ("frames", "<i4"), ("bpm", "<f4"), ("score", "<f4")])
+assert COMB_JOB_DTYPE.itemsize == C.sizeof(CombJob) == 12 and COMB_DTYPE.itemsize == C.sizeof(Comb) == 16
+assert TEMPO_WINDOW_DTYPE.itemsize == C.sizeof(TempoWindow) == 16 and C.sizeof(TempoParams) == 56 and C.sizeof(Tempo) == 40
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -233,6 +261,15 @@ SIGNATURES = {
                               C.POINTER(_i64)]),
     "mx_timing_params_default": (None, [C.POINTER(TimingParams)]),
     "mx_timing_markers": (_i, [_vp, _i64, _i64, _i, C.POINTER(TimingParams), _vp, _i, C.POINTER(_vp), C.POINTER(_i64)]),
+    "mx_tempo_params_default": (None, [C.POINTER(TempoParams)]),
+    "mx_tempo_smooth_dev": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "mx_tempo_smooth": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "mx_tempo_comb_dev": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "mx_tempo_comb": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "mx_tempo_from_flux": (_i, [_vp, _vp, _i64, _i, _i, _i64, C.POINTER(TempoParams), C.POINTER(Tempo), C.POINTER(_vp),
+                                C.POINTER(_i64)]),
+    "mx_tempo_detect": (_i, [_vp, _vp, _i, _i, C.POINTER(OnsetFluxParams), C.POINTER(TempoParams), C.POINTER(Tempo),
+                             C.POINTER(_vp), C.POINTER(_i64)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

@@ -7,7 +7,7 @@
 namespace melonix {
 
 OnsetTrack::OnsetTrack(std::span<const float> wav, int sampleRate, int hop, int device)
-    : sampleRate(sampleRate), hop_(hop), n_((int64_t)wav.size()) {
+    : sampleRate(sampleRate), hop_(hop), device_(device), n_((int64_t)wav.size()) {
   good = glue::fileTrack(wav, hop, device, flux_, [&](mx_ctx *ctx, const mx_audio *audio, int64_t frames, float *out) {
     return mx_onset_flux(ctx, audio, sampleRate, hop, 0, frames, nullptr, out);
   });
@@ -34,6 +34,37 @@ std::vector<Marker> OnsetTrack::timingMarkers(const mx_timing_params &p, const s
                         reinterpret_cast<const mx_marker *>(baseMarkers.data()), (int)baseMarkers.size(), &v, &n) != MX_OK)
     return {};
   return glue::taken<Marker>(v, n);
+}
+
+mx_tempo_params OnsetTrack::tempoParams() { return glue::defaults(mx_tempo_params_default); }
+
+// the estimate over flux() on a context of its own for the call (the track keeps none); windows null: not wanted
+bool OnsetTrack::estimate(const mx_tempo_params &p, mx_tempo &t, std::vector<mx_tempo_window> *windows) const {
+  t = mx_tempo{};
+  if (windows) windows->clear();
+  mx_ctx *ctx = nullptr;
+  if (!good || mx_ctx_create(device_, &ctx) != MX_OK) return false;
+  mx_tempo_window *v = nullptr;
+  int64_t n = 0;
+  const bool done = mx_tempo_from_flux(ctx, flux_.data(), (int64_t)flux_.size(), sampleRate, hop_, 0, &p, &t, windows ? &v : nullptr,
+                                       windows ? &n : nullptr) == MX_OK;
+  mx_ctx_destroy(ctx);
+  if (!done) t = mx_tempo{};
+  else if (windows) *windows = glue::taken<mx_tempo_window>(v, n);
+  return done;
+}
+
+mx_tempo OnsetTrack::tempo(const mx_tempo_params &p) const {
+  mx_tempo t;
+  estimate(p, t, nullptr);
+  return t;
+}
+
+std::vector<mx_tempo_window> OnsetTrack::tempoWindows(const mx_tempo_params &p) const {
+  mx_tempo t;
+  std::vector<mx_tempo_window> w;
+  estimate(p, t, &w);
+  return w;
 }
 
 }  // namespace melonix

@@ -223,6 +223,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     for (auto &st : ctx->stage) st.drop();
     for (auto &st : ctx->chain) st.drop();
     for (auto &st : ctx->f0dec) st.drop();
+    for (auto &st : ctx->tempo) st.drop();
     pv_release(ctx);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -275,6 +276,10 @@ int mx_ctx_release_scratch(mx_ctx *ctx) {
     {
       std::lock_guard<std::mutex> lk(ctx->f0_mu);
       for (auto &st : ctx->f0dec) st.drop();
+    }
+    {
+      std::lock_guard<std::mutex> lk(ctx->tempo_mu);
+      for (auto &st : ctx->tempo) st.drop();
     }
     return MX_OK;
   });

@@ -147,6 +147,8 @@ enum StageSlot { kStageMags, kStagePitch, kStageRanges, kStageTexels, kStageSlot
 enum ChainSlot { kChainBitmap7, kChainBitmap3, kChainRanks, kChainTables, kChainSlots };
 // work buffers of the f0 decode (mx_ctx::f0dec, under f0_mu): bp rows, chunk products, chunk maps
 enum F0DecSlot { kF0DecBp, kF0DecProd, kF0DecMap, kF0DecSlots };
+// work buffers of the tempo estimate (mx_ctx::tempo, under tempo_mu): the flux curve, the smoothed curve, jobs, records
+enum TempoSlot { kTempoFlux, kTempoCurve, kTempoJobs, kTempoRecords, kTempoSlots };
 
 // Arrays handed to the caller, who frees them with mx_free.  add(): a fresh malloc block of n elements (at least one, so an
 // empty result is not a null pointer), copied from src or, src null, left for a download.  give(): every block is there and
@@ -258,6 +260,9 @@ struct mx_ctx {
   std::mutex f0_mu;
   mx::GrowBuf f0dec[mx::kF0DecSlots];
   int64_t f0_chunk = 0;
+  // device work buffers of the tempo estimate (capi_tempo.cpp), kept between calls like the staging buffers
+  std::mutex tempo_mu;
+  mx::GrowBuf tempo[mx::kTempoSlots];
   // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;

@@ -213,6 +213,14 @@ struct OnsetArgs {
 };
 int onset_default_run(int64_t count);
 hipError_t launch_onset_flux(const OnsetArgs &a, hipStream_t s);
+// Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
+// count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
+// range (the caller's check) gives a wrong record and nothing worse.
+namespace tempo { struct SmoothWeights; }
+hipError_t launch_tempo_smooth(const float *d_flux, int64_t count, int width, const tempo::SmoothWeights &w, float *d_out,
+                               hipStream_t s);
+hipError_t launch_tempo_comb(const float *d_curve, int64_t count, const mx_comb_job *d_jobs, int64_t njobs, mx_comb *d_out,
+                             hipStream_t s);
 // spec-cache.cpp:77-96 colormap: nbins_total magnitudes -> 3*nbins_total bytes (both device).
 hipError_t launch_colormap(const float *mags, uint8_t *rgb, int64_t nbins_total, float k, hipStream_t s);
 
