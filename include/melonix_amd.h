@@ -850,6 +850,114 @@ int mx_tempo_from_flux(mx_ctx *ctx, const float *flux, int64_t count, int sample
 int mx_tempo_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_onset_flux_params *fp,
                     const mx_tempo_params *p, mx_tempo *out, mx_tempo_window **windows, int64_t *nwindows);
 
+/* ---- Sibilant detection, protection and balance (BUILD-DEFINED; restated in f64 by tests/sibilant_ref.py) ----
+ * The pitch chain and the timing chain treat every frame that is not a tracked note alike.  Sibilants ("s", "sh", "z", "ch",
+ * "t" bursts) are the one class of such frames an editor must know: a formant shift moves them with the note (the lisp), and
+ * "sibilant balance" is the control next to the formant knob.  The YIN record cannot find them (aperiodicity separates voiced
+ * from unvoiced, not "s" from a breath); the separation is spectral.  The reference has nothing of the kind.
+ *
+ * Features.  The onset detector's frame: for frame h of the bulk indexing (h < mx_frame_count(n, hop)),
+ *   x_j = audio[h*hop - 512 + j], j < 1024, zeros outside the file;  w_j = 0.5 - 0.5 cos(2 pi j / 1024);
+ *   X_k = the 1024-point DFT of w x;  P_k = (|X_k| / 512)^2, in f32;  ks = clamp(ceil(split_hz * 1024 / sr), 1, 512);
+ *   low = sum_{k = 1..ks-1} P_k;  high = sum_{k = ks..511} P_k;
+ *   centroid = sum_{k = 1..511} k P_k / (low + high), in bins, 0 where low + high is 0;
+ *   zero_crossings = the number of j in 0..1022 with (x_j < 0) != (x_{j+1} < 0), on the raw samples: zeros, -0 and NaN count as
+ *   "not negative", so silence and the pad give 0.
+ * Bin 0 and bin 512 belong to neither sum.  ks = 1 makes low 0 for every frame, ks = 512 makes high 0.  The three sums have one
+ * fixed order, so a record depends on its frame's samples alone: the same bytes whatever first_frame, count or the run
+ * length a walker takes.  The launch writes 16 bytes per frame and no spectrum. */
+typedef struct mx_sib_feat {
+  float low, high;
+  float centroid; /* bins of 1024: Hz = centroid * sr / 1024 */
+  int32_t zero_crossings;
+} mx_sib_feat;
+typedef struct mx_sib_feature_params {
+  float split_hz; /* finite, in (0, sr / 2] */
+} mx_sib_feature_params;
+/* {3500.f} */
+void mx_sib_feature_params_default(mx_sib_feature_params *p);
+/* Frames [first_frame, first_frame + count) -> d_feat (count records in HBM).  Asynchronous on the context's stream.
+ * params NULL: the defaults.  MX_ERR_INVALID, before any launch, for sr <= 0, hop outside [1, 16384], frames outside the
+ * file or split_hz out of range. */
+int mx_sib_features_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                        const mx_sib_feature_params *params, mx_sib_feat *d_feat);
+/* Same, host output through the context's staging buffers.  Blocks. */
+int mx_sib_features(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                    const mx_sib_feature_params *params, mx_sib_feat *feat_out);
+
+/* Segments (host, binary64, exact).  Per frame s = (double)low + (double)high; where s is finite and > 0,
+ * level = sqrt(s) and share = (double)high / s, else both are 0.
+ *   a run opens at a frame with level >= level_floor, share >= share_on and zero_crossings >= zc_min, and continues while
+ *   level >= level_floor and share >= share_off (the frame that fails is not part of it);
+ *   runs with at most merge_gap frames between them become one (the frames between them included);
+ *   then runs of fewer than min_frames frames are dropped.
+ * start_sample / end_sample are the centres of the run's first and last frame; share is the mean of the run's frames' shares
+ * (binary64, ascending), level the maximum of their levels.  Runs come out in order and do not overlap.
+ * Defaults {0.6, 0.4, 1e-3, 64, 2, 6}: values that separate tests/sibilant_ref.py's synthetic take (vowels, "s", "sh", a soft
+ * "s", a breath, a click).  Nobody has tuned them on recordings.  Steady white noise IS a sibilant by this definition (more
+ * than half of its energy lies above 3.5 kHz): one segment over the whole take. */
+typedef struct mx_sibilant_params {
+  double share_on, share_off; /* in [0, 1], share_off <= share_on */
+  double level_floor;         /* finite, >= 0 */
+  int32_t zc_min;             /* [0, 1023] */
+  int32_t merge_gap;          /* frames, [0, 4096] */
+  int32_t min_frames;         /* [1, 4096] */
+} mx_sibilant_params;
+typedef struct mx_sibilant {
+  int32_t start_sample, end_sample; /* centres of the first and the last frame, absolute */
+  int32_t first_frame, frames;
+  float share, level;
+} mx_sibilant;
+void mx_sibilant_params_default(mx_sibilant_params *p);
+/* feat[i] is frame first_frame + i.  params NULL: the defaults.  *out is library-allocated (free with mx_free).
+ * MX_ERR_INVALID for a parameter out of range, hop < 1 or frame centres beyond int32 samples. */
+int mx_sibilants(const mx_sib_feat *feat, int64_t count, int hop, int64_t first_frame, const mx_sibilant_params *params,
+                 mx_sibilant **out, int64_t *nout);
+/* Features over the whole file and the segments from them.  Either params may be NULL.  Blocks. */
+int mx_sibilants_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_sib_feature_params *feature_params,
+                        const mx_sibilant_params *params, mx_sibilant **out, int64_t *nout);
+
+/* Spans (what protection and balance share).  Sibilants: 0 <= start_sample <= end_sample <= n - 1, each start_sample above
+ * the end_sample before it; n in [1, INT32_MAX]; ramp_samples >= 1 (and <= 2^30).  A sibilant whose start_sample - ramp is
+ * <= the end_sample + ramp of the span before it joins that span.  A span is {lo, start, end, hi}: start the first
+ * sibilant's start_sample, end the last one's end_sample (the core), lo = max(start - ramp, 0), hi = min(end + ramp, n - 1).
+ * A span gives the points lo (if lo < start), start, end (if end > start), hi (if hi > end): strictly increasing, and
+ * strictly above the span before.
+ *
+ * Protection (host, binary64).  F: the curve of mx_psola_plan_formant.  The result keeps every point of F outside all
+ * [lo, hi], and per span the points {lo, (float)F(lo)}, {start, 0}, {end, 0}, {hi, (float)F(hi)}: it equals F outside the
+ * spans (to the binary32 rounding of F(lo), F(hi)), is exactly 0 st on [start, end] and linear on the ramps.
+ * mx_psola_plan_formant accepts it as it is.  No points: no points.  No sibilants: the input.  *out is library-allocated.
+ * MX_ERR_INVALID for a bad curve, sibilants out of order or range, ramp_samples < 1. */
+int mx_formant_protect(const mx_formant_point *points, int npoints, const mx_sibilant *sibs, int64_t nsib, int32_t ramp_samples,
+                       int64_t n, mx_formant_point **out, int64_t *nout);
+
+/* Balance.  The gain is applied to the SOURCE, before any renderer: the granular resampler, the phase vocoder and PSOLA render
+ * the result untouched, and the f0 track of the original take stays valid (periods do not depend on level).
+ *   points    {sample, amp}: samples strictly increasing, amp finite and > 0 (the grain scan's zero crossings stay put).
+ *   gain      g(i) in binary64: the first point's amp for i below its sample, the last point's from its sample on, and for
+ *             s0 <= i < s1 between two points  g = a0 + (a1 - a0) * ((double)(i - s0) / (double)(s1 - s0)), no contraction.
+ *   output    out_i = (float)((double)x_i * g(i)).  The host, the device and numpy give the same bytes. */
+typedef struct mx_gain_point {
+  int32_t sample;
+  float amp;
+} mx_gain_point;
+/* A new audio object (free with mx_audio_free) of a's length with zeroed pads, like an upload; a is untouched.  npts == 0
+ * copies.  Checks every point and returns MX_ERR_INVALID before any launch, *out untouched.  Blocks. */
+int mx_audio_gain(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *points, int64_t npts, mx_audio **out);
+/* Same with the points in HBM.  Asynchronous on the context's stream (the points must stay until it has run).
+ * PRECONDITION (not checked on the device — mx_audio_gain does check it): the points as defined above.  Points that break it
+ * give wrong samples and nothing worse: nothing is stored outside samples [0, n) of the new object. */
+int mx_audio_gain_dev(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_points, int64_t npts, mx_audio **out);
+/* Samples [first, first + count) of an audio object into host memory; the pads are readable: first >= -MX_AUDIO_PAD,
+ * first + count <= n + MX_AUDIO_PAD.  Blocks. */
+int mx_audio_download(mx_ctx *ctx, const mx_audio *a, int64_t first, int64_t count, float *host_out);
+/* The points of a sibilant balance of db decibels (finite, in [-120, 40]): per span {lo, 1}, {start, A}, {end, A}, {hi, 1}
+ * with A = (float)pow(10, db / 20) in binary64.  No sibilants: no points.  *out is library-allocated.  MX_ERR_INVALID as
+ * mx_formant_protect, and for db out of range. */
+int mx_sibilant_gain_points(const mx_sibilant *sibs, int64_t nsib, double db, int32_t ramp_samples, int64_t n,
+                            mx_gain_point **out, int64_t *nout);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

@@ -17,6 +17,7 @@ from . import _capi
 from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, ONSET_DTYPE, PITCH_DTYPE,  # noqa: F401
                     PSOLA_FGRAIN_DTYPE, PSOLA_GRAIN_DTYPE, STEP_DTYPE, MxError)
 from ._capi import COMB_DTYPE, COMB_JOB_DTYPE, TEMPO_WINDOW_DTYPE  # noqa: F401
+from ._capi import GAIN_POINT_DTYPE, SIB_FEAT_DTYPE, SIBILANT_DTYPE  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
@@ -24,7 +25,9 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "PSOLA_GRAIN_DTYPE", "psola_params_default", "psola_plan",
            "PSOLA_FGRAIN_DTYPE", "FORMANT_POINT_DTYPE", "psola_plan_formant",
            "ONSET_DTYPE", "onset_flux_params_default", "onset_pick_params_default", "onset_pick", "timing_params_default",
-           "timing_markers", "COMB_JOB_DTYPE", "COMB_DTYPE", "TEMPO_WINDOW_DTYPE", "tempo_params_default"]
+           "timing_markers", "COMB_JOB_DTYPE", "COMB_DTYPE", "TEMPO_WINDOW_DTYPE", "tempo_params_default",
+           "SIB_FEAT_DTYPE", "SIBILANT_DTYPE", "GAIN_POINT_DTYPE", "sib_feature_params_default", "sibilant_params_default", "sibilants",
+           "formant_protect", "sibilant_gain_points"]
 
 
 def _ptr(a):
@@ -55,7 +58,9 @@ def _take_records(p, count: int, dtype):
 _PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "note": (_capi.NoteParams, "mx_note_params_default"),
            "psola": (_capi.PsolaParams, "mx_psola_params_default"), "flux": (_capi.OnsetFluxParams, "mx_onset_flux_params_default"),
            "pick": (_capi.OnsetPickParams, "mx_onset_pick_params_default"), "timing": (_capi.TimingParams, "mx_timing_params_default"),
-           "tempo": (_capi.TempoParams, "mx_tempo_params_default")}
+           "tempo": (_capi.TempoParams, "mx_tempo_params_default"),
+           "sib_feature": (_capi.SibFeatureParams, "mx_sib_feature_params_default"),
+           "sibilant": (_capi.SibilantParams, "mx_sibilant_params_default")}
 
 
 def _params_default(kind: str) -> dict:
@@ -105,6 +110,14 @@ def timing_params_default() -> dict:
 
 def tempo_params_default() -> dict:
     return _params_default("tempo")
+
+
+def sib_feature_params_default() -> dict:
+    return _params_default("sib_feature")
+
+
+def sibilant_params_default() -> dict:
+    return _params_default("sibilant")
 
 
 def pitch_band(N: int, sr: int = 48000):
@@ -408,6 +421,62 @@ class Context:
         _capi.check(_capi.lib().mx_onsets_detect(self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
                                                  _params_arg("pick", pick_params or {}), C.byref(out), C.byref(cnt)))
         return _take_records(out, cnt.value, ONSET_DTYPE)
+
+    # ---- sibilant features, segments, protection and balance (build-defined; include/melonix_amd.h) ----
+    sib_feature_params_default = staticmethod(sib_feature_params_default)
+    sibilant_params_default = staticmethod(sibilant_params_default)
+
+    def sib_features(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, **params):
+        """-> SIB_FEAT_DTYPE records of frames [first, first + count) (frame h centred on sample h*hop).  params: fields of
+        sib_feature_params_default()."""
+        count = _frames_from(audio, hop, first, count)
+        out = np.empty(max(count, 0), dtype=SIB_FEAT_DTYPE)
+        _capi.check(_capi.lib().mx_sib_features(self.handle, audio.handle, sr, hop, first, count, _params_arg("sib_feature", params),
+                                                _ptr(out)))
+        return out
+
+    def sib_features_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_feat: int, **params):
+        """The records stay in HBM at d_feat (count x 16 bytes); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_sib_features_dev(self.handle, audio.handle, sr, hop, first, count,
+                                                    _params_arg("sib_feature", params), C.c_void_p(d_feat or 0)))
+
+    def sibilants_detect(self, audio: Audio, sr: int, hop: int = 256, feature_params: dict | None = None, **params):
+        """Features over the whole file and the segments from them -> SIBILANT_DTYPE array.  params: fields of
+        sibilant_params_default()."""
+        out, cnt = C.c_void_p(), C.c_int64()
+        _capi.check(_capi.lib().mx_sibilants_detect(self.handle, audio.handle, sr, hop, _params_arg("sib_feature", feature_params or {}),
+                                                    _params_arg("sibilant", params), C.byref(out), C.byref(cnt)))
+        return _take_records(out, cnt.value, SIBILANT_DTYPE)
+
+    def sibilants(self, feat, hop: int = 256, first: int = 0, **params):
+        return sibilants(feat, hop, first, **params)
+
+    def formant_protect(self, points, sibs, ramp: int, n: int):
+        return formant_protect(points, sibs, ramp, n)
+
+    def sibilant_gain_points(self, sibs, db: float, ramp: int, n: int):
+        return sibilant_gain_points(sibs, db, ramp, n)
+
+    def audio_gain(self, audio: Audio, points) -> Audio:
+        """A new Audio: `audio` through the piecewise-linear gain of `points` ((sample, amp) pairs or a GAIN_POINT_DTYPE array;
+        none: a copy).  Blocks."""
+        pts = _gain_points(points)
+        h = C.c_void_p()
+        _capi.check(_capi.lib().mx_audio_gain(self.handle, audio.handle, _ptr(pts) if len(pts) else None, len(pts), C.byref(h)))
+        return Audio(self, h, audio.n)
+
+    def audio_gain_dev(self, audio: Audio, d_points: int, npts: int) -> Audio:
+        """The same with the points in HBM (not validated there); asynchronous on the context's stream."""
+        h = C.c_void_p()
+        _capi.check(_capi.lib().mx_audio_gain_dev(self.handle, audio.handle, C.c_void_p(d_points or 0), npts, C.byref(h)))
+        return Audio(self, h, audio.n)
+
+    def audio_download(self, audio: Audio, first: int = 0, count: int | None = None):
+        """Samples [first, first + count) of an Audio (count None: to the end of the file; the pads are readable) -> float32."""
+        count = audio.n - first if count is None else count
+        out = np.empty(max(count, 0), dtype=np.float32)
+        _capi.check(_capi.lib().mx_audio_download(self.handle, audio.handle, first, count, _ptr(out)))
+        return out
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
     def tempo_smooth(self, flux, width: int = 4):
@@ -851,3 +920,47 @@ def timing_markers(anchors, n: int, sr: int, base=None, **params):
                                               _params_arg("timing", params),
                                               _ptr(base) if len(base) else None, len(base), C.byref(out), C.byref(cnt)))
     return _take_records(out, cnt.value, MARKER_DTYPE)
+
+
+# ---- sibilant segments, protected formant curves, balance points (host; build-defined) ----
+def _records(items, dtype):
+    """Tuples, or an array of `dtype` -> a contiguous array of `dtype`."""
+    if isinstance(items, np.ndarray) and items.dtype == dtype:
+        return np.ascontiguousarray(items)
+    out = np.zeros(len(items), dtype=dtype)
+    for i, it in enumerate(items):
+        out[i] = tuple(it)
+    return out
+
+
+def _gain_points(points):
+    return _records(points, GAIN_POINT_DTYPE)
+
+
+def sibilants(feat, hop: int = 256, first: int = 0, **params):
+    """Segments of SIB_FEAT_DTYPE records (feat[0] = frame `first`) -> SIBILANT_DTYPE array.  params: fields of
+    sibilant_params_default()."""
+    feat = _records(feat, SIB_FEAT_DTYPE)
+    out, cnt = C.c_void_p(), C.c_int64()
+    _capi.check(_capi.lib().mx_sibilants(_ptr(feat) if len(feat) else None, len(feat), hop, first, _params_arg("sibilant", params),
+                                         C.byref(out), C.byref(cnt)))
+    return _take_records(out, cnt.value, SIBILANT_DTYPE)
+
+
+def formant_protect(points, sibs, ramp: int, n: int):
+    """A formant curve ((sample, semitones) pairs) held at 0 st across `sibs` (SIBILANT_DTYPE), `ramp` samples of linear
+    return either side -> FORMANT_POINT_DTYPE array that psola_plan_formant takes as it is."""
+    pts, sibs = _formant_points(points), _records(sibs, SIBILANT_DTYPE)
+    out, cnt = C.c_void_p(), C.c_int64()
+    _capi.check(_capi.lib().mx_formant_protect(_ptr(pts) if len(pts) else None, len(pts), _ptr(sibs) if len(sibs) else None, len(sibs),
+                                               int(ramp), int(n), C.byref(out), C.byref(cnt)))
+    return _take_records(out, cnt.value, FORMANT_POINT_DTYPE)
+
+
+def sibilant_gain_points(sibs, db: float, ramp: int, n: int):
+    """The gain points of a sibilant balance of `db` decibels -> GAIN_POINT_DTYPE array for Context.audio_gain."""
+    sibs = _records(sibs, SIBILANT_DTYPE)
+    out, cnt = C.c_void_p(), C.c_int64()
+    _capi.check(_capi.lib().mx_sibilant_gain_points(_ptr(sibs) if len(sibs) else None, len(sibs), float(db), int(ramp), int(n),
+                                                    C.byref(out), C.byref(cnt)))
+    return _take_records(out, cnt.value, GAIN_POINT_DTYPE)

@@ -121,6 +121,28 @@ class TempoWindow(C.Structure):
     _fields_ = [("first_frame", C.c_int32), ("frames", C.c_int32), ("bpm", C.c_float), ("score", C.c_float)]
 
 
+class SibFeat(C.Structure):
+    _fields_ = [("low", C.c_float), ("high", C.c_float), ("centroid", C.c_float), ("zero_crossings", C.c_int32)]
+
+
+class SibFeatureParams(C.Structure):
+    _fields_ = [("split_hz", C.c_float)]
+
+
+class SibilantParams(C.Structure):
+    _fields_ = [("share_on", C.c_double), ("share_off", C.c_double), ("level_floor", C.c_double), ("zc_min", C.c_int32),
+                ("merge_gap", C.c_int32), ("min_frames", C.c_int32)]
+
+
+class Sibilant(C.Structure):
+    _fields_ = [("start_sample", C.c_int32), ("end_sample", C.c_int32), ("first_frame", C.c_int32), ("frames", C.c_int32),
+                ("share", C.c_float), ("level", C.c_float)]
+
+
+class GainPoint(C.Structure):
+    _fields_ = [("sample", C.c_int32), ("amp", C.c_float)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -145,6 +167,12 @@ COMB_DTYPE = np.dtype([("score", "<f4"), ("phase", "<i4"), ("prev", "<f4"), ("ne
 TEMPO_WINDOW_DTYPE = np.dtype([("first_frame", "<i4"), ("frames", "<i4"), ("bpm", "<f4"), ("score", "<f4")])
 assert COMB_JOB_DTYPE.itemsize == C.sizeof(CombJob) == 12 and COMB_DTYPE.itemsize == C.sizeof(Comb) == 16
 assert TEMPO_WINDOW_DTYPE.itemsize == C.sizeof(TempoWindow) == 16 and C.sizeof(TempoParams) == 56 and C.sizeof(Tempo) == 40
+SIB_FEAT_DTYPE = np.dtype([("low", "<f4"), ("high", "<f4"), ("centroid", "<f4"), ("zero_crossings", "<i4")])
+SIBILANT_DTYPE = np.dtype([("start_sample", "<i4"), ("end_sample", "<i4"), ("first_frame", "<i4"), ("frames", "<i4"),
+                           ("share", "<f4"), ("level", "<f4")])
+GAIN_POINT_DTYPE = np.dtype([("sample", "<i4"), ("amp", "<f4")])
+assert SIB_FEAT_DTYPE.itemsize == C.sizeof(SibFeat) == 16 and SIBILANT_DTYPE.itemsize == C.sizeof(Sibilant) == 24
+assert GAIN_POINT_DTYPE.itemsize == C.sizeof(GainPoint) == 8 and C.sizeof(SibilantParams) == 40
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -270,6 +298,18 @@ SIGNATURES = {
                                 C.POINTER(_i64)]),
     "mx_tempo_detect": (_i, [_vp, _vp, _i, _i, C.POINTER(OnsetFluxParams), C.POINTER(TempoParams), C.POINTER(Tempo),
                              C.POINTER(_vp), C.POINTER(_i64)]),
+    "mx_sib_feature_params_default": (None, [C.POINTER(SibFeatureParams)]),
+    "mx_sib_features_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, C.POINTER(SibFeatureParams), _vp]),
+    "mx_sib_features": (_i, [_vp, _vp, _i, _i, _i64, _i64, C.POINTER(SibFeatureParams), _vp]),
+    "mx_sibilant_params_default": (None, [C.POINTER(SibilantParams)]),
+    "mx_sibilants": (_i, [_vp, _i64, _i, _i64, C.POINTER(SibilantParams), C.POINTER(_vp), C.POINTER(_i64)]),
+    "mx_sibilants_detect": (_i, [_vp, _vp, _i, _i, C.POINTER(SibFeatureParams), C.POINTER(SibilantParams), C.POINTER(_vp),
+                                 C.POINTER(_i64)]),
+    "mx_formant_protect": (_i, [_vp, _i, _vp, _i64, C.c_int32, _i64, C.POINTER(_vp), C.POINTER(_i64)]),
+    "mx_audio_gain": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "mx_audio_gain_dev": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "mx_audio_download": (_i, [_vp, _vp, _i64, _i64, _vp]),
+    "mx_sibilant_gain_points": (_i, [_vp, _i64, _d, C.c_int32, _i64, C.POINTER(_vp), C.POINTER(_i64)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

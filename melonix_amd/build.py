@@ -47,6 +47,10 @@ UNITS = [
     ("onset_kernels.hip", "hip", ["-ffp-contract=off"]),
     # build-defined tempo estimation: f32 products rounded before a binary64 running sum (tempo_core.h), bit for bit the host's
     ("tempo_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined sibilant features: the onset transform with another tail (sibilant_core.h), every rounding as written
+    ("sibilant_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined source gain: a binary64 product rounded before the sum (gain_core.h), bit for bit numpy's
+    ("gain_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -59,12 +63,14 @@ UNITS = [
     ("capi_psola.cpp", "hip", []),
     ("capi_onset.cpp", "hip", []),
     ("capi_tempo.cpp", "hip", []),
+    ("capi_sibilant.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
     ("psola_plan.cpp", "cxx", ["-ffp-contract=off"]),
     ("onset_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("tempo_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("sibilant_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

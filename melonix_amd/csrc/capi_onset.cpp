@@ -42,21 +42,6 @@ int flux_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t 
   return MX_OK;
 }
 
-// W1024^j = e^{-2 pi i j / 1024}, j < 1024, rounded from binary64: built on the context's first flux call, kept until it goes
-int onset_table(mx_ctx *ctx, const float2 **out) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!ctx->onset_tw) {
-    std::vector<float2> tw(1024);
-    for (int j = 0; j < 1024; ++j) {
-      const double ang = -2.0 * M_PI * (double)j / 1024.0;
-      tw[(size_t)j] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
-    if (const int rc = upload_table(tw, &ctx->onset_tw)) return rc;
-  }
-  *out = ctx->onset_tw;
-  return MX_OK;
-}
-
 int flux_launch(const FluxCall &q, float *d_flux) {
   if (q.count == 0) return MX_OK;
   HIP_TRY(hipSetDevice(q.ctx->device));
@@ -93,6 +78,25 @@ int pick_params(const mx_onset_pick_params *p, mx_onset_pick_params &out) {
 }
 
 }  // namespace
+
+namespace mx {
+
+// W1024^j = e^{-2 pi i j / 1024}, j < 1024, rounded from binary64: built on the context's first flux call, kept until it goes
+int onset_table(mx_ctx *ctx, const float2 **out) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!ctx->onset_tw) {
+    std::vector<float2> tw(1024);
+    for (int j = 0; j < 1024; ++j) {
+      const double ang = -2.0 * M_PI * (double)j / 1024.0;
+      tw[(size_t)j] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+    }
+    if (const int rc = upload_table(tw, &ctx->onset_tw)) return rc;
+  }
+  *out = ctx->onset_tw;
+  return MX_OK;
+}
+
+}  // namespace mx
 
 extern "C" {
 

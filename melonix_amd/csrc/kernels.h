@@ -213,6 +213,22 @@ struct OnsetArgs {
 };
 int onset_default_run(int64_t count);
 hipError_t launch_onset_flux(const OnsetArgs &a, hipStream_t s);
+// Build-defined sibilant features (sibilant_kernels.hip; definition: include/melonix_amd.h, arithmetic: sibilant_core.h on
+// onset_core.h's transform).  Frames as OnsetArgs; out[f] the record of frame first_frame + f.  1 <= ks <= 512: checked by the caller.
+struct SibArgs {
+  const float *audio;  // padded image (zeros in the pads)
+  int hop;
+  int64_t first_frame;
+  int64_t count;
+  int ks;
+  const float2 *tw;  // the onset transform's table
+  mx_sib_feat *out;
+  int run;  // consecutive frames per wavefront; 0: onset_default_run's.  The output does not depend on it
+};
+hipError_t launch_sib_features(const SibArgs &a, hipStream_t s);
+// Build-defined source gain (gain_kernels.hip; definition: include/melonix_amd.h).  dst: samples [0, n) of the new object
+// (16-byte aligned, as src).  The points are not validated on the device: bad ones give wrong samples, no store outside [0, n).
+hipError_t launch_audio_gain(const float *src, float *dst, int64_t n, const mx_gain_point *pts, int64_t npts, hipStream_t s);
 // Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
 // count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
 // range (the caller's check) gives a wrong record and nothing worse.
