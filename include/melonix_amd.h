@@ -958,6 +958,102 @@ int mx_audio_download(mx_ctx *ctx, const mx_audio *a, int64_t first, int64_t cou
 int mx_sibilant_gain_points(const mx_sibilant *sibs, int64_t nsib, double db, int32_t ramp_samples, int64_t n,
                             mx_gain_point **out, int64_t *nout);
 
+/* ---- Key, scale and tuning reference (BUILD-DEFINED; restated in f64 by tests/key_ref.py) ----
+ * mx_correction_markers takes its scale from the caller and its grid from A = 440 Hz.  This section finds both in the audio:
+ * the evidence is a chromagram of whatever the editor has loaded (the accompaniment or the mix says more about the key than a
+ * monophonic f0 track), with a cheap host path from the detected notes for dry solo takes.  The reference has no detector.
+ *
+ * Chroma record.  Frame h of the bulk indexing (h < mx_frame_count(n, hop)) is centred on sample h*hop:
+ *   x_j = audio[h*hop - 2048 + j], j < 4096, zeros outside the file;  w_j = 0.5 - 0.5 cos(2 pi j / 4096);
+ *   X = the 4096-point DFT of w x;  m[k] = |X_k| / 1024 (a unit sine reads 1), in f32.
+ *   band   kmin = max(2, ceil(fmin * 4096 / sr)), kmax = min(2046, floor(fmax * 4096 / sr)); kmin > kmax: MX_ERR_INVALID.
+ *   peaks  bin k of the band is a peak when m[k] > m[k-1], m[k] >= m[k+1] and m[k] >= max(floor, rel * max of m over the band).
+ *   place  delta = (a - c) / (2 (a - 2b + c)) on a, b, c = ln m[k-1], ln m[k], ln m[k+1], clamped to [-1/2, 1/2]; 0 where the
+ *          denominator is not negative or a logarithm is not finite.  f = (k + delta) * sr / 4096; cents = 1200 log2(f / 55).
+ *   record forty floats.  A peak weighs m[k].  Columns 0..35: a pitch-class profile of 36 bins, bin b centred 100 b / 3 cents
+ *          above A (A = 0 as everywhere here); the peak at p = (cents mod 1200) / (100 / 3) adds m[k] * max(0, 1 - d/2) / 2
+ *          to every bin at circular distance d = |p - b| < 2 — a partition of unity, so columns 0..35 sum to column 38.
+ *          Columns 36, 37: the tuning phasor sum m cos t, sum m sin t, t = 2 pi (cents/100 - rint(cents/100)).  Column 38: sum m.
+ *          Column 39: the number of peaks.  Every sum runs over the frame's peaks in ascending k.
+ * A silent frame gives forty exact zeros.  So does a frame that holds an Inf or a NaN sample, and one whose band maximum
+ * overflows f32: a record is never Inf or NaN.  A record depends on its frame's samples alone: the same bytes whatever
+ * first_frame, count, the launch split or the pinned run length.  The launch writes 160 bytes per frame and no spectrum.
+ * Defaults {100, 5000, 1e-4, 0.05}: the relative floor sits above a Hann window's highest side lobe (-31.5 dB).  Untuned. */
+typedef struct mx_chroma_rec {
+  float pcp[36];
+  float tune_cos, tune_sin;
+  float weight;
+  float peaks;
+} mx_chroma_rec;
+typedef struct mx_chroma_params {
+  float fmin, fmax; /* Hz, finite, 0 < fmin <= fmax */
+  float floor;      /* finite, >= 0 */
+  float rel;        /* in [0, 1] */
+} mx_chroma_params;
+void mx_chroma_params_default(mx_chroma_params *p);
+/* Frames [first_frame, first_frame + count) -> d_out (count records in HBM).  Asynchronous on the context's stream.
+ * params NULL: the defaults.  MX_ERR_INVALID, before any launch, for sr <= 0, hop outside [1, 16384], frames outside the
+ * file, a parameter out of range or an empty band. */
+int mx_chroma_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                  const mx_chroma_params *params, mx_chroma_rec *d_out);
+/* Same, host output through the context's staging buffers.  Blocks. */
+int mx_chroma(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+              const mx_chroma_params *params, mx_chroma_rec *out);
+
+/* Sums over frame windows.  Job j gives 40 binary64 values: column c summed over records first_frame .. first_frame +
+ * frames - 1 in ascending order, each f32 widened first, a value that is not finite counting as 0.  No tolerance: the device,
+ * the host form and tests/key_ref.py give the same bytes.  A job must lie inside the `count` records (first_frame >= 0,
+ * frames >= 0, first_frame + frames <= count): mx_chroma_sum checks it (MX_ERR_INVALID before any launch); the device form
+ * cannot see its jobs and clips them to the records instead — a bad job gives a wrong sum and nothing worse. */
+typedef struct mx_chroma_job {
+  int64_t first_frame, frames;
+} mx_chroma_job;
+int mx_chroma_sum_dev(mx_ctx *ctx, const mx_chroma_rec *d_chroma, int64_t count, const mx_chroma_job *d_jobs, int64_t njobs,
+                      double *d_out);
+int mx_chroma_sum(mx_ctx *ctx, const mx_chroma_rec *chroma, int64_t count, const mx_chroma_job *jobs, int64_t njobs, double *out);
+
+/* Key (host, binary64, exact: tests/key_ref.py does the same operations in the same order).  From a 40-value sum S, values
+ * that are not finite read as 0:
+ *   tuning_cents = 100 / (2 pi) * atan2(S37, S36), in (-50, 50]; tuning_confidence = sqrt(S36^2 + S37^2) / S38; both 0 where S38
+ *   is not positive or the phasor is 0.
+ *   The twelve-class profile is read at that tuning: p[c] = sum_b S_b * max(0, 1 - d / 2), d the circular distance of b from
+ *   (100 c + tuning) / (100 / 3) over 36 bins.  p is Pearson-correlated with the 24 rotations of the Krumhansl-Kessler profiles
+ *     major 6.35 2.23 3.48 2.33 4.38 4.09 2.52 5.19 2.39 3.66 2.29 2.88,  minor 6.33 2.68 3.52 5.38 2.60 3.53 2.54 4.75 3.98 2.69 3.34 3.17
+ *   in the order major before minor, then ascending tonic; the first candidate that attains the maximum wins.
+ *   correlation: the winner's; clarity: the winner's minus the best of the other 23; scale_mask: the winner's seven diatonic
+ *   classes (major 0 2 4 5 7 9 11, natural minor 0 2 3 5 7 8 10 above the tonic) in mx_correction_markers' bit numbering.
+ * A flat or empty profile gives tonic 0, mode 0, scale_mask 0, correlation 0, clarity 0: "don't know", which the marker calls
+ * read as all twelve classes.  The profiles and the defaults above are untuned; nothing here was run on recordings. */
+typedef struct mx_key {
+  int32_t tonic;      /* 0..11, A = 0 */
+  int32_t mode;       /* 0 major, 1 natural minor */
+  int32_t scale_mask; /* for mx_correction_markers / mx_correction_markers_tuned */
+  int32_t reserved;   /* 0 */
+  double tuning_cents, tuning_confidence;
+  double correlation, clarity;
+} mx_key;
+typedef struct mx_key_window {
+  int32_t first_frame, frames;
+  mx_key key;
+} mx_key_window;
+int mx_key_from_chroma(const double *sum40, mx_key *out);
+/* The same estimate from mx_detect_notes' output, for dry solo takes.  A note weighs its `frames` (none where frames <= 0);
+ * the phasor is taken from the notes' fractional parts, t = 2 pi (note - rint(note)); the profile is p[rint(note - tuning / 100)
+ * mod 12] += frames.  The notes may overlap or be out of order.  MX_ERR_INVALID for a note that is not finite. */
+int mx_key_from_notes(const mx_note *notes, int64_t count, mx_key *out);
+/* The whole file: mx_chroma_dev, then mx_chroma_sum_dev over the windows and over the whole take, in device memory of the call;
+ * what comes back is 320 bytes per job.  Window w covers frames [w * window_hop, w * window_hop + window_frames) cut at the
+ * file's end, w = 0, 1, .. while w * window_hop lies inside the file; window_frames 0 or windows NULL: no windows (window_hop
+ * >= 1 otherwise).  *key: the take's.  *windows is library-allocated (free with mx_free).  params NULL: the defaults.  A hop of
+ * 2048 is plenty: key needs no 5 ms resolution.  Blocks. */
+int mx_key_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_chroma_params *params,
+                  int64_t window_frames, int64_t window_hop, mx_key *key, mx_key_window **windows, int64_t *nwindows);
+/* mx_correction_markers on a grid tuning_cents (finite, in [-50, 50]) above A = 440 Hz: the target of a note is
+ * snap(note - t / 100) + t / 100 with mx_correction_markers' snap, t = tuning_cents; everything else as there.  With
+ * tuning_cents 0 the output is mx_correction_markers', byte for byte. */
+int mx_correction_markers_tuned(const mx_note *notes, int64_t count, double strength, int scale_mask, double tuning_cents,
+                                mx_marker *out);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

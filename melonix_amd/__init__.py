@@ -18,6 +18,7 @@ from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, 
                     PSOLA_FGRAIN_DTYPE, PSOLA_GRAIN_DTYPE, STEP_DTYPE, MxError)
 from ._capi import COMB_DTYPE, COMB_JOB_DTYPE, TEMPO_WINDOW_DTYPE  # noqa: F401
 from ._capi import GAIN_POINT_DTYPE, SIB_FEAT_DTYPE, SIBILANT_DTYPE  # noqa: F401
+from ._capi import CHROMA_COLS, CHROMA_JOB_DTYPE, KEY_DTYPE, KEY_WINDOW_DTYPE  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
@@ -27,7 +28,9 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "ONSET_DTYPE", "onset_flux_params_default", "onset_pick_params_default", "onset_pick", "timing_params_default",
            "timing_markers", "COMB_JOB_DTYPE", "COMB_DTYPE", "TEMPO_WINDOW_DTYPE", "tempo_params_default",
            "SIB_FEAT_DTYPE", "SIBILANT_DTYPE", "GAIN_POINT_DTYPE", "sib_feature_params_default", "sibilant_params_default", "sibilants",
-           "formant_protect", "sibilant_gain_points"]
+           "formant_protect", "sibilant_gain_points",
+           "CHROMA_COLS", "CHROMA_JOB_DTYPE", "KEY_DTYPE", "KEY_WINDOW_DTYPE", "chroma_params_default", "key_from_chroma",
+           "key_from_notes", "correction_markers_tuned"]
 
 
 def _ptr(a):
@@ -60,7 +63,8 @@ _PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "not
            "pick": (_capi.OnsetPickParams, "mx_onset_pick_params_default"), "timing": (_capi.TimingParams, "mx_timing_params_default"),
            "tempo": (_capi.TempoParams, "mx_tempo_params_default"),
            "sib_feature": (_capi.SibFeatureParams, "mx_sib_feature_params_default"),
-           "sibilant": (_capi.SibilantParams, "mx_sibilant_params_default")}
+           "sibilant": (_capi.SibilantParams, "mx_sibilant_params_default"),
+           "chroma": (_capi.ChromaParams, "mx_chroma_params_default")}
 
 
 def _params_default(kind: str) -> dict:
@@ -118,6 +122,10 @@ def sib_feature_params_default() -> dict:
 
 def sibilant_params_default() -> dict:
     return _params_default("sibilant")
+
+
+def chroma_params_default() -> dict:
+    return _params_default("chroma")
 
 
 def pitch_band(N: int, sr: int = 48000):
@@ -450,6 +458,44 @@ class Context:
 
     def sibilants(self, feat, hop: int = 256, first: int = 0, **params):
         return sibilants(feat, hop, first, **params)
+
+    # ---- chroma records, their window sums, key / scale / tuning (build-defined; include/melonix_amd.h) ----
+    chroma_params_default = staticmethod(chroma_params_default)
+
+    def chroma(self, audio: Audio, sr: int, hop: int = 2048, first: int = 0, count: int | None = None, **params):
+        """-> (count, 40) float32: the chroma records of frames [first, first + count) (frame h centred on sample h*hop).
+        params: fields of chroma_params_default()."""
+        count = _frames_from(audio, hop, first, count)
+        out = np.empty((max(count, 0), CHROMA_COLS), dtype=np.float32)
+        _capi.check(_capi.lib().mx_chroma(self.handle, audio.handle, sr, hop, first, count, _params_arg("chroma", params), _ptr(out)))
+        return out
+
+    def chroma_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_out: int, **params):
+        """The records stay in HBM at d_out (count x 160 bytes); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_chroma_dev(self.handle, audio.handle, sr, hop, first, count, _params_arg("chroma", params),
+                                              C.c_void_p(d_out or 0)))
+
+    def chroma_sum(self, chroma, jobs):
+        """Column sums of (count, 40) float32 records over `jobs` ((first_frame, frames) pairs) -> (njobs, 40) float64."""
+        rec = np.ascontiguousarray(chroma, dtype=np.float32).reshape(-1, CHROMA_COLS)
+        jobs = _records(jobs, CHROMA_JOB_DTYPE)
+        out = np.empty((len(jobs), CHROMA_COLS), dtype=np.float64)
+        _capi.check(_capi.lib().mx_chroma_sum(self.handle, _ptr(rec) if len(rec) else None, len(rec), _ptr(jobs) if len(jobs) else None,
+                                              len(jobs), _ptr(out) if len(jobs) else None))
+        return out
+
+    def chroma_sum_dev(self, d_chroma: int, count: int, d_jobs: int, njobs: int, d_out: int):
+        """The same with records, jobs and sums (njobs x 320 bytes) in HBM; asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_chroma_sum_dev(self.handle, C.c_void_p(d_chroma or 0), count, C.c_void_p(d_jobs or 0), njobs,
+                                                  C.c_void_p(d_out or 0)))
+
+    def key_detect(self, audio: Audio, sr: int, hop: int = 2048, window_frames: int = 0, window_hop: int = 1, **params):
+        """Key, scale and tuning of the whole file -> (dict of KEY_DTYPE's fields, KEY_WINDOW_DTYPE array: one key per window
+        of window_frames frames every window_hop; none where window_frames is 0).  params: fields of chroma_params_default()."""
+        key, out, cnt = _capi.Key(), C.c_void_p(), C.c_int64()
+        _capi.check(_capi.lib().mx_key_detect(self.handle, audio.handle, sr, hop, _params_arg("chroma", params), int(window_frames),
+                                              int(window_hop), C.byref(key), C.byref(out), C.byref(cnt)))
+        return _key_dict(key), _take_records(out, cnt.value, KEY_WINDOW_DTYPE)
 
     def formant_protect(self, points, sibs, ramp: int, n: int):
         return formant_protect(points, sibs, ramp, n)
@@ -840,6 +886,38 @@ def correction_markers(notes, strength: float = 1.0, scale_mask: int = 0):
     _capi.check(_capi.lib().mx_correction_markers(_ptr(notes) if len(notes) else None, len(notes), float(strength),
                                                   int(scale_mask), _ptr(out) if len(out) else None))
     return out
+
+
+def correction_markers_tuned(notes, strength: float = 1.0, scale_mask: int = 0, tuning_cents: float = 0.0):
+    """correction_markers on a grid `tuning_cents` above A = 440 Hz (key_detect's or key_from_notes' tuning_cents)."""
+    notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    out = np.zeros(2 * len(notes), dtype=MARKER_DTYPE)
+    _capi.check(_capi.lib().mx_correction_markers_tuned(_ptr(notes) if len(notes) else None, len(notes), float(strength),
+                                                        int(scale_mask), float(tuning_cents), _ptr(out) if len(out) else None))
+    return out
+
+
+# ---- key, scale and tuning (host; build-defined) ----
+def _key_dict(key) -> dict:
+    return {k: getattr(key, k) for k, _ in _capi.Key._fields_ if k != "reserved"}
+
+
+def key_from_chroma(sum40) -> dict:
+    """The key estimate from a 40-value chroma sum (Context.chroma_sum) -> dict of KEY_DTYPE's fields."""
+    s = np.ascontiguousarray(sum40, dtype=np.float64)
+    if s.shape != (CHROMA_COLS,):
+        raise ValueError("a chroma sum is 40 values")
+    key = _capi.Key()
+    _capi.check(_capi.lib().mx_key_from_chroma(_ptr(s), C.byref(key)))
+    return _key_dict(key)
+
+
+def key_from_notes(notes) -> dict:
+    """The key estimate from detect_notes' output (NOTE_DTYPE), each note weighing its frames."""
+    notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    key = _capi.Key()
+    _capi.check(_capi.lib().mx_key_from_notes(_ptr(notes) if len(notes) else None, len(notes), C.byref(key)))
+    return _key_dict(key)
 
 
 # ---- PSOLA planning (host; build-defined) ----

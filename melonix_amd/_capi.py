@@ -143,6 +143,24 @@ class GainPoint(C.Structure):
     _fields_ = [("sample", C.c_int32), ("amp", C.c_float)]
 
 
+class ChromaParams(C.Structure):
+    _fields_ = [("fmin", C.c_float), ("fmax", C.c_float), ("floor", C.c_float), ("rel", C.c_float)]
+
+
+class ChromaJob(C.Structure):
+    _fields_ = [("first_frame", C.c_int64), ("frames", C.c_int64)]
+
+
+class Key(C.Structure):
+    _fields_ = [("tonic", C.c_int32), ("mode", C.c_int32), ("scale_mask", C.c_int32), ("reserved", C.c_int32),
+                ("tuning_cents", C.c_double), ("tuning_confidence", C.c_double), ("correlation", C.c_double),
+                ("clarity", C.c_double)]
+
+
+class KeyWindow(C.Structure):
+    _fields_ = [("first_frame", C.c_int32), ("frames", C.c_int32), ("key", Key)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -173,6 +191,13 @@ SIBILANT_DTYPE = np.dtype([("start_sample", "<i4"), ("end_sample", "<i4"), ("fir
 GAIN_POINT_DTYPE = np.dtype([("sample", "<i4"), ("amp", "<f4")])
 assert SIB_FEAT_DTYPE.itemsize == C.sizeof(SibFeat) == 16 and SIBILANT_DTYPE.itemsize == C.sizeof(Sibilant) == 24
 assert GAIN_POINT_DTYPE.itemsize == C.sizeof(GainPoint) == 8 and C.sizeof(SibilantParams) == 40
+CHROMA_COLS = 40  # a chroma record: 36 profile bins, the tuning phasor, the summed weight, the number of peaks
+CHROMA_JOB_DTYPE = np.dtype([("first_frame", "<i8"), ("frames", "<i8")])
+KEY_DTYPE = np.dtype([("tonic", "<i4"), ("mode", "<i4"), ("scale_mask", "<i4"), ("reserved", "<i4"), ("tuning_cents", "<f8"),
+                      ("tuning_confidence", "<f8"), ("correlation", "<f8"), ("clarity", "<f8")])
+KEY_WINDOW_DTYPE = np.dtype([("first_frame", "<i4"), ("frames", "<i4"), ("key", KEY_DTYPE)])
+assert CHROMA_JOB_DTYPE.itemsize == C.sizeof(ChromaJob) == 16 and C.sizeof(ChromaParams) == 16
+assert KEY_DTYPE.itemsize == C.sizeof(Key) == 48 and KEY_WINDOW_DTYPE.itemsize == C.sizeof(KeyWindow) == 56
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -310,6 +335,16 @@ SIGNATURES = {
     "mx_audio_gain_dev": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_vp)]),
     "mx_audio_download": (_i, [_vp, _vp, _i64, _i64, _vp]),
     "mx_sibilant_gain_points": (_i, [_vp, _i64, _d, C.c_int32, _i64, C.POINTER(_vp), C.POINTER(_i64)]),
+    "mx_chroma_params_default": (None, [C.POINTER(ChromaParams)]),
+    "mx_chroma_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, C.POINTER(ChromaParams), _vp]),
+    "mx_chroma": (_i, [_vp, _vp, _i, _i, _i64, _i64, C.POINTER(ChromaParams), _vp]),
+    "mx_chroma_sum_dev": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "mx_chroma_sum": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "mx_key_from_chroma": (_i, [_vp, C.POINTER(Key)]),
+    "mx_key_from_notes": (_i, [_vp, _i64, C.POINTER(Key)]),
+    "mx_key_detect": (_i, [_vp, _vp, _i, _i, C.POINTER(ChromaParams), _i64, _i64, C.POINTER(Key), C.POINTER(_vp),
+                           C.POINTER(_i64)]),
+    "mx_correction_markers_tuned": (_i, [_vp, _i64, _d, _i, _d, _vp]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

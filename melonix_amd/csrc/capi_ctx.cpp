@@ -220,6 +220,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     for (auto &kv : ctx->tables) free_tables(kv.second);
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
     hipFree(ctx->onset_tw);
+    hipFree(ctx->chroma_hann);
     for (auto &st : ctx->stage) st.drop();
     for (auto &st : ctx->chain) st.drop();
     for (auto &st : ctx->f0dec) st.drop();

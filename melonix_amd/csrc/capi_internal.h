@@ -244,13 +244,14 @@ struct mx_ctx {
   std::map<std::pair<int, int>, float *> wtabs;  // (N, hop) -> forward weights
   int frames_per_block = 0;  // 0 = per-N default
   float2 *onset_tw = nullptr;  // the 1024-point transform's twiddles (onset_table), built on first use under mu
+  float *chroma_hann = nullptr;  // the chroma frame's window (chroma_window), built on first use under mu
   std::mutex mu;
   // host landing zone of the zero-crossing bitmaps (mx_grains_dev), kept between calls: a copy into
   // pages that are already mapped runs at PCIe rate, a fresh 2 x n/8-byte buffer pays ~3 ms of faults
   std::mutex zc_mu;
   mx::ZcBitmaps zc_scratch;
   // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
-  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features), kept between calls.  One host-staged call per context at a time.
+  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_chroma), kept between calls.  One host-staged call per context at a time.
   std::mutex stage_mu;
   mx::GrowBuf stage[mx::kStageSlots];
   // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)
@@ -296,6 +297,9 @@ int frame_span(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t first_fram
 // The 1024-point transform's twiddle table (capi_onset.cpp): W1024^j, j < 1024, in HBM, built on the context's first use and kept
 // until it goes.  Onset strength and sibilant features share it.
 int onset_table(mx_ctx *ctx, const float2 **out);
+// The chroma frame's window (capi_key.cpp): periodic Hann over 4096 samples, pre-scaled by 1/2048, in HBM, built on the context's
+// first use and kept until it goes.
+int chroma_window(mx_ctx *ctx, const float **out);
 int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_t first_frame, const int32_t *d_ranges,
                 int64_t count, int kmin, int kmax, float *d_mags, mx_pitch *d_pitch, uint8_t *d_rgb, float cmap_k,
                 int run_length = 0);

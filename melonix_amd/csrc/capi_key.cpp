@@ -1,0 +1,245 @@
+// capi_key.cpp — chroma records and their window sums (chroma_kernels.hip), the key, scale and tuning estimate and the tuned
+// correction markers (key_logic.cpp): BUILD-DEFINED, the reference has none of it.  One unit of the C-ABI implementation behind
+// include/melonix_amd.h (see capi_internal.h).
+#include "capi_internal.h"
+#include "chroma_core.h"
+#include "key_logic.h"
+
+using namespace mx;
+
+namespace {
+
+const mx_chroma_params kChromaDefaults{100.f, 5000.f, 1e-4f, 0.05f};
+
+// What the chroma entry points share: their arguments, checked, and the band they give
+struct ChromaCall {
+  mx_ctx *ctx;
+  const mx_audio *a;
+  int sampleRate, hop;
+  int64_t first_frame, count;
+  int kmin, kmax;
+  mx_chroma_params p;
+};
+
+int chroma_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                 const mx_chroma_params *params, const void *out, ChromaCall &q) {
+  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
+  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  const mx_chroma_params p = params_or(params, kChromaDefaults);
+  if (!std::isfinite(p.fmin) || !std::isfinite(p.fmax) || !(p.fmin > 0.f) || !(p.fmax >= p.fmin))
+    return fail(MX_ERR_INVALID, "chroma band [%g, %g] Hz: finite, 0 < fmin <= fmax", (double)p.fmin, (double)p.fmax);
+  if (!std::isfinite(p.floor) || p.floor < 0.f) return fail(MX_ERR_INVALID, "floor %g must be finite and >= 0", (double)p.floor);
+  if (!(p.rel >= 0.f && p.rel <= 1.f)) return fail(MX_ERR_INVALID, "rel %g outside [0, 1]", (double)p.rel);
+  const double sr = (double)sampleRate, n = (double)chroma::kN;
+  const int kmin = (int)std::max(2.0, std::min(std::ceil((double)p.fmin * n / sr), 1e9));
+  const int kmax = (int)std::min((double)(chroma::kBins - 2), std::floor((double)p.fmax * n / sr));
+  if (kmin > kmax)
+    return fail(MX_ERR_INVALID, "empty band: bins [%d, %d] for %g..%g Hz at %d Hz", kmin, kmax, (double)p.fmin, (double)p.fmax, sampleRate);
+  q = ChromaCall{ctx, a, sampleRate, hop, first_frame, count, kmin, kmax, p};
+  return MX_OK;
+}
+
+int chroma_launch(const ChromaCall &q, mx_chroma_rec *d_out) {
+  if (q.count == 0) return MX_OK;
+  HIP_TRY(hipSetDevice(q.ctx->device));
+  NTables t;
+  if (const int rc = get_tables(q.ctx, 4096, t)) return rc;
+  ChromaArgs g{};
+  if (const int rc = chroma_window(q.ctx, &g.hann)) return rc;
+  g.audio = q.a->d_padded;
+  g.hop = q.hop;
+  g.first_frame = q.first_frame;
+  g.count = q.count;
+  g.kmin = q.kmin;
+  g.kmax = q.kmax;
+  g.floor_abs = q.p.floor;
+  g.rel = q.p.rel;
+  g.bin_hz = (float)q.sampleRate / (float)chroma::kN;
+  g.tw2 = t.tw2;
+  g.tw3 = t.tw3;
+  g.ubase = t.ubase;
+  g.out = d_out;
+  g.frames_per_block = q.ctx->frames_per_block > 0 ? q.ctx->frames_per_block : 0;  // (the context's pinned run length; the bytes do not depend on it)
+  HIP_TRY(launch_chroma(g, q.ctx->stream));
+  return MX_OK;
+}
+
+// the host form (staged_records): the records pass through the context's staging buffer of the magnitude rows
+int chroma_host(const ChromaCall &q, mx_chroma_rec *out) {
+  const StagedSlot slots[] = {{kStageMags, sizeof(mx_chroma_rec), nullptr, out}};
+  return staged_records(q.ctx, q.count, slots, "chroma records",
+                        [&](void *const *d) { return chroma_launch(q, static_cast<mx_chroma_rec *>(d[0])); });
+}
+
+int sum_args(const mx_ctx *ctx, const void *chroma, int64_t count, const void *jobs, int64_t njobs, const void *out) {
+  if (!ctx) return fail(MX_ERR_INVALID, "null context");
+  if (count < 0 || njobs < 0 || njobs > INT32_MAX) return fail(MX_ERR_INVALID, "%lld records, %lld jobs", (long long)count, (long long)njobs);
+  if ((count > 0 && !chroma) || (njobs > 0 && (!jobs || !out))) return fail(MX_ERR_INVALID, "null argument");
+  return MX_OK;
+}
+
+int jobs_inside(const mx_chroma_job *jobs, int64_t njobs, int64_t count) {
+  for (int64_t j = 0; j < njobs; ++j)
+    if (jobs[j].first_frame < 0 || jobs[j].frames < 0 || jobs[j].first_frame > count || jobs[j].frames > count - jobs[j].first_frame)
+      return fail(MX_ERR_INVALID, "job %lld: records [%lld, +%lld) outside the %lld given", (long long)j, (long long)jobs[j].first_frame,
+                  (long long)jobs[j].frames, (long long)count);
+  return MX_OK;
+}
+
+}  // namespace
+
+namespace mx {
+
+// periodic Hann / 2048, rounded from binary64 (the scale is a power of two): built on the context's first chroma call, kept
+// until it goes
+int chroma_window(mx_ctx *ctx, const float **out) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!ctx->chroma_hann) {
+    std::vector<float> w((size_t)chroma::kN);
+    for (int j = 0; j < chroma::kN; ++j)
+      w[(size_t)j] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)j / (double)chroma::kN)) * (1.0f / 2048.0f);
+    if (const int rc = upload_table(w, &ctx->chroma_hann)) return rc;
+  }
+  *out = ctx->chroma_hann;
+  return MX_OK;
+}
+
+}  // namespace mx
+
+extern "C" {
+
+void mx_chroma_params_default(mx_chroma_params *p) {
+  mx_guard_void([&] { params_default(p, kChromaDefaults); });
+}
+
+int mx_chroma_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+                  const mx_chroma_params *params, mx_chroma_rec *d_out) {
+  return mx_guard([&]() -> int {
+    ChromaCall q;
+    if (const int rc = chroma_parse(ctx, a, sampleRate, hop, first_frame, count, params, d_out, q)) return rc;
+    return chroma_launch(q, d_out);
+  });
+}
+
+int mx_chroma(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
+              const mx_chroma_params *params, mx_chroma_rec *out) {
+  return mx_guard([&]() -> int {
+    ChromaCall q;
+    if (const int rc = chroma_parse(ctx, a, sampleRate, hop, first_frame, count, params, out, q)) return rc;
+    return chroma_host(q, out);
+  });
+}
+
+int mx_chroma_sum_dev(mx_ctx *ctx, const mx_chroma_rec *d_chroma, int64_t count, const mx_chroma_job *d_jobs, int64_t njobs,
+                      double *d_out) {
+  return mx_guard([&]() -> int {
+    if (const int rc = sum_args(ctx, d_chroma, count, d_jobs, njobs, d_out)) return rc;
+    if (njobs == 0) return MX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(launch_chroma_sum(d_chroma, count, d_jobs, njobs, d_out, ctx->stream));
+    return MX_OK;
+  });
+}
+
+int mx_chroma_sum(mx_ctx *ctx, const mx_chroma_rec *chroma, int64_t count, const mx_chroma_job *jobs, int64_t njobs, double *out) {
+  return mx_guard([&]() -> int {
+    if (const int rc = sum_args(ctx, chroma, count, jobs, njobs, out)) return rc;
+    if (const int rc = jobs_inside(jobs, njobs, count)) return rc;
+    if (njobs == 0) return MX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DeviceArray<mx_chroma_rec> d_rec;  // (freed once the stream has drained)
+    DeviceArray<mx_chroma_job> d_jobs;
+    DeviceArray<double> d_out;
+    hipError_t e = d_rec.alloc(ctx->stream, (size_t)count);
+    if (e == hipSuccess) e = d_jobs.alloc(ctx->stream, (size_t)njobs);
+    if (e == hipSuccess) e = d_out.alloc(ctx->stream, (size_t)njobs * chroma::kCols);
+    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "chroma sums: %s", hipGetErrorString(e));
+    if (count) e = hipMemcpyAsync(d_rec.p, chroma, (size_t)count * sizeof(mx_chroma_rec), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs.p, jobs, (size_t)njobs * sizeof(mx_chroma_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = launch_chroma_sum(d_rec.p, count, d_jobs.p, njobs, d_out.p, ctx->stream);
+    if (e == hipSuccess) e = d_out.download(out);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "chroma sums: %s", hipGetErrorString(e));
+  });
+}
+
+int mx_key_from_chroma(const double *sum40, mx_key *out) {
+  return mx_guard([&]() -> int {
+    if (!sum40 || !out) return fail(MX_ERR_INVALID, "null argument");
+    *out = key_from_sum(sum40);
+    return MX_OK;
+  });
+}
+
+int mx_key_from_notes(const mx_note *notes, int64_t count, mx_key *out) {
+  return mx_guard([&]() -> int {
+    if (!out || count < 0 || (count > 0 && !notes)) return fail(MX_ERR_INVALID, "null argument or negative count");
+    for (int64_t i = 0; i < count; ++i)
+      if (!std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
+    *out = key_from_notes(notes, count);
+    return MX_OK;
+  });
+}
+
+int mx_key_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_chroma_params *params,
+                  int64_t window_frames, int64_t window_hop, mx_key *key, mx_key_window **windows, int64_t *nwindows) {
+  return mx_guard([&]() -> int {
+    if (!key || (windows && !nwindows)) return fail(MX_ERR_INVALID, "null argument");
+    if (window_frames < 0 || (windows && window_frames > 0 && window_hop < 1))
+      return fail(MX_ERR_INVALID, "windows of %lld frames every %lld", (long long)window_frames, (long long)window_hop);
+    int64_t count = 0;  // (the whole file)
+    if (const int rc = file_frames(ctx, a, hop, count)) return rc;
+    if (count > INT32_MAX) return fail(MX_ERR_INVALID, "%lld frames beyond int32", (long long)count);
+    ChromaCall q;
+    if (const int rc = chroma_parse(ctx, a, sampleRate, hop, 0, count, params, key, q)) return rc;
+    std::vector<mx_chroma_job> jobs = key_windows(count, windows ? window_frames : 0, window_hop);
+    if (jobs.size() >= (size_t)INT32_MAX) return fail(MX_ERR_INVALID, "too many windows");
+    jobs.push_back(mx_chroma_job{0, count});  // the take, behind its windows
+    const size_t njobs = jobs.size();
+    std::vector<double> sums(njobs * chroma::kCols);
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+      DeviceArray<mx_chroma_rec> d_rec;
+      DeviceArray<mx_chroma_job> d_jobs;
+      DeviceArray<double> d_out;
+      hipError_t e = d_rec.alloc(ctx->stream, (size_t)count);
+      if (e == hipSuccess) e = d_jobs.alloc(ctx->stream, njobs);
+      if (e == hipSuccess) e = d_out.alloc(ctx->stream, sums.size());
+      if (e != hipSuccess) return fail(MX_ERR_NOMEM, "key detection: %s", hipGetErrorString(e));
+      e = hipMemcpyAsync(d_jobs.p, jobs.data(), njobs * sizeof(mx_chroma_job), hipMemcpyHostToDevice, ctx->stream);
+      if (e != hipSuccess) return fail(MX_ERR_DEVICE, "job upload: %s", hipGetErrorString(e));
+      if (const int rc = chroma_launch(q, d_rec.p)) return rc;
+      e = launch_chroma_sum(d_rec.p, count, d_jobs.p, (int64_t)njobs, d_out.p, ctx->stream);
+      if (e == hipSuccess) e = d_out.download(sums.data());
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) return fail(MX_ERR_DEVICE, "key detection: %s", hipGetErrorString(e));
+    }
+    if (windows) {
+      std::vector<mx_key_window> w(njobs - 1);
+      for (size_t j = 0; j + 1 < njobs; ++j)
+        w[j] = mx_key_window{(int32_t)jobs[j].first_frame, (int32_t)jobs[j].frames, key_from_sum(&sums[j * chroma::kCols])};
+      if (const int rc = hand_over(w, windows, nwindows)) return rc;
+    }
+    *key = key_from_sum(&sums[(njobs - 1) * chroma::kCols]);
+    return MX_OK;
+  });
+}
+
+int mx_correction_markers_tuned(const mx_note *notes, int64_t count, double strength, int scale_mask, double tuning_cents,
+                                mx_marker *out) {
+  return mx_guard([&]() -> int {
+    if (count < 0 || (count > 0 && (!notes || !out))) return fail(MX_ERR_INVALID, "null argument");
+    if (!(strength >= 0.0 && strength <= 1.0)) return fail(MX_ERR_INVALID, "strength %g outside [0, 1]", strength);
+    if (scale_mask < 0 || scale_mask > 0xFFF) return fail(MX_ERR_INVALID, "scale mask 0x%x beyond the twelve classes", scale_mask);
+    if (!(tuning_cents >= -50.0 && tuning_cents <= 50.0)) return fail(MX_ERR_INVALID, "tuning of %g cents outside [-50, 50]", tuning_cents);
+    for (int64_t i = 0; i < count; ++i) {
+      if (!std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
+      if (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample))
+        return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
+    }
+    correction_markers_tuned(notes, count, strength, scale_mask, tuning_cents, out);
+    return MX_OK;
+  });
+}
+
+}  // extern "C"
