@@ -1054,6 +1054,156 @@ int mx_key_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const
 int mx_correction_markers_tuned(const mx_note *notes, int64_t count, double strength, int scale_mask, double tuning_cents,
                                 mx_marker *out);
 
+/* ---- Pitch drift and vibrato inside notes (BUILD-DEFINED; restated in int64 / f64 by tests/contour_ref.py) ----
+ * mx_correction_markers_tuned moves a note by one constant bend; what happens inside the note stays.  This section splits the f0
+ * contour of every note into centre, slow drift and vibrato, reports the vibrato's rate and extent, turns the split into a
+ * per-frame bend curve, and lets the PSOLA renderer follow that curve.  The reference has none of it.
+ *
+ * Stage A, cents.  A frame is voiced by mx_detect_notes' rule (tau > 0, aperiodicity < threshold, rms >= rms_floor) and, in
+ * addition, has a finite period > 0.  A voiced frame gives
+ *   cents = (int32)rint(16.0 * (1200.0 * log2((double)sr / (double)period / 55.0) + 2400.0)),
+ * in binary64 from the f32 period, no contraction: units of 1/16 cent, 1600 x mx_bin_note's note, negative at low sample rates.
+ * Any other frame gives MX_CONTOUR_NONE.  A value depends on its record alone.  THE int32 IS THE DEFINITION FROM HERE ON:
+ * everything downstream is exact integer arithmetic, the same on the device, on the host and in numpy; no summation order
+ * matters and there is no tolerance.  (Two correctly built log2 may differ in the last place, so a value whose pre-rounding
+ * magnitude lies within 1e-11 of a tie can differ by one unit between the device and a host restatement: about two frames in a
+ * million lie within 1e-6 of one.)
+ *
+ * Stage B, split and statistics.  A span {first, frames} is a note's frames relative to the array: spans sorted, disjoint, inside
+ * the array, frames >= 1, possibly adjacent.  Parameters: half-width w in [0, 64], 1 <= lag_min <= lag_max <= 256.  For the span
+ * [f0, f0 + F) and a frame f in it:
+ *   mean(v, f) = floor((2 S + c) / (2 c)) in int64 (nearest, halves up; the floor toward minus infinity, also for negative S),
+ *                S the sum of v_g over g in [max(f - w, f0), min(f + w, f0 + F - 1)], c the number of taps;
+ *   b_f = mean(cents, f);  smooth_f = mean(b, f);  vib_f = cents_f - smooth_f.
+ * The window is clipped to the span in both passes: nothing leaks across a span boundary, not even between adjacent spans.  Two
+ * box passes make a triangle of 4w + 1 frames; at the default w (250 ms) each box has its first null at 4 Hz.
+ * Record of every frame of the array: {smooth, vib}; {MX_CONTOUR_NONE, 0} outside every span.
+ * Statistics of a span: sum_smooth, min_smooth, max_smooth over its frames; r0 = sum vib_f^2;
+ *   r(L) = sum of vib_f * vib_{f+L} over f, f + L both in the span, L in [lag_min, min(lag_max, F - 1)];
+ *   lag = the L with the greatest r(L), the lowest L on ties, r_lag = r(lag); an empty range gives lag = 0, r_lag = 0.
+ * Bound: the tracker's default band (55 .. 1760 Hz) spans 6000 cents = 96000 units, so inside a span |vib| < 2^17, a product
+ * is below 2^34 and a sum over a span of up to 2^29 frames (a month at 187.5 frames/s) stays inside int64; sum_smooth is
+ * smaller still.  For arbitrary records |cents| < 2^22 (any positive f32 period at any int sample rate: |log2| < 181), a
+ * product is below 2^46 and 2^17 frames of one span are safe.  Beyond that the int64 sums wrap: wrong values, nothing worse.
+ * Defaults (mx_contour_params_default): w = floor(0.125 sr / hop) clamped to [0, 64]; lag_min = max(1, floor(sr / hop / 12)),
+ * lag_max = min(256, ceil(sr / hop / 3)) (at least lag_min): vibrato between 3 and 12 Hz.  The window, the band and the glide of
+ * mx_bend_params are tuned on nothing but synthetic takes; nothing here was run on recordings. */
+#define MX_CONTOUR_NONE INT32_MIN
+typedef struct mx_contour_span {
+  int32_t first, frames;
+} mx_contour_span;
+typedef struct mx_contour_params {
+  int32_t half_width;       /* w, in [0, 64] */
+  int32_t lag_min, lag_max; /* 1 <= lag_min <= lag_max <= 256 */
+} mx_contour_params;
+typedef struct mx_contour_rec {
+  int32_t smooth; /* centre + drift, 1/16 cent (MX_CONTOUR_NONE outside every span) */
+  int32_t vib;    /* cents - smooth (0 outside every span) */
+} mx_contour_rec;
+typedef struct mx_contour_stat {
+  int64_t sum_smooth;
+  int32_t min_smooth, max_smooth;
+  int64_t r0;
+  int32_t lag;      /* 0: no lag in range */
+  int32_t reserved; /* 0 */
+  int64_t r_lag;
+} mx_contour_stat;
+/* MX_ERR_INVALID for sr <= 0, hop outside [1, 16384] or p NULL. */
+int mx_contour_params_default(int sampleRate, int hop, mx_contour_params *p);
+/* Stage A over count records in HBM -> count int32 in HBM.  A thread per frame; asynchronous on the context's stream.
+ * MX_ERR_INVALID, before any launch, for count outside [0, INT32_MAX], sr <= 0, a threshold or rms_floor that is not finite,
+ * a null argument where count > 0. */
+int mx_contour_cents_dev(mx_ctx *ctx, const mx_f0 *d_track, int64_t count, int sampleRate, float threshold, float rms_floor,
+                         int32_t *d_cents);
+/* Same, host pointers, through the context's staging buffers.  Blocks. */
+int mx_contour_cents(mx_ctx *ctx, const mx_f0 *track, int64_t count, int sampleRate, float threshold, float rms_floor,
+                     int32_t *cents);
+/* Stage B: count values and nspans spans in HBM -> count records at d_rec and nspans statistics at d_stat (either may be NULL),
+ * in HBM.  Asynchronous on the context's stream.  The smoothing is one launch (a workgroup per 256 frames, both box passes
+ * through LDS), the statistics two (partial sums per 1024 frames of a span, then one workgroup per span): a span of a whole take
+ * is spread over the device, and integer sums give the same bytes whatever the tiling.  Work memory (24 + 8 x lags bytes per
+ * span and per 1024 frames, 8 bytes per frame where d_rec is NULL) belongs to the context, kept between calls, released by
+ * mx_ctx_release_scratch; MX_ERR_NOMEM when it cannot be had.
+ * MX_ERR_INVALID, before any launch, for count outside [0, INT32_MAX], nspans outside [0, count], parameters out of range, p NULL
+ * or a null argument that is needed.
+ * PRECONDITION (not checked on the device — mx_contour_split does check it): the spans are sorted, disjoint, inside the array
+ * with frames >= 1, and no frame inside a span holds MX_CONTOUR_NONE.  Anything else gives wrong values and nothing worse:
+ * every span is clipped to the array and every index into its array. */
+int mx_contour_split_dev(mx_ctx *ctx, const int32_t *d_cents, int64_t count, const mx_contour_span *d_spans, int64_t nspans,
+                         const mx_contour_params *p, mx_contour_rec *d_rec, mx_contour_stat *d_stat);
+/* Same, host pointers (rec and stat: either may be NULL).  Checks the precondition first: MX_ERR_INVALID, before any launch
+ * and with the outputs untouched, for spans out of order, overlapping, outside the array or with frames < 1, and for a frame
+ * inside a span that holds MX_CONTOUR_NONE.  Blocks. */
+int mx_contour_split(mx_ctx *ctx, const int32_t *cents, int64_t count, const mx_contour_span *spans, int64_t nspans,
+                     const mx_contour_params *p, mx_contour_rec *rec, mx_contour_stat *stat);
+
+/* Host logic (binary64, no contraction; tests/contour_ref.py does the same operations in the same order).
+ * mx_contour_spans: spans[i] = {notes[i].first_frame - first_frame, notes[i].frames}, first_frame the frame index of the
+ * track's record 0 (mx_detect_notes').  MX_ERR_INVALID for a null argument or a negative count; the spans are not judged here. */
+int mx_contour_spans(const mx_note *notes, int64_t nnotes, int64_t first_frame, mx_contour_span *spans);
+/* Vibrato figures of a span of `frames` frames at sr / hop frames per second:
+ *   rate_hz = sr / hop / lag;  extent_cents = sqrt(2 r0 / frames) / 16, the peak of the sinusoid of the same power;
+ *   strength = (r_lag / r0) * frames / (frames - lag), 1 for a pure sinusoid;  drift_cents = (max_smooth - min_smooth) / 16.
+ * All four are 0 where lag == 0 or r0 == 0.  MX_ERR_INVALID for a null argument, frames < 1, frames <= lag, sr <= 0 or hop
+ * outside [1, 16384]. */
+typedef struct mx_vibrato {
+  double rate_hz, extent_cents, strength, drift_cents;
+} mx_vibrato;
+int mx_contour_vibrato(const mx_contour_stat *stat, int32_t frames, int sampleRate, int hop, mx_vibrato *out);
+/* The bend curve (semitones per frame of the array) that corrects the notes.  For frame h of note i (span i):
+ *   bend_h = (float)(shift_i - drift_amount * ((double)smooth_h / 1600 - notes[i].note)
+ *                    + (vibrato_scale - 1) * (double)vib_h / 1600),  evaluated in that order;
+ * shift_i: the note's own move in semitones (shift NULL: 0), e.g. mx_correction_markers_tuned's target minus the note.  With
+ * drift_amount 1, vibrato_scale 0 and shift_i = T_i - note_i the note's contour becomes flat at T_i: cents = centre + drift +
+ * vib, the centre at the note's median, which is what the correction markers snap.  Between two notes whose gap is <=
+ * glide_frames frames: binary64 linear interpolation between the bend of the last frame of one (x0, as a float) and of the
+ * first frame of the next (x1), frame j of the G gap frames (j = 1..G) getting (float)(x0 + (x1 - x0) * j / (G + 1)).
+ * Everywhere else outside notes: 0.  Parameters: drift_amount in [0, 1], vibrato_scale in [0, 4], glide_frames >= 0; defaults
+ * {1, 1, 8}.  MX_ERR_INVALID for parameters out of range or not finite, a shift or a note that is not finite, spans that are
+ * not what mx_contour_split accepts for `count` frames, a null argument.  p NULL: the defaults. */
+typedef struct mx_bend_params {
+  double drift_amount, vibrato_scale;
+  int32_t glide_frames;
+} mx_bend_params;
+void mx_bend_params_default(mx_bend_params *p);
+int mx_contour_bend(const mx_contour_rec *rec, int64_t count, const mx_note *notes, const mx_contour_span *spans, int64_t nnotes,
+                    const double *shift, const mx_bend_params *p, float *bend_out);
+/* One call: stage A over the host track (track[0] = frame first_frame, as in mx_detect_notes, with the note parameters'
+ * threshold and rms_floor), stage B over the notes' spans, in device memory of the context.  params NULL:
+ * mx_contour_params_default(sr, hop).  rec_out (count records) and stat_out (nnotes): either may be NULL.  Blocks.
+ * MX_ERR_INVALID for what the stages refuse; an unvoiced frame inside a note is refused like any MX_CONTOUR_NONE inside a span. */
+int mx_pitch_contour(mx_ctx *ctx, const mx_f0 *track, int64_t count, int sampleRate, int hop, int64_t first_frame,
+                     const mx_note *notes, int64_t nnotes, float threshold, float rms_floor, const mx_contour_params *params,
+                     mx_contour_rec *rec_out, mx_contour_stat *stat_out);
+
+/* PSOLA follows a bend curve.  `bend`: count floats, semitones, one per frame of the track — a curve over the SOURCE, like the
+ * formant curve, so it follows a time-stretch.  For a voiced grain
+ *   r_k = clamp(exp2(((double)time2pitchbend(s_k / sr) + (double)bend[h]) / 12), 1/2, 2),
+ *   h = clamp(floor((a_m + (2048 - p_m) / 2) / hop + 1/2), 0, count - 1), a_m = a_{m(k)} the grain's analysis mark, p_m its period:
+ * the frame whose MEASUREMENT is centred on the mark.  The tracker's frame h reads samples [h hop - 2048, h hop + tau), so its
+ * period describes the signal (2048 - tau) / 2 samples before h hop, 18 ms at 150 Hz and 48 kHz: a tenth of a 6 Hz vibrato
+ * cycle, and a curve read at the frame P(a_m) reads would leave three quarters of such a vibrato standing (tests/
+ * test_gpu_contour_render.py: 25.8 of 34.1 cents; 8.0 with the lead).  Everything else is mx_psola_plan's /
+ * mx_psola_plan_formant's; bend NULL adds nothing (those entry points' bytes), and so does an all-zero curve.  The record
+ * types and the kernels are the existing ones.  MX_ERR_INVALID for a bend value that is not finite and for whatever the
+ * existing plans refuse.  The phase-vocoder and granular renderers follow markers only. */
+int mx_psola_plan_bend(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params *params,
+                       const mx_marker *markers, int nmarkers, const float *bend, mx_psola_grain **grains, int64_t *ngrains,
+                       int64_t *nsamples);
+int mx_psola_plan_formant_bend(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                               const mx_psola_params *params, const mx_marker *markers, int nmarkers,
+                               const mx_formant_point *points, int npoints, const float *bend, mx_psola_fgrain **fgrains,
+                               int64_t *ngrains, int64_t *nsamples);
+/* Plan and synthesis in one call, as mx_psola_render_formant / mx_psola_render_formant_dev: npoints == 0 selects the plain
+ * records and the plain kernel. */
+int mx_psola_render_bend(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                         const mx_psola_params *params, const mx_marker *markers, int nmarkers, const mx_formant_point *points,
+                         int npoints, const float *bend, float *pcm_f32_out, int16_t *pcm_i16_out);
+int mx_psola_render_bend_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                             const mx_psola_params *params, const mx_marker *markers, int nmarkers,
+                             const mx_formant_point *points, int npoints, const float *bend, float *d_pcm_f32,
+                             int16_t *d_pcm_i16);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

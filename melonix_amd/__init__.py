@@ -19,6 +19,7 @@ from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, 
 from ._capi import COMB_DTYPE, COMB_JOB_DTYPE, TEMPO_WINDOW_DTYPE  # noqa: F401
 from ._capi import GAIN_POINT_DTYPE, SIB_FEAT_DTYPE, SIBILANT_DTYPE  # noqa: F401
 from ._capi import CHROMA_COLS, CHROMA_JOB_DTYPE, KEY_DTYPE, KEY_WINDOW_DTYPE  # noqa: F401
+from ._capi import CONTOUR_NONE, CONTOUR_REC_DTYPE, CONTOUR_SPAN_DTYPE, CONTOUR_STAT_DTYPE  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
@@ -30,7 +31,9 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "SIB_FEAT_DTYPE", "SIBILANT_DTYPE", "GAIN_POINT_DTYPE", "sib_feature_params_default", "sibilant_params_default", "sibilants",
            "formant_protect", "sibilant_gain_points",
            "CHROMA_COLS", "CHROMA_JOB_DTYPE", "KEY_DTYPE", "KEY_WINDOW_DTYPE", "chroma_params_default", "key_from_chroma",
-           "key_from_notes", "correction_markers_tuned"]
+           "key_from_notes", "correction_markers_tuned",
+           "CONTOUR_NONE", "CONTOUR_SPAN_DTYPE", "CONTOUR_REC_DTYPE", "CONTOUR_STAT_DTYPE", "contour_params_default",
+           "bend_params_default", "contour_spans", "contour_vibrato", "contour_bend", "psola_plan_bend", "psola_plan_formant_bend"]
 
 
 def _ptr(a):
@@ -64,7 +67,7 @@ _PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "not
            "tempo": (_capi.TempoParams, "mx_tempo_params_default"),
            "sib_feature": (_capi.SibFeatureParams, "mx_sib_feature_params_default"),
            "sibilant": (_capi.SibilantParams, "mx_sibilant_params_default"),
-           "chroma": (_capi.ChromaParams, "mx_chroma_params_default")}
+           "chroma": (_capi.ChromaParams, "mx_chroma_params_default"), "bend": (_capi.BendParams, "mx_bend_params_default")}
 
 
 def _params_default(kind: str) -> dict:
@@ -126,6 +129,22 @@ def sibilant_params_default() -> dict:
 
 def chroma_params_default() -> dict:
     return _params_default("chroma")
+
+
+def bend_params_default() -> dict:
+    return _params_default("bend")
+
+
+def contour_params_default(sr: int, hop: int) -> dict:
+    """The split's parameters at sr / hop frames per second: a 250 ms window, lags of 3 .. 12 Hz."""
+    p = _capi.ContourParams()
+    _capi.check(_capi.lib().mx_contour_params_default(sr, hop, C.byref(p)))
+    return {k: getattr(p, k) for k, _ in _capi.ContourParams._fields_}
+
+
+def _contour_params(params: dict):
+    """half_width, lag_min, lag_max -> the struct (the split's entry points take no NULL)."""
+    return C.byref(_capi.ContourParams(int(params["half_width"]), int(params["lag_min"]), int(params["lag_max"])))
 
 
 def pitch_band(N: int, sr: int = 48000):
@@ -496,6 +515,74 @@ class Context:
         _capi.check(_capi.lib().mx_key_detect(self.handle, audio.handle, sr, hop, _params_arg("chroma", params), int(window_frames),
                                               int(window_hop), C.byref(key), C.byref(out), C.byref(cnt)))
         return _key_dict(key), _take_records(out, cnt.value, KEY_WINDOW_DTYPE)
+
+    # ---- pitch drift and vibrato inside notes (build-defined; include/melonix_amd.h) ----
+    def contour_cents(self, track, sr: int, threshold: float = 0.15, rms_floor: float = 1e-3):
+        """-> int32[count]: the cents (1/16 cent, 1600 x the note) of F0_DTYPE records, CONTOUR_NONE where unvoiced."""
+        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+        out = np.empty(len(track), dtype=np.int32)
+        _capi.check(_capi.lib().mx_contour_cents(self.handle, _ptr(track) if len(track) else None, len(track), sr, threshold,
+                                                 rms_floor, _ptr(out) if len(out) else None))
+        return out
+
+    def contour_cents_dev(self, d_track: int, count: int, sr: int, threshold: float, rms_floor: float, d_cents: int):
+        """count records at d_track -> count int32 at d_cents, both in HBM; asynchronous on the context's stream."""
+        _capi.check(_capi.lib().mx_contour_cents_dev(self.handle, C.c_void_p(d_track or 0), count, sr, threshold, rms_floor,
+                                                     C.c_void_p(d_cents or 0)))
+
+    def contour_split(self, cents, spans, want_rec: bool = True, want_stat: bool = True, **params):
+        """int32 cents and (first, frames) spans -> (CONTOUR_REC_DTYPE[count] | None, CONTOUR_STAT_DTYPE[nspans] | None).
+        params: half_width, lag_min, lag_max, all three (contour_params_default(sr, hop))."""
+        cents = np.ascontiguousarray(cents, dtype=np.int32)
+        spans = _records(spans, CONTOUR_SPAN_DTYPE)
+        rec = np.empty(len(cents), dtype=CONTOUR_REC_DTYPE) if want_rec else None
+        stat = np.empty(len(spans), dtype=CONTOUR_STAT_DTYPE) if want_stat else None
+        _capi.check(_capi.lib().mx_contour_split(self.handle, _ptr(cents) if len(cents) else None, len(cents),
+                                                 _ptr(spans) if len(spans) else None, len(spans), _contour_params(params),
+                                                 _ptr(rec), _ptr(stat)))
+        return rec, stat
+
+    def contour_split_dev(self, d_cents: int, count: int, d_spans: int, nspans: int, d_rec: int | None, d_stat: int | None,
+                          **params):
+        """Everything in HBM; asynchronous on the context's stream.  The spans are NOT checked (include/melonix_amd.h)."""
+        _capi.check(_capi.lib().mx_contour_split_dev(self.handle, C.c_void_p(d_cents or 0), count, C.c_void_p(d_spans or 0), nspans,
+                                                     _contour_params(params), C.c_void_p(d_rec or 0), C.c_void_p(d_stat or 0)))
+
+    def pitch_contour(self, track, sr: int, hop: int, notes, first: int = 0, threshold: float = 0.15, rms_floor: float = 1e-3,
+                      **params):
+        """Cents and split of a host track over detect_notes' notes -> (CONTOUR_REC_DTYPE[count], CONTOUR_STAT_DTYPE[nnotes]).
+        params: none (contour_params_default(sr, hop)) or all of half_width, lag_min, lag_max."""
+        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+        notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+        rec = np.empty(len(track), dtype=CONTOUR_REC_DTYPE)
+        stat = np.empty(len(notes), dtype=CONTOUR_STAT_DTYPE)
+        _capi.check(_capi.lib().mx_pitch_contour(self.handle, _ptr(track) if len(track) else None, len(track), sr, hop, first,
+                                                 _ptr(notes) if len(notes) else None, len(notes), threshold, rms_floor,
+                                                 _contour_params(params) if params else None, _ptr(rec), _ptr(stat)))
+        return rec, stat
+
+    def psola_render_bend(self, audio: Audio, sr: int, hop: int, track, markers, bend, points=(), want_f32: bool = True,
+                          want_i16: bool = True, **params):
+        """psola_render_formant following a bend curve (float32 semitones per frame of the track, contour_bend's); no points:
+        the plain records and kernel."""
+        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+        m = _capi.markers_array(markers)
+        pts, b = _formant_points(points), _bend_arg(bend, len(track))
+        f32, i16 = _pcm_pair(_render_length(audio.n, sr, m, len(markers)), want_f32, want_i16)
+        _capi.check(_capi.lib().mx_psola_render_bend(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
+                                                     len(track), _params_arg("psola", params), m, len(markers), *_points_args(pts),
+                                                     _ptr(b), _ptr(f32), _ptr(i16)))
+        return f32, i16
+
+    def psola_render_bend_dev(self, audio: Audio, sr: int, hop: int, track, markers, bend, points, d_f32: int | None,
+                              d_i16: int | None, **params):
+        """The same with the PCM left in HBM (the render's length each); blocks until the records are uploaded and used."""
+        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+        m = _capi.markers_array(markers)
+        pts, b = _formant_points(points), _bend_arg(bend, len(track))
+        _capi.check(_capi.lib().mx_psola_render_bend_dev(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
+                                                         len(track), _params_arg("psola", params), m, len(markers),
+                                                         *_points_args(pts), _ptr(b), C.c_void_p(d_f32 or 0), C.c_void_p(d_i16 or 0)))
 
     def formant_protect(self, points, sibs, ramp: int, n: int):
         return formant_protect(points, sibs, ramp, n)
@@ -968,6 +1055,72 @@ def psola_plan_formant(n: int, sr: int, hop: int, track, markers, points, **para
     """psola_plan with a formant curve -> (PSOLA_FGRAIN_DTYPE array, nsamples).  points: (source sample, semitones) pairs,
     samples strictly increasing; none: every record's step is 65536."""
     return _psola_plan(True, n, sr, hop, track, markers, points, params)
+
+
+def _bend_arg(bend, count: int):
+    if bend is None:
+        return None
+    bend = np.ascontiguousarray(bend, dtype=np.float32)
+    if len(bend) != count:
+        raise ValueError("a bend curve has one value per frame of the track")
+    return bend
+
+
+def psola_plan_bend(n: int, sr: int, hop: int, track, markers, bend, **params):
+    """psola_plan following a bend curve (float32 semitones, one per frame of the track; None: psola_plan itself)."""
+    return _psola_plan_bend(False, n, sr, hop, track, markers, None, bend, params)
+
+
+def psola_plan_formant_bend(n: int, sr: int, hop: int, track, markers, points, bend, **params):
+    """psola_plan_formant following a bend curve."""
+    return _psola_plan_bend(True, n, sr, hop, track, markers, points, bend, params)
+
+
+def _psola_plan_bend(formant: bool, n: int, sr: int, hop: int, track, markers, points, bend, params: dict):
+    track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+    m = _capi.markers_array(markers)
+    sfx, dtype, pts = _psola_kind(formant, points)
+    b = _bend_arg(bend, len(track))
+    out, cnt, ns = C.c_void_p(), C.c_int64(), C.c_int64()
+    _capi.check(getattr(_capi.lib(), f"mx_psola_plan{sfx}_bend")(n, sr, hop, _ptr(track) if len(track) else None, len(track),
+                                                                  _params_arg("psola", params), m, len(markers), *_points_args(pts),
+                                                                  _ptr(b), C.byref(out), C.byref(cnt), C.byref(ns)))
+    return _take_records(out, cnt.value, dtype), ns.value
+
+
+# ---- pitch drift and vibrato inside notes (host; build-defined) ----
+def contour_spans(notes, first: int = 0):
+    """The spans of detect_notes' output relative to a track whose record 0 is frame `first` -> CONTOUR_SPAN_DTYPE array."""
+    notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    out = np.zeros(len(notes), dtype=CONTOUR_SPAN_DTYPE)
+    _capi.check(_capi.lib().mx_contour_spans(_ptr(notes) if len(notes) else None, len(notes), first, _ptr(out) if len(out) else None))
+    return out
+
+
+def contour_vibrato(stat, frames: int, sr: int, hop: int) -> dict:
+    """rate_hz, extent_cents, strength, drift_cents of one CONTOUR_STAT_DTYPE record of a span of `frames` frames."""
+    s = np.ascontiguousarray(np.asarray(stat, dtype=CONTOUR_STAT_DTYPE).reshape(1))
+    v = _capi.Vibrato()
+    _capi.check(_capi.lib().mx_contour_vibrato(_ptr(s), int(frames), sr, hop, C.byref(v)))
+    return {k: getattr(v, k) for k, _ in _capi.Vibrato._fields_}
+
+
+def contour_bend(rec, notes, spans, shift=None, **params):
+    """The bend curve (float32 semitones per frame) that corrects the notes: rec from Context.contour_split / pitch_contour,
+    shift one float per note (None: 0); params: drift_amount, vibrato_scale, glide_frames (bend_params_default())."""
+    rec = np.ascontiguousarray(rec, dtype=CONTOUR_REC_DTYPE)
+    notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    spans = _records(spans, CONTOUR_SPAN_DTYPE)
+    if len(spans) != len(notes):
+        raise ValueError("one span per note")
+    sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float64)
+    if sh is not None and len(sh) != len(notes):
+        raise ValueError("one shift per note")
+    out = np.zeros(len(rec), dtype=np.float32)
+    _capi.check(_capi.lib().mx_contour_bend(_ptr(rec) if len(rec) else None, len(rec), _ptr(notes) if len(notes) else None,
+                                            _ptr(spans) if len(spans) else None, len(notes), _ptr(sh),
+                                            _params_arg("bend", params), _ptr(out) if len(out) else None))
+    return out
 
 
 # ---- onsets and timing markers (host; build-defined) ----

@@ -161,6 +161,27 @@ class KeyWindow(C.Structure):
     _fields_ = [("first_frame", C.c_int32), ("frames", C.c_int32), ("key", Key)]
 
 
+class ContourSpan(C.Structure):
+    _fields_ = [("first", C.c_int32), ("frames", C.c_int32)]
+
+
+class ContourParams(C.Structure):
+    _fields_ = [("half_width", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32)]
+
+
+class ContourStat(C.Structure):
+    _fields_ = [("sum_smooth", C.c_int64), ("min_smooth", C.c_int32), ("max_smooth", C.c_int32), ("r0", C.c_int64),
+                ("lag", C.c_int32), ("reserved", C.c_int32), ("r_lag", C.c_int64)]
+
+
+class Vibrato(C.Structure):
+    _fields_ = [("rate_hz", C.c_double), ("extent_cents", C.c_double), ("strength", C.c_double), ("drift_cents", C.c_double)]
+
+
+class BendParams(C.Structure):
+    _fields_ = [("drift_amount", C.c_double), ("vibrato_scale", C.c_double), ("glide_frames", C.c_int32)]
+
+
 PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
 STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
                        ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
@@ -198,6 +219,13 @@ KEY_DTYPE = np.dtype([("tonic", "<i4"), ("mode", "<i4"), ("scale_mask", "<i4"), 
 KEY_WINDOW_DTYPE = np.dtype([("first_frame", "<i4"), ("frames", "<i4"), ("key", KEY_DTYPE)])
 assert CHROMA_JOB_DTYPE.itemsize == C.sizeof(ChromaJob) == 16 and C.sizeof(ChromaParams) == 16
 assert KEY_DTYPE.itemsize == C.sizeof(Key) == 48 and KEY_WINDOW_DTYPE.itemsize == C.sizeof(KeyWindow) == 56
+CONTOUR_NONE = -2 ** 31  # MX_CONTOUR_NONE: an unvoiced frame's cents, the smooth value outside every span
+CONTOUR_SPAN_DTYPE = np.dtype([("first", "<i4"), ("frames", "<i4")])
+CONTOUR_REC_DTYPE = np.dtype([("smooth", "<i4"), ("vib", "<i4")])
+CONTOUR_STAT_DTYPE = np.dtype([("sum_smooth", "<i8"), ("min_smooth", "<i4"), ("max_smooth", "<i4"), ("r0", "<i8"), ("lag", "<i4"),
+                               ("reserved", "<i4"), ("r_lag", "<i8")])
+assert CONTOUR_SPAN_DTYPE.itemsize == C.sizeof(ContourSpan) == 8 and CONTOUR_STAT_DTYPE.itemsize == C.sizeof(ContourStat) == 40
+assert C.sizeof(ContourParams) == 12 and C.sizeof(Vibrato) == 32 and C.sizeof(BendParams) == 24
 assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
 assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
 assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
@@ -345,6 +373,22 @@ SIGNATURES = {
     "mx_key_detect": (_i, [_vp, _vp, _i, _i, C.POINTER(ChromaParams), _i64, _i64, C.POINTER(Key), C.POINTER(_vp),
                            C.POINTER(_i64)]),
     "mx_correction_markers_tuned": (_i, [_vp, _i64, _d, _i, _d, _vp]),
+    "mx_contour_params_default": (_i, [_i, _i, C.POINTER(ContourParams)]),
+    "mx_contour_cents_dev": (_i, [_vp, _vp, _i64, _i, _f, _f, _vp]),
+    "mx_contour_cents": (_i, [_vp, _vp, _i64, _i, _f, _f, _vp]),
+    "mx_contour_split_dev": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(ContourParams), _vp, _vp]),
+    "mx_contour_split": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(ContourParams), _vp, _vp]),
+    "mx_contour_spans": (_i, [_vp, _i64, _i64, _vp]),
+    "mx_contour_vibrato": (_i, [_vp, C.c_int32, _i, _i, C.POINTER(Vibrato)]),
+    "mx_bend_params_default": (None, [C.POINTER(BendParams)]),
+    "mx_contour_bend": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(BendParams), _vp]),
+    "mx_pitch_contour": (_i, [_vp, _vp, _i64, _i, _i, _i64, _vp, _i64, _f, _f, C.POINTER(ContourParams), _vp, _vp]),
+    "mx_psola_plan_bend": (_i, [_i64, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, C.POINTER(_vp), C.POINTER(_i64),
+                                C.POINTER(_i64)]),
+    "mx_psola_plan_formant_bend": (_i, [_i64, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, C.POINTER(_vp),
+                                        C.POINTER(_i64), C.POINTER(_i64)]),
+    "mx_psola_render_bend": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "mx_psola_render_bend_dev": (_i, [_vp, _vp, _i, _i, _vp, _i64, C.POINTER(PsolaParams), _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

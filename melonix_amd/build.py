@@ -54,6 +54,8 @@ UNITS = [
     # build-defined chroma records: the f0 tracker's walk, one windowed transform per frame, another tail (chroma_core.h), every
     # rounding as written; and their binary64 window sums, bit for bit the host's
     ("chroma_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # build-defined pitch-contour split: binary64 cents as written, integers after that (contour_core.h), bit for bit numpy's
+    ("contour_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -68,6 +70,7 @@ UNITS = [
     ("capi_tempo.cpp", "hip", []),
     ("capi_sibilant.cpp", "hip", []),
     ("capi_key.cpp", "hip", []),
+    ("capi_contour.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
@@ -76,6 +79,7 @@ UNITS = [
     ("tempo_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("sibilant_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("key_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("contour_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

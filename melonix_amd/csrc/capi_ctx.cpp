@@ -225,6 +225,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     for (auto &st : ctx->chain) st.drop();
     for (auto &st : ctx->f0dec) st.drop();
     for (auto &st : ctx->tempo) st.drop();
+    for (auto &st : ctx->contour) st.drop();
     pv_release(ctx);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -281,6 +282,10 @@ int mx_ctx_release_scratch(mx_ctx *ctx) {
     {
       std::lock_guard<std::mutex> lk(ctx->tempo_mu);
       for (auto &st : ctx->tempo) st.drop();
+    }
+    {
+      std::lock_guard<std::mutex> lk(ctx->contour_mu);
+      for (auto &st : ctx->contour) st.drop();
     }
     return MX_OK;
   });

@@ -149,6 +149,9 @@ enum ChainSlot { kChainBitmap7, kChainBitmap3, kChainRanks, kChainTables, kChain
 enum F0DecSlot { kF0DecBp, kF0DecProd, kF0DecMap, kF0DecSlots };
 // work buffers of the tempo estimate (mx_ctx::tempo, under tempo_mu): the flux curve, the smoothed curve, jobs, records
 enum TempoSlot { kTempoFlux, kTempoCurve, kTempoJobs, kTempoRecords, kTempoSlots };
+// work buffers of the pitch-contour split (mx_ctx::contour, under contour_mu): the pieces' partial sums, and the records where
+// the caller wants the statistics alone
+enum ContourSlot { kContourPart, kContourRec, kContourSlots };
 
 // Arrays handed to the caller, who frees them with mx_free.  add(): a fresh malloc block of n elements (at least one, so an
 // empty result is not a null pointer), copied from src or, src null, left for a download.  give(): every block is there and
@@ -251,7 +254,8 @@ struct mx_ctx {
   std::mutex zc_mu;
   mx::ZcBitmaps zc_scratch;
   // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
-  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_chroma), kept between calls.  One host-staged call per context at a time.
+  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_chroma, mx_contour_cents,
+  // mx_contour_split, mx_pitch_contour), kept between calls.  One host-staged call per context at a time.
   std::mutex stage_mu;
   mx::GrowBuf stage[mx::kStageSlots];
   // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)
@@ -264,6 +268,9 @@ struct mx_ctx {
   // device work buffers of the tempo estimate (capi_tempo.cpp), kept between calls like the staging buffers
   std::mutex tempo_mu;
   mx::GrowBuf tempo[mx::kTempoSlots];
+  // device work buffers of the pitch-contour split (capi_contour.cpp), kept between calls like the staging buffers
+  std::mutex contour_mu;
+  mx::GrowBuf contour[mx::kContourSlots];
   // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;

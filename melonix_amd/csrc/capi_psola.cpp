@@ -7,7 +7,7 @@ using namespace mx;
 
 namespace {
 
-// What the plan and render entry points hand on; no points: the plain records and the plain kernel
+// What the plan and render entry points hand on; no points: the plain records and the plain kernel; no bend: the markers' alone
 struct PsolaCall {
   int64_t n;
   int sampleRate, hop;
@@ -18,13 +18,14 @@ struct PsolaCall {
   int nmarkers;
   const mx_formant_point *points;
   int npoints;
+  const float *bend = nullptr;
 };
 
 int psola_build(const PsolaCall &c, const mx_psola_params &p, std::vector<mx_psola_grain> &v, int64_t &m, std::string &err) {
-  return build_psola_plan(c.n, c.sampleRate, c.hop, c.track, c.count, p, c.markers, c.nmarkers, v, m, err);
+  return build_psola_plan(c.n, c.sampleRate, c.hop, c.track, c.count, p, c.markers, c.nmarkers, v, m, err, c.bend);
 }
 int psola_build(const PsolaCall &c, const mx_psola_params &p, std::vector<mx_psola_fgrain> &v, int64_t &m, std::string &err) {
-  return build_psola_plan(c.n, c.sampleRate, c.hop, c.track, c.count, p, c.markers, c.nmarkers, c.points, c.npoints, v, m, err);
+  return build_psola_plan(c.n, c.sampleRate, c.hop, c.track, c.count, p, c.markers, c.nmarkers, c.points, c.npoints, v, m, err, c.bend);
 }
 
 // the plan of a call's host arguments, or a failed status
@@ -217,6 +218,45 @@ int mx_psola_render_formant(mx_ctx *ctx, const mx_audio *a, int sampleRate, int 
                             const mx_formant_point *points, int npoints, float *pcm_f32_out, int16_t *pcm_i16_out) {
   return mx_guard([&] {
     const PsolaCall c{0, sampleRate, hop, track, count, params, markers, nmarkers, points, npoints};
+    return psola_render(ctx, a, c, pcm_f32_out, pcm_i16_out, true);
+  });
+}
+
+// ---- the same with a bend curve over the source's frames (include/melonix_amd.h "PSOLA follows a bend curve") ----
+int mx_psola_plan_bend(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params *params,
+                       const mx_marker *markers, int nmarkers, const float *bend, mx_psola_grain **grains, int64_t *ngrains,
+                       int64_t *nsamples) {
+  return mx_guard([&] {
+    const PsolaCall c{n, sampleRate, hop, track, count, params, markers, nmarkers, nullptr, 0, bend};
+    return psola_plan_out(c, grains, ngrains, nsamples);
+  });
+}
+
+int mx_psola_plan_formant_bend(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                               const mx_psola_params *params, const mx_marker *markers, int nmarkers,
+                               const mx_formant_point *points, int npoints, const float *bend, mx_psola_fgrain **fgrains,
+                               int64_t *ngrains, int64_t *nsamples) {
+  return mx_guard([&] {
+    const PsolaCall c{n, sampleRate, hop, track, count, params, markers, nmarkers, points, npoints, bend};
+    return psola_plan_out(c, fgrains, ngrains, nsamples);
+  });
+}
+
+int mx_psola_render_bend_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                             const mx_psola_params *params, const mx_marker *markers, int nmarkers,
+                             const mx_formant_point *points, int npoints, const float *bend, float *d_pcm_f32,
+                             int16_t *d_pcm_i16) {
+  return mx_guard([&] {
+    const PsolaCall c{0, sampleRate, hop, track, count, params, markers, nmarkers, points, npoints, bend};
+    return psola_render(ctx, a, c, d_pcm_f32, d_pcm_i16, false);
+  });
+}
+
+int mx_psola_render_bend(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_f0 *track, int64_t count,
+                         const mx_psola_params *params, const mx_marker *markers, int nmarkers, const mx_formant_point *points,
+                         int npoints, const float *bend, float *pcm_f32_out, int16_t *pcm_i16_out) {
+  return mx_guard([&] {
+    const PsolaCall c{0, sampleRate, hop, track, count, params, markers, nmarkers, points, npoints, bend};
     return psola_render(ctx, a, c, pcm_f32_out, pcm_i16_out, true);
   });
 }

@@ -12,6 +12,8 @@ namespace mx {
 
 namespace {
 
+constexpr double kTrackerHalf = 2048.0;  // W of the f0 tracker (include/melonix_amd.h: N = 4096, W = N/2)
+
 int invalid(std::string &err, const char *fmt, long long a = 0, long long b = 0) {
   char buf[160];
   snprintf(buf, sizeof buf, fmt, a, b);
@@ -21,11 +23,12 @@ int invalid(std::string &err, const char *fmt, long long a = 0, long long b = 0)
 
 // The plan: arguments checked, then the marks, one record per synthesis mark.  The window fields are the same for both record
 // kinds; source(record, a_m, s, m) — the record, its analysis mark, its synthesis mark and the mark's index — then fills in
-// where the grain reads the source.
+// where the grain reads the source.  bend: null, or count semitone values over the source's frames, added to the markers' bend
+// at the frame whose measurement is centred on the grain's analysis mark (fr below).
 template <class Rec, class Source>
 int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
-               const mx_marker *markers, int nmarkers, std::vector<Rec> &grains, int64_t &nsamples, std::string &err,
-               Source source) {
+               const mx_marker *markers, int nmarkers, const float *bend, std::vector<Rec> &grains, int64_t &nsamples,
+               std::string &err, Source source) {
   grains.clear();
   nsamples = 0;
   if (n < 0 || n > (int64_t)INT32_MAX - 2 * MX_AUDIO_PAD) return invalid(err, "%lld samples: outside [0, INT32_MAX - 2*MX_AUDIO_PAD]", n);
@@ -36,6 +39,8 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
   if (!std::isfinite(p.threshold) || !std::isfinite(p.rms_floor)) return invalid(err, "threshold / rms_floor is not finite");
   if (!(p.unvoiced_period >= 32.f && p.unvoiced_period <= (float)MX_PSOLA_MAX_HALF))
     return invalid(err, "unvoiced period outside [32, %lld]", MX_PSOLA_MAX_HALF);
+  for (int64_t h = 0; bend && h < count; ++h)
+    if (!std::isfinite(bend[h])) return invalid(err, "bend of frame %lld is not finite", h);
   // the output length, and the marker checks, are the phase vocoder's
   PvPlan pv;
   if (const int rc = build_pv_plan(markers, nmarkers, sampleRate, n, pv, err)) return rc;
@@ -45,11 +50,14 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
   if (n == 0 || L == 0) return MX_OK;
 
   const double U = (double)p.unvoiced_period;
+  // the frame nearest to source position x
+  auto frame_at = [&](double x) {
+    const double h = std::floor(x / (double)hop + 0.5);
+    return (int64_t)(h < 0. ? 0. : (h > (double)(count - 1) ? (double)(count - 1) : h));
+  };
   // P(x) and voiced(x): period_of(x) < 0 marks an unvoiced frame
   auto period_at = [&](double x, bool &voiced) {
-    double h = std::floor(x / (double)hop + 0.5);
-    h = h < 0. ? 0. : (h > (double)(count - 1) ? (double)(count - 1) : h);
-    const mx_f0 &r = track[(int64_t)h];
+    const mx_f0 &r = track[frame_at(x)];
     voiced = r.tau > 0 && r.aperiodicity < p.threshold && r.rms >= p.rms_floor && std::isfinite(r.period) && r.period >= 2.f &&
              r.period <= (float)MX_PSOLA_MAX_HALF;
     return voiced ? (double)r.period : U;
@@ -58,6 +66,7 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
   // analysis marks
   std::vector<double> a, per;
   std::vector<char> vo;
+  std::vector<int64_t> fr;  // the frame each mark reads the curve at (where there is one)
   for (double am = 0.;;) {
     bool v;
     const double pm = period_at(am, v);
@@ -65,6 +74,8 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
     a.push_back(am);
     per.push_back(pm);
     vo.push_back((char)v);
+    // the tracker's frame h reads samples [h hop - 2048, h hop + tau): what it measures lies (2048 - period) / 2 before h hop
+    if (bend) fr.push_back(frame_at(am + (kTrackerHalf - pm) / 2.0));
     am = am + pm;
   }
 
@@ -84,7 +95,9 @@ int plan_marks(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t c
     if (!(s - H < (double)L)) break;
     double r = 1.;
     if (vo[m]) {
-      r = std::exp2((double)tm.time2pitchbend(t, hint_b) / 12.0);
+      double b = (double)tm.time2pitchbend(t, hint_b);
+      if (bend) b = b + (double)bend[fr[m]];
+      r = std::exp2(b / 12.0);
       r = !(r >= 0.5) ? 0.5 : (r > 2. ? 2. : r);
     }
     Rec g{};
@@ -157,8 +170,8 @@ int check_grains(const Rec *g, int64_t ngrains, int64_t nsamples, int64_t n, std
 
 int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
                      const mx_marker *markers, int nmarkers, std::vector<mx_psola_grain> &grains, int64_t &nsamples,
-                     std::string &err) {
-  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, grains, nsamples, err,
+                     std::string &err, const float *bend) {
+  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, bend, grains, nsamples, err,
                     [](mx_psola_grain &g, double am, double s, int32_t m) {
                       const double d = am - s, dfl = std::floor(d);
                       g.src_off = (int32_t)dfl;
@@ -173,7 +186,7 @@ int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int
 
 int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int64_t count, const mx_psola_params &p,
                      const mx_marker *markers, int nmarkers, const mx_formant_point *points, int npoints,
-                     std::vector<mx_psola_fgrain> &fgrains, int64_t &nsamples, std::string &err) {
+                     std::vector<mx_psola_fgrain> &fgrains, int64_t &nsamples, std::string &err, const float *bend) {
   fgrains.clear();
   nsamples = 0;
   if (npoints < 0 || (npoints > 0 && !points)) return invalid(err, "bad formant curve: %lld points", npoints);
@@ -192,7 +205,7 @@ int build_psola_plan(int64_t n, int sampleRate, int hop, const mx_f0 *track, int
     return (double)q0.semitones +
            (x - (double)q0.sample) * ((double)q1.semitones - (double)q0.semitones) / ((double)q1.sample - (double)q0.sample);
   };
-  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, fgrains, nsamples, err,
+  return plan_marks(n, sampleRate, hop, track, count, p, markers, nmarkers, bend, fgrains, nsamples, err,
                     [&](mx_psola_fgrain &f, double am, double, int32_t) {
                       double phi = std::exp2(curve(am) / 12.0);
                       phi = !(phi >= 0.5) ? 0.5 : (phi > 2. ? 2. : phi);
