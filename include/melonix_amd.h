@@ -36,7 +36,9 @@ typedef struct mx_ctx mx_ctx;     /* one per GPU / per process rank */
 typedef struct mx_audio mx_audio; /* device-resident mono f32 audio */
 
 /* Per-frame pitch record (build-defined op, SURVEY §8 a-6: the reference has no
- * detector; note law from app.cpp:499-516). */
+ * detector; note law from app.cpp:499-516).  A frame that holds a sample that is Inf or NaN has a row without a finite
+ * magnitude; its pitch record has kmin <= bin <= kmax and a mag that is not finite, and that record is identical whatever
+ * frames_per_block or launch split computes it.  Rows and records of frames that do not hold the sample are unaffected. */
 typedef struct mx_pitch {
   int32_t bin; /* argmax_k mag[k], k in [kmin,kmax], ties -> lowest k */
   float mag;   /* mag[bin] */
@@ -665,8 +667,13 @@ int mx_psola_render_formant_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, 
  *   kmin = max(1, ceil(fmin * 1024 / sr)), kmax = min(511, floor(fmax * 1024 / sr)); fmax = 0 means sr / 2.
  * The level matters by design: log1p(compress * m) is linear in m for a quiet take, so a quiet take has small flux (at a
  * tenth of the level the curve is not a tenth, and the picker's additive term delta does not scale).  A frame of zeros has
- * c = 0; silence has flux exactly 0.  A sample that is Inf or NaN makes its frames' values Inf or NaN; the picker counts
- * those as 0.
+ * c = 0; silence has flux exactly 0.  max(0, d) keeps a NaN d: a frame whose 1024 samples hold a NaN has flux NaN, and so
+ * has frame h+lag, which is measured against it; a frame that holds +Inf or -Inf has a flux that is not finite.  Every other
+ * frame keeps the bytes it has without the bad sample; the picker and the tempo estimate count values that are not finite as 0.
+ * Accuracy: the f32-versus-f64 yardstick of the tests, |error| <= 2e-5 * max_h flux_h + 1e-9, is claimed for compress * level up
+ * to 1e4, level the take's largest |sample| (compress <= 1e4 for a take at full scale).  log1p has slope compress at m = 0, so above
+ * that the transform's f32 noise on the quiet bins (about 1e-7 of the frame's peak) stops being small against the curve: at
+ * compress = 1e6 the tests allow 1.64 x the yardstick on a take with a 1e-4 noise floor.
  * The per-frame reduction has one fixed order, so frame h's value depends on nothing but its samples and frame h-lag's:
  * the same bytes whatever the launch split (first_frame, count) or the run length a walker takes.  No spectrum goes to HBM:
  * the launch writes 4 bytes per frame. */

@@ -130,14 +130,16 @@ MX_ONSET_HD void compressed(int lane, const LaneConsts &c, const float2 (&z)[8],
     out[r] = log1pf(compress * m);
   }
 }
-// the lane's share of the flux: bins lane + 64 r in ascending r, those inside [kmin, kmax]
+// the lane's share of the flux: bins lane + 64 r in ascending r, those inside [kmin, kmax].  max(0, d) keeps a NaN, as
+// np.maximum does: !(d <= 0) is d > 0 for every d that is not NaN (the same additions in the same order), and true for a NaN,
+// which then stays in the sum — a frame that could not be measured does not read as "no flux".
 MX_ONSET_HD float lane_flux(int lane, const float (&cur)[8], const float (&prev)[8], int kmin, int kmax) {
   float s = 0.f;
   MX_ONSET_UNROLL
   for (int r = 0; r < 8; ++r) {
     const int k = lane + 64 * r;
     const float d = cur[r] - prev[r];
-    if (k >= kmin && k <= kmax && d > 0.f) s += d;
+    if (k >= kmin && k <= kmax && !(d <= 0.f)) s += d;
   }
   return s;
 }

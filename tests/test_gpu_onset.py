@@ -123,6 +123,14 @@ def test_short_inputs_and_hops(gpu_ctx, n, hop):
 
 @pytest.mark.parametrize("lag", [1, 2, 3, 4])
 def test_lags_and_a_band_at_44100(gpu_ctx, cases, lag):
+    """Every lag at 48 kHz over the whole band and at 44.1 kHz over 100-5000 Hz, and compress at 7.5, 1e4 and 1e6 (the top of
+    its range), on a take with a noise floor (notes30's first second: the 1e-4 bed under the notes).  Up to 1e4 the yardstick
+    holds.  At 1e6 the f32 transform's noise on the quiet bins goes through log1p at a slope near compress: the CPU emulation
+    (libm's log1pf and sqrtf) is off by at most 0.41 x the yardstick on this take (lags 1..4: 0.41, 0.31, 0.26, 0.24; pinned by
+    tests/test_onset_host.py::test_lags_and_high_compression_on_the_cpu), and the device, whose log1pf and sqrtf are its own, is
+    allowed 4 x that: 1.64 x the yardstick."""
+    from test_onset_host import DEVICE_FACTOR, EMU_ERROR_AT_1E6
+
     w = cases["notes30"][0][:SR]
     a = gpu_ctx.upload(w)
     try:
@@ -134,6 +142,11 @@ def test_lags_and_a_band_at_44100(gpu_ctx, cases, lag):
         # another compression: the curve scales with it, the bound with the curve
         ref = R.flux(w, SR, HOP, lag=lag, compress=7.5)
         assert np.abs(gpu_ctx.onset_flux(a, SR, HOP, lag=lag, compress=7.5) - ref).max() <= flux_tol(ref)
+        for compress, share in ((1e4, 1.0), (1e6, DEVICE_FACTOR * EMU_ERROR_AT_1E6)):
+            ref = R.flux(w, SR, HOP, lag=lag, compress=compress)
+            err = np.abs(gpu_ctx.onset_flux(a, SR, HOP, lag=lag, compress=compress) - ref).max()
+            print(f"lag {lag} compress {compress:g}: worst error {err:.3e} = {err / flux_tol(ref):.3f} x the yardstick")
+            assert err <= share * flux_tol(ref), (lag, compress, err / flux_tol(ref))
     finally:
         a.free()
 

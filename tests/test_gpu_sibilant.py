@@ -11,7 +11,7 @@ import pytest
 import onset_ref as R
 import sibilant_ref as S
 from conftest import DevBuf
-from test_sibilant_host import check_features, decision_margins
+from test_sibilant_host import check_features, decision_margins, with_gain_edges
 
 pytestmark = pytest.mark.gpu
 
@@ -203,7 +203,9 @@ def _point_lists(rng, n):
 @pytest.mark.parametrize("n", [1, 255, TILE - 1, TILE, TILE + 1, 3 * TILE + 5])
 def test_gain_equals_numpy(mxlib, gpu_ctx, n):
     rng = np.random.default_rng(n)
-    x = rng.standard_normal(n).astype(np.float32)
+    # noise, its first samples replaced by NaN, +-Inf, -0, subnormals, the largest normals and a small normal: the point lists
+    # put gains of 2.5 (Inf from 3.4e38), 0.37 and 0.01 (a subnormal from 1.5e-38) on them
+    x = with_gain_edges(rng.standard_normal(n))
     pad = mxlib.MX_AUDIO_PAD
     a = gpu_ctx.upload(x)
     try:

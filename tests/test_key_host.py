@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bad_samples as B
 import key_ref as K
 import yin_ref as Y
 
@@ -143,6 +144,22 @@ def test_noise_silence_and_bad_samples_on_the_cpu(emu, cases):
         assert holds.any() and not got[holds].any() and got[~holds][:, 38].all()
         assert not case.ref[holds].any()
         check_records(got, case, f"sample {bad}")
+
+
+@pytest.mark.parametrize("k", B.CHROMA_SCALES)
+def test_levels_far_off_full_scale_on_the_cpu(emu, cases, k):
+    """The `chord` take times 2^k from 2^-140 (subnormal samples) to 2^126: a record is never Inf or NaN; forty zeros below the
+    absolute floor and where the band maximum overflows f32 (2^80 and above); at 2^20 and 2^60 the peak count is the clean
+    take's and the weight the clean one times 2^k, byte for byte, and the other columns lie inside key_ref's bound on the scaled
+    take (tests/bad_samples.check_scaled_chroma says why they are not exact); 2^66 inside the bound as well."""
+    clean = emu.chroma(cases["chord"])
+    case = Case(B.scaled(cases["chord"].w, k))
+    got = emu.chroma(case)
+    B.check_scaled_chroma(got, clean, k, "emulation")
+    if k not in B.CHROMA_ZERO:
+        assert got[:, 38].all()
+        worst, left_out = check_records(got, case, f"2^{k}")
+        assert left_out <= GUARD_SHARE * len(got) and worst <= 0.25, (k, worst, left_out)
 
 
 def test_window_sums_on_the_cpu(emu, cases):

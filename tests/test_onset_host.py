@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bad_samples as B
 import onset_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -249,6 +250,91 @@ def test_the_kernels_arithmetic_on_the_cpu(onset_emu):
         assert onset_emu(w, 256, 0, len(ref), lag, R.band(SR, fmin, fmax), run=5).tobytes() == got.tobytes()
         assert onset_emu(w, 256, 37, 50, lag, R.band(SR, fmin, fmax), run=7).tobytes() == got[37:87].tobytes()
     assert not onset_emu(np.zeros(5000, np.float32), 255, 0, 20).any()
+
+
+BAD_TAKE = (8000, 24000)  # notes5's samples: the first note's attack (sample 12000) and 0.21 s of the bed before it
+
+
+@pytest.mark.parametrize("name", list(B.BAD))
+def test_a_bad_sample_on_the_cpu(onset_emu, name):
+    """A NaN sample makes the frames that hold it, and the frames `lag` later, NaN — where onset_ref.flux is not finite, frame
+    for frame; an Inf sample leaves its frames not finite; every other frame keeps the clean take's bytes; the same bytes
+    whatever the run or a split inside the affected frames (tests/bad_samples.py; tests/test_gpu_bad_samples.py asks the
+    same of the device)."""
+    w = R.notes(0.005)[BAD_TAKE[0]:BAD_TAKE[1]]
+    n = len(w)
+    for pos, s in B.positions(n, 256, 512, 512).items():
+        v = B.with_bad(w, s, B.BAD[name])
+        for lag in (1, 4):
+            with np.errstate(invalid="ignore"):
+                ref = R.flux(v, SR, 256, lag=lag) if name == "nan" else None
+            B.check_flux(lambda first, count, run: onset_emu(v, 256, first, count, lag, run=run or 8),
+                         lambda first, count, run: onset_emu(w, 256, first, count, lag, run=run or 8), ref, n, 256, lag, s, name,
+                         (name, pos, lag))
+
+
+# The emulation's worst error at compress = 1e6 over lags 1..4 on test_lags_and_high_compression's take, in units of the
+# yardstick 2e-5 * max + 1e-9 (measured: 0.41, 0.31, 0.26, 0.24 for lags 1..4; 0.032 at 1e4, 0.15 at 1e5).  The device is allowed
+# DEVICE_FACTOR times this in tests/test_gpu_onset.py: its log1pf and sqrtf are not libm's, and the emulation cannot vouch for them.
+EMU_ERROR_AT_1E6 = 0.41
+DEVICE_FACTOR = 4.0
+
+
+@pytest.mark.parametrize("lag", [1, 2, 3, 4])
+def test_lags_and_high_compression_on_the_cpu(onset_emu, lag):
+    """compress at 1e4 and at 1e6, the top of the accepted range, on a take with a noise floor (notes30's first second: the 1e-4
+    bed under the notes).  log1p(compress * m) has slope compress at m = 0, so the f32 transform's noise on the quiet bins
+    (about 1e-7 of the frame's peak) is no longer small against the curve once compress * level passes about 1e4.  At 1e4 the
+    yardstick holds; at 1e6 the emulation's worst error is EMU_ERROR_AT_1E6 = 0.41 of the yardstick on this take (libm's
+    log1pf and sqrtf), which this test pins: the device's bound is derived from it."""
+    w = R.notes(0.030)[:SR]
+    for compress, share in ((1e4, 1.0), (1e6, EMU_ERROR_AT_1E6)):
+        ref = R.flux(w, SR, 256, lag=lag, compress=compress)
+        got = onset_emu(w, 256, 0, len(ref), lag, compress=compress)
+        err, tol = np.abs(got - ref).max(), 2e-5 * ref.max() + 1e-9
+        print(f"lag {lag} compress {compress:g}: worst error {err:.3e} = {err / tol:.3f} x the yardstick {tol:.3e}")
+        assert err <= share * tol, (lag, compress, err / tol)
+
+
+def test_the_chain_with_a_nan_on_the_cpu(mxlib, onset_emu):
+    """notes5 with one NaN: the picker reads the affected frames as 0, mx_onset_pick equals onset_ref.pick on the emulation's
+    flux, and every onset of the clean take whose decision window [f - pre_avg, f + max(post_max, post_avg)] does not reach an
+    affected frame survives unchanged — five of the six (the condition on the reference alone: at least three quarters)."""
+    w = R.notes(0.005)
+    v = B.with_bad(w, CHAIN_NAN, np.nan)
+    frames = B.frame_count(len(w), 256)
+    with np.errstate(invalid="ignore"):
+        ref_clean, ref_bad = R.flux(w, SR, 256), R.flux(v, SR, 256)
+    keep = chain_survivors(R.pick(ref_clean, 256), R.pick(ref_bad, 256), len(w), "reference")
+    assert len(keep) >= 0.75 * len(R.pick(ref_clean, 256))
+    flux = onset_emu(v, 256, 0, frames)
+    _same_picks(mxlib, flux)
+    chain_survivors(R.pick(onset_emu(w, 256, 0, frames), 256), R.pick(flux, 256), len(w), "emulation")
+
+
+CHAIN_NAN = 290 * 256 + 100  # inside the pre_avg window of notes5's fourth onset (frame 304), clear of the other five
+
+
+def chain_survivors(clean, bad, n, what, lag=1):
+    """clean / bad: onset_ref.pick lists (or the library's records as such tuples) of notes5 without / with the NaN at CHAIN_NAN.
+    -> the clean onsets whose decision window holds no affected frame; each must be in `bad` unchanged.  The window is
+    [f - wait - pre_avg, f + post_max]: the frames the local maximum and the mean read, and those of any frame close enough
+    before f to take its place under `wait` (the take's onsets lie 75 frames and more apart: no longer chain exists)."""
+    p = R.PICK_DEFAULTS
+    hold = B.holding(n, 256, 512, 512, CHAIN_NAN)
+    affected = np.nonzero(hold | B.lagged(hold, lag))[0]
+    keep = []
+    for o in clean:
+        f = o[1]
+        lo, hi = f - p["wait"] - max(p["pre_avg"], p["pre_max"]), f + max(p["post_max"], p["post_avg"])
+        if not ((affected >= lo) & (affected <= hi)).any():
+            keep.append(o)
+    have = {o[1]: o for o in bad}
+    for o in keep:
+        assert o[1] in have, (what, o)
+        assert (o[0], np.float32(o[2]).tobytes(), np.float32(o[3]).tobytes()) == (have[o[1]][0], np.float32(have[o[1]][2]).tobytes(),
+                                                                                  np.float32(have[o[1]][3]).tobytes()), (what, o)
+    return keep
 
 
 def test_onset_kernels_do_not_spill():

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bad_samples as B
 import onset_ref as R
 import sibilant_ref as S
 
@@ -117,6 +118,68 @@ def test_edges_of_the_split_and_of_the_frame_on_the_cpu(emu, takes):
         ref = S.features(v, SR, hop)
         assert len(ref) == -(-n // hop)
         check_features(emu.features(v, hop, 0, len(ref)), ref, f"n {n} hop {hop}")
+
+
+BAD_TAKE = (14000, 30000)  # the synthetic take's samples: the end of the first vowel, the "s" and the next vowel's start
+
+
+@pytest.mark.parametrize("name", list(B.BAD))
+def test_a_bad_sample_on_the_cpu(emu, takes, name):
+    """An Inf or NaN sample leaves the frames that hold it without a finite low + high; zero_crossings (NaN is "not negative",
+    Inf has its sign) equals the reference on every frame; every other record keeps the clean take's bytes; the same bytes
+    whatever the run or a split inside the affected frames (tests/bad_samples.py; tests/test_gpu_bad_samples.py asks the same
+    of the device)."""
+    w = takes["take"][0][BAD_TAKE[0]:BAD_TAKE[1]]
+    n = len(w)
+    for pos, s in B.positions(n, HOP, 512, 512).items():
+        v = B.with_bad(w, s, B.BAD[name])
+        with np.errstate(invalid="ignore"):
+            zc = S.features(v, SR, HOP)["zero_crossings"]
+        B.check_features(lambda first, count, run: emu.features(v, HOP, first, count, run=run or 8),
+                         lambda first, count, run: emu.features(w, HOP, first, count, run=run or 8), zc, n, HOP, s, (name, pos))
+
+
+def test_levels_scale_exactly_on_the_cpu(emu, takes):
+    """The take times 2^k, k in -30, -8, 8, 30: low and high are the clean bytes times 2^2k, centroid and crossings the clean
+    bytes (all four k hold on the emulation; 2^-40 and 2^40 do as well)."""
+    w = takes["take"][0][BAD_TAKE[0]:BAD_TAKE[1]]
+    frames = B.frame_count(len(w), HOP)
+    clean = emu.features(w, HOP, 0, frames)
+    assert clean["low"].all() and clean["high"].all()
+    for k in B.SIB_SCALES + (-40, 40):
+        B.check_scaled_features(emu.features(B.scaled(w, k), HOP, 0, frames), clean, k, "emulation")
+
+
+SIB_CHAIN_NAN = 120 * HOP + 7  # inside the take's second vowel, 28 frames from the nearest sibilant
+
+
+def segment_survivors(clean, bad, n, what):
+    """clean / bad: sibilant_ref.segments lists (or the library's records as such tuples) of the take without / with the NaN at
+    SIB_CHAIN_NAN -> the clean segments whose decision window [first - merge_gap - 1, last + merge_gap + 1] (the frames that open,
+    continue, close or merge it) holds no affected frame; each must be in `bad` unchanged."""
+    gap = S.SEGMENT_DEFAULTS["merge_gap"]
+    affected = np.nonzero(B.holding(n, HOP, 512, 512, SIB_CHAIN_NAN))[0]
+    keep = [s for s in clean if not ((affected >= s[2] - gap - 1) & (affected <= s[2] + s[3] + gap)).any()]
+    have = {s[2]: s for s in bad}
+    for s in keep:
+        assert s[2] in have and tuple(s[:4]) == tuple(have[s[2]][:4]), (what, s)
+        assert np.float32(s[4]).tobytes() == np.float32(have[s[2]][4]).tobytes() and np.float32(s[5]).tobytes() == np.float32(have[s[2]][5]).tobytes(), (what, s)
+    return keep
+
+
+def test_the_chain_with_a_nan_on_the_cpu(mxlib, emu, takes):
+    """The take with one NaN inside a vowel: mx_sibilants equals sibilant_ref.segments on the emulation's records, and every
+    segment of the clean take whose decision window does not reach a frame that holds the NaN survives unchanged — all three
+    (the condition on the reference alone: at least three quarters)."""
+    w, ref = takes["take"]
+    v = B.with_bad(w, SIB_CHAIN_NAN, np.nan)
+    with np.errstate(invalid="ignore"):
+        ref_bad = S.features(v, SR, HOP)
+    clean = S.segments(ref, HOP)
+    assert len(segment_survivors(clean, S.segments(ref_bad, HOP), len(w), "reference")) >= 0.75 * len(clean)
+    rec = emu.features(v, HOP, 0, len(ref))
+    _same_segments(mxlib, rec)
+    segment_survivors(S.segments(emu.features(w, HOP, 0, len(ref)), HOP), S.segments(rec, HOP), len(w), "emulation")
 
 
 # ---- the host logic of the library against the reference ----
@@ -274,10 +337,23 @@ def test_protected_curves_pass_the_formant_plan(mxlib):
         assert inside and all(st == 65536 for st in inside)  # 0 st on the cores: the plain step
 
 
+# What a gain must carry like numpy does: NaN, Inf, -0, subnormals, the largest normals (Inf under a gain above 1) and a small
+# normal that a gain below 1 takes into the subnormals.
+GAIN_EDGES = np.array([np.nan, np.inf, -np.inf, -0.0, 1e-45, -1e-45, 1e-39, -1e-39, 3.4e38, -3.4e38, 1.5e-38, -1.5e-38], dtype=np.float32)
+
+
+def with_gain_edges(x):
+    """x with its first samples replaced by GAIN_EDGES (as many as fit)."""
+    x = np.array(x, dtype=np.float32, copy=True)
+    m = min(len(x), len(GAIN_EDGES))
+    x[:m] = GAIN_EDGES[:m]
+    return x
+
+
 def test_gain_arithmetic_equals_numpy(emu):
     rng = np.random.default_rng(5)
     for n in (1, 255, 2047, 2048, 2049, 6000):
-        x = rng.standard_normal(n).astype(np.float32)
+        x = with_gain_edges(rng.standard_normal(n))
         many = sorted(set(int(v) for v in rng.integers(-50, n + 50, 5000)))
         lists = [[(n // 2, 0.37)], [(n // 3, 2.5), (n // 3 + 1, 0.01)], [(-10, 0.5), (n + 10, 1.5)],
                  [(s, float(np.float32(rng.uniform(0.01, 4.0)))) for s in many]]
