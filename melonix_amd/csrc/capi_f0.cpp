@@ -24,21 +24,18 @@ int f0_range(int sampleRate, float fmin, float fmax, int &tmin, int &tmax) {
 }
 
 // What the tracker-side entry points share: their arguments, checked, with the search range they give
-struct F0Call {
-  mx_ctx *ctx;
-  const mx_audio *a;
-  int sampleRate, hop;
-  int64_t first_frame, count;
+struct F0Call : TrackCall {
   int tmin, tmax;
   float threshold;
 };
 
-// the frame span (frame_span: `out`) and what is the tracker's own: the threshold and the lag range
+// the frame span (frame_span: `out`) and what is the tracker's own: the threshold and the lag range, which checks the sample
+// rate — behind the threshold, so not track_parse's order
 int f0_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, float fmin,
              float fmax, float threshold, const void *out, F0Call &q) {
   if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
   if (!std::isfinite(threshold)) return fail(MX_ERR_INVALID, "threshold is not finite");
-  q = F0Call{ctx, a, sampleRate, hop, first_frame, count, 0, 0, threshold};
+  q = F0Call{{ctx, a, sampleRate, hop, first_frame, count}, 0, 0, threshold};
   return f0_range(sampleRate, fmin, fmax, q.tmin, q.tmax);
 }
 
@@ -117,15 +114,15 @@ int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, 
   return MX_OK;
 }
 
-// The host-pointer forms (staged_records): the track — decoded in place — passes through the staging buffer of the pitch
-// records, the states through the texels' and, where the call has candidates (`ladder`), those through the magnitude rows'.
+// The host-pointer forms with candidates (staged_records; the plain track is a staged_track): the track — decoded in place —
+// passes through the staging buffer of the pitch records, the candidates through the magnitude rows', the states through the texels'.
 // `in`: upload the caller's track and candidates; `run(d_track, d_cands, d_state)` queues the device form; the outputs that
 // are set come back.
 template <class F>
-int f0_staged(mx_ctx *ctx, int64_t count, bool ladder, const mx_f0 *track_in, const mx_f0_cand *cands_in, mx_f0 *track_out,
+int f0_staged(mx_ctx *ctx, int64_t count, const mx_f0 *track_in, const mx_f0_cand *cands_in, mx_f0 *track_out,
               mx_f0_cand *cands_out, uint8_t *state_out, F &&run) {
   const StagedSlot slots[] = {{kStagePitch, sizeof(mx_f0), track_in, track_out},
-                              {kStageMags, ladder ? MX_F0_CANDS * sizeof(mx_f0_cand) : 0, cands_in, cands_out},
+                              {kStageMags, MX_F0_CANDS * sizeof(mx_f0_cand), cands_in, cands_out},
                               {kStageTexels, state_out ? 1u : 0u, nullptr, state_out}};
   return staged_records(ctx, count, slots, "f0", [&](void *const *d) {
     return run(static_cast<mx_f0 *>(d[0]), static_cast<mx_f0_cand *>(d[1]), static_cast<uint8_t *>(d[2]));
@@ -150,8 +147,7 @@ int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t
   return mx_guard([&]() -> int {
     F0Call q;
     if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, out, q)) return rc;
-    return f0_staged(ctx, count, false, nullptr, nullptr, out, nullptr, nullptr,
-                     [&](mx_f0 *d_track, mx_f0_cand *, uint8_t *) { return f0_launch(q, d_track, nullptr); });
+    return staged_track(q, kStagePitch, "f0", out, [&](mx_f0 *d_track) { return f0_launch(q, d_track, nullptr); });
   });
 }
 
@@ -169,7 +165,7 @@ int mx_f0_candidates(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, in
   return mx_guard([&]() -> int {
     F0Call q;
     if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, cands, q)) return rc;
-    return f0_staged(ctx, count, true, nullptr, nullptr, track, cands, nullptr,
+    return f0_staged(ctx, count, nullptr, nullptr, track, cands, nullptr,
                      [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) { return f0_launch(q, d_track, d_cands); });
   });
 }
@@ -192,7 +188,7 @@ int mx_f0_decode(mx_ctx *ctx, const mx_f0 *track, const mx_f0_cand *cands, int64
   return mx_guard([&]() -> int {
     mx_f0_decode_params dp;
     if (const int rc = decode_parse(ctx, track, cands, count, p, out, dp)) return rc;
-    return f0_staged(ctx, count, true, track, cands, out, nullptr, state, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *d_state) {
+    return f0_staged(ctx, count, track, cands, out, nullptr, state, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *d_state) {
       return decode_launch(ctx, d_track, d_cands, count, dp, d_track, d_state);
     });
   });
@@ -205,7 +201,7 @@ int mx_f0_track_decoded(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop,
     if (const int rc = decode_params(p, dp)) return rc;
     F0Call q;
     if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, out, q)) return rc;
-    return f0_staged(ctx, count, true, nullptr, nullptr, out, nullptr, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
+    return f0_staged(ctx, count, nullptr, nullptr, out, nullptr, nullptr, [&](mx_f0 *d_track, mx_f0_cand *d_cands, uint8_t *) {
       if (const int rc = f0_launch(q, d_track, d_cands)) return rc;
       return decode_launch(ctx, d_track, d_cands, count, dp, d_track, nullptr);
     });

@@ -2,7 +2,8 @@
 // types, the error slot behind mx_last_error, the per-N table cache, and the sequences written once: the owners of device
 // memory (DeviceArray for a call, GrowBuf for a context), the chunked host-staged loop (staged_batch), the PCM download
 // (pcm_to_host), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING phase clock (PhaseClock); and for
-// the per-frame tracks (f0, onset strength): the frame-span check (frame_span), the staged host form (staged_records), the
+// the per-frame tracks (f0, onset strength, sibilant features, chroma): the frame-span check (frame_span), the staged host form
+// (staged_records), a call's common head, its parse and its one-record host form (TrackCall, track_parse, staged_track), the
 // parameters in force and their defaults (params_or, params_default), the device tables built on the host (upload_table).
 // Not installed; include/melonix_amd.h is the boundary.
 #pragma once
@@ -423,6 +424,32 @@ int staged_records(mx_ctx *ctx, int64_t count, const StagedSlot (&slots)[K], con
   if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "%s download: %s", what, hipGetErrorString(e));
   stage_trim(ctx);
   return rc;
+}
+
+// The head of every per-frame track call (f0, onset strength, sibilant features, chroma): the arguments its two forms share,
+// checked.  A unit's own call derives from it and adds what its parameters give.
+struct TrackCall {
+  mx_ctx *ctx;
+  const mx_audio *a;
+  int sampleRate, hop;
+  int64_t first_frame, count;
+};
+// the frame span (frame_span: `out`), then the sample rate
+inline int track_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, const void *out,
+                       TrackCall &q) {
+  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
+  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  q = TrackCall{ctx, a, sampleRate, hop, first_frame, count};
+  return MX_OK;
+}
+// the context's pinned run length (0: the kernel's default); no track's bytes depend on it
+inline int pinned_run(const mx_ctx *ctx) { return ctx->frames_per_block > 0 ? ctx->frames_per_block : 0; }
+// The host form of a track with one kind of record (staged_records): q.count records of Rec pass through staging buffer `slot`
+// to `out`; `launch(d_out) -> status` is the device form.
+template <class Rec, class F>
+int staged_track(const TrackCall &q, StageSlot slot, const char *what, Rec *out, F &&launch) {
+  const StagedSlot slots[] = {{slot, sizeof(Rec), nullptr, out}};
+  return staged_records(q.ctx, q.count, slots, what, [&](void *const *d) { return launch(static_cast<Rec *>(d[0])); });
 }
 
 }  // namespace mx

@@ -12,20 +12,15 @@ namespace {
 const mx_chroma_params kChromaDefaults{100.f, 5000.f, 1e-4f, 0.05f};
 
 // What the chroma entry points share: their arguments, checked, and the band they give
-struct ChromaCall {
-  mx_ctx *ctx;
-  const mx_audio *a;
-  int sampleRate, hop;
-  int64_t first_frame, count;
+struct ChromaCall : TrackCall {
   int kmin, kmax;
   mx_chroma_params p;
 };
 
 int chroma_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                  const mx_chroma_params *params, const void *out, ChromaCall &q) {
-  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
-  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
-  const mx_chroma_params p = params_or(params, kChromaDefaults);
+  if (const int rc = track_parse(ctx, a, sampleRate, hop, first_frame, count, out, q)) return rc;
+  const mx_chroma_params &p = q.p = params_or(params, kChromaDefaults);
   if (!std::isfinite(p.fmin) || !std::isfinite(p.fmax) || !(p.fmin > 0.f) || !(p.fmax >= p.fmin))
     return fail(MX_ERR_INVALID, "chroma band [%g, %g] Hz: finite, 0 < fmin <= fmax", (double)p.fmin, (double)p.fmax);
   if (!std::isfinite(p.floor) || p.floor < 0.f) return fail(MX_ERR_INVALID, "floor %g must be finite and >= 0", (double)p.floor);
@@ -35,7 +30,8 @@ int chroma_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_
   const int kmax = (int)std::min((double)(chroma::kBins - 2), std::floor((double)p.fmax * n / sr));
   if (kmin > kmax)
     return fail(MX_ERR_INVALID, "empty band: bins [%d, %d] for %g..%g Hz at %d Hz", kmin, kmax, (double)p.fmin, (double)p.fmax, sampleRate);
-  q = ChromaCall{ctx, a, sampleRate, hop, first_frame, count, kmin, kmax, p};
+  q.kmin = kmin;
+  q.kmax = kmax;
   return MX_OK;
 }
 
@@ -59,16 +55,14 @@ int chroma_launch(const ChromaCall &q, mx_chroma_rec *d_out) {
   g.tw3 = t.tw3;
   g.ubase = t.ubase;
   g.out = d_out;
-  g.frames_per_block = q.ctx->frames_per_block > 0 ? q.ctx->frames_per_block : 0;  // (the context's pinned run length; the bytes do not depend on it)
+  g.frames_per_block = pinned_run(q.ctx);
   HIP_TRY(launch_chroma(g, q.ctx->stream));
   return MX_OK;
 }
 
-// the host form (staged_records): the records pass through the context's staging buffer of the magnitude rows
+// the host form: the records pass through the context's staging buffer of the magnitude rows
 int chroma_host(const ChromaCall &q, mx_chroma_rec *out) {
-  const StagedSlot slots[] = {{kStageMags, sizeof(mx_chroma_rec), nullptr, out}};
-  return staged_records(q.ctx, q.count, slots, "chroma records",
-                        [&](void *const *d) { return chroma_launch(q, static_cast<mx_chroma_rec *>(d[0])); });
+  return staged_track(q, kStageMags, "chroma records", out, [&](mx_chroma_rec *d_out) { return chroma_launch(q, d_out); });
 }
 
 int sum_args(const mx_ctx *ctx, const void *chroma, int64_t count, const void *jobs, int64_t njobs, const void *out) {

@@ -13,22 +13,16 @@ const mx_onset_pick_params kPickDefaults{3, 3, 25, 1, 8, 2.0, 1.0};
 const mx_timing_params kTimingDefaults{120.0, 4, 0.0, 1.0, 0.1, 2.0};
 
 // What the two flux entry points share: their arguments, checked, with the parameters in force and the band they give
-struct FluxCall {
-  mx_ctx *ctx;
-  const mx_audio *a;
-  int hop;
-  int64_t first_frame, count;
+struct FluxCall : TrackCall {
   mx_onset_flux_params p;
   int kmin, kmax;
 };
 
-// the frame span (frame_span: `out`) and what is the detector's own: the sample rate, the flux parameters and their band
+// the call's head (track_parse: `out`) and what is the detector's own: the flux parameters and their band
 int flux_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                const mx_onset_flux_params *params, const void *out, FluxCall &q) {
-  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
-  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
-  q = FluxCall{ctx, a, hop, first_frame, count, params_or(params, kFluxDefaults), 0, 0};
-  const mx_onset_flux_params &p = q.p;
+  if (const int rc = track_parse(ctx, a, sampleRate, hop, first_frame, count, out, q)) return rc;
+  const mx_onset_flux_params &p = q.p = params_or(params, kFluxDefaults);
   if (!std::isfinite(p.compress) || !(p.compress > 0.f) || p.compress > 1e6f)
     return fail(MX_ERR_INVALID, "compress %g outside (0, 1e6]", (double)p.compress);
   if (p.lag < 1 || p.lag > 4) return fail(MX_ERR_INVALID, "lag %d outside [1, 4]", p.lag);
@@ -56,15 +50,14 @@ int flux_launch(const FluxCall &q, float *d_flux) {
   g.kmax = q.kmax;
   g.compress = q.p.compress;
   g.flux = d_flux;
-  g.run = q.ctx->frames_per_block > 0 ? q.ctx->frames_per_block : 0;  // (the context's pinned run length; the bytes do not depend on it)
+  g.run = pinned_run(q.ctx);
   HIP_TRY(launch_onset_flux(g, q.ctx->stream));
   return MX_OK;
 }
 
-// the host form (staged_records): the values pass through the context's staging buffer of the pitch records
+// the host form: the values pass through the context's staging buffer of the pitch records
 int flux_host(const FluxCall &q, float *flux_out) {
-  const StagedSlot slots[] = {{kStagePitch, sizeof(float), nullptr, flux_out}};
-  return staged_records(q.ctx, q.count, slots, "flux", [&](void *const *d) { return flux_launch(q, static_cast<float *>(d[0])); });
+  return staged_track(q, kStagePitch, "flux", flux_out, [&](float *d_flux) { return flux_launch(q, d_flux); });
 }
 
 // the parameters in force (p null: the defaults), checked

@@ -12,24 +12,18 @@ const mx_sib_feature_params kFeatureDefaults{3500.f};
 const mx_sibilant_params kSegmentDefaults{0.6, 0.4, 1e-3, 64, 2, 6};
 
 // What the two feature entry points share: their arguments, checked, and the split bin
-struct FeatureCall {
-  mx_ctx *ctx;
-  const mx_audio *a;
-  int hop;
-  int64_t first_frame, count;
+struct FeatureCall : TrackCall {
   int ks;
 };
 
 int feature_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count,
                   const mx_sib_feature_params *params, const void *out, FeatureCall &q) {
-  if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
-  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  if (const int rc = track_parse(ctx, a, sampleRate, hop, first_frame, count, out, q)) return rc;
   const mx_sib_feature_params p = params_or(params, kFeatureDefaults);
   const double sr = (double)sampleRate;
   if (!std::isfinite(p.split_hz) || !(p.split_hz > 0.f) || (double)p.split_hz > sr / 2.0)
     return fail(MX_ERR_INVALID, "split %g Hz outside (0, %g]", (double)p.split_hz, sr / 2.0);
-  const int ks = (int)std::max(1.0, std::min(std::ceil((double)p.split_hz * 1024.0 / sr), 512.0));
-  q = FeatureCall{ctx, a, hop, first_frame, count, ks};
+  q.ks = (int)std::max(1.0, std::min(std::ceil((double)p.split_hz * 1024.0 / sr), 512.0));
   return MX_OK;
 }
 
@@ -44,16 +38,14 @@ int feature_launch(const FeatureCall &q, mx_sib_feat *d_feat) {
   g.count = q.count;
   g.ks = q.ks;
   g.out = d_feat;
-  g.run = q.ctx->frames_per_block > 0 ? q.ctx->frames_per_block : 0;  // (the context's pinned run length; the bytes do not depend on it)
+  g.run = pinned_run(q.ctx);
   HIP_TRY(launch_sib_features(g, q.ctx->stream));
   return MX_OK;
 }
 
-// the host form (staged_records): the records pass through the context's staging buffer of the pitch records
+// the host form: the records pass through the context's staging buffer of the pitch records
 int feature_host(const FeatureCall &q, mx_sib_feat *feat_out) {
-  const StagedSlot slots[] = {{kStagePitch, sizeof(mx_sib_feat), nullptr, feat_out}};
-  return staged_records(q.ctx, q.count, slots, "sibilant features",
-                        [&](void *const *d) { return feature_launch(q, static_cast<mx_sib_feat *>(d[0])); });
+  return staged_track(q, kStagePitch, "sibilant features", feat_out, [&](mx_sib_feat *d_feat) { return feature_launch(q, d_feat); });
 }
 
 // the parameters in force (p null: the defaults), checked

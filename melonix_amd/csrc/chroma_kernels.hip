@@ -35,28 +35,14 @@ static_assert(t1_size<FP>() == FP::M, "one spectrum fills the FFT image");
 static_assert(4 * (kMaxPeaks + 1) <= 2 * FP::M, "the peak list fits the FFT image (as floats)");
 static_assert(16 * FP::T == kBins && kCols <= 64, "16 bins per thread, the columns in one wave");
 
-// The three passes of stft_core.h on the register image Y (thread t's point c = t + T*e in Y[e]) and the real-FFT split:
-// X[o] = 2 * DFT_N(y)[out_bin(t, o)].  Leaves the image busy: the caller synchronises before it writes it.
+// wave_walk.h's three passes on the register image Y (thread t's point c = t + T*e in Y[e]) and the real-FFT split:
+// X[o] = 2 * DFT_N(y)[out_bin(t, o)].  The passes' first barrier is behind every wave's last read of the previous frame's peak
+// list.  Leaves the image busy: the caller synchronises before it writes it.
 __device__ __forceinline__ void forward(int t, bool wave0, const cpx (&Y)[FP::E], cpx (&X)[FP::E], cpx *img, const cpx *ltw2,
                                         const cpx (&w3b)[3], cpx ulo0, cpx uhi0) {
-  using P = FP;
-  cpx v[P::E];
-  pass1<P>(Y, v);
-  __syncthreads();  // every wave is done with the image's previous contents (the previous frame's peak list)
-  store_t1<P>(t, v, img);
-  __syncthreads();
-  cpx w2[P::R2 - 1];
-  load_t1_tw2<P>(t, v, img, ltw2, w2);
-  __syncthreads();
-  pass2_reg<P>(v, w2);
-  store_t2<P>(t, v, img);
-  __syncthreads();
-  load_t2<P>(t, v, img);
-  cpx w3r[P::R3 - 1];
-  root_powers7(w3b, w3r);
-  if (wave0) pass3_reg<P, true>(t, v, w3r);
-  else pass3_reg<P, false>(t, v, w3r);
-  post_split<P>(t, wave0, ulo0, uhi0, v, X);
+  cpx v[FP::E];
+  walk_passes<FP>(t, wave0, Y, v, img, ltw2, w3b);
+  post_split<FP>(t, wave0, ulo0, uhi0, v, X);
 }
 
 __global__ __launch_bounds__(FP::T) void chroma_frames(const ChromaArgs a) {
@@ -74,11 +60,10 @@ __global__ __launch_bounds__(FP::T) void chroma_frames(const ChromaArgs a) {
   post_bases<P>(t_, a.ubase, ulo0, uhi0);
   cpx w3b[3];
   load_w3_bases<P>(a.tw3, t_ ? t_ : P::NS3 / 2, w3b);
-  for (int i = t_; i < P::TW2; i += P::T) ltw2[i] = a.tw2[i];
+  fill_ltw2<P>(t_, a.tw2, ltw2);
 
-  const unsigned lb = xcd_block(blockIdx.x, gridDim.x);
-  const int64_t f0 = (int64_t)lb * a.frames_per_block;
-  const int64_t f1 = f0 + a.frames_per_block < a.count ? f0 + a.frames_per_block : a.count;
+  int64_t f0, f1;
+  block_run(a.frames_per_block, a.count, f0, f1);
   if (f0 >= f1) return;
   const float *const base = a.audio + MX_AUDIO_PAD - kBins;
   cpx xr[P::E];
@@ -159,10 +144,8 @@ __global__ __launch_bounds__(64) void chroma_sum(const float *rec, int64_t count
 hipError_t launch_chroma(const ChromaArgs &a0, hipStream_t s) {
   if (a0.count <= 0) return hipSuccess;
   ChromaArgs a = a0;
-  if (a.frames_per_block <= 0) a.frames_per_block = 8;
-  while ((a.count + a.frames_per_block - 1) / a.frames_per_block > (1ll << 30)) a.frames_per_block *= 2;  // (the grid's x extent)
-  const int64_t blocks = (a.count + a.frames_per_block - 1) / a.frames_per_block;
-  hipLaunchKernelGGL(chroma_frames, dim3((unsigned)blocks), dim3(FP::T), 0, s, a);
+  const dim3 grid = walk_grid(a.count, a.frames_per_block, kPlan4096Run);
+  hipLaunchKernelGGL(chroma_frames, grid, dim3(FP::T), 0, s, a);
   return hipGetLastError();
 }
 

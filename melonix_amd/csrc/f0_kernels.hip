@@ -79,36 +79,13 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k)
   return ((unsigned long long)hi << 32) | lo;
 }
 
-// The three passes of stft_core.h on the register image Y (thread t's point c = t + T*e in Y[e]): on return v holds
-// the transform in pass 3's layout (v[r] = Z[t + NS3 r], v[q_index(r)] = Z[k0q + NS3 r]).  Leaves the image busy:
-// the caller synchronises before it writes it.
-__device__ __forceinline__ void f0_passes(int t, bool wave0, const cpx (&Y)[FP::E], cpx (&v)[FP::E], cpx *img,
-                                          const cpx *ltw2, const cpx (&w3b)[3]) {
-  using P = FP;
-  pass1<P>(Y, v);
-  __syncthreads();  // every wave is done with the image's previous contents
-  store_t1<P>(t, v, img);
-  __syncthreads();
-  cpx w2[P::R2 - 1];
-  load_t1_tw2<P>(t, v, img, ltw2, w2);
-  __syncthreads();
-  pass2_reg<P>(v, w2);
-  store_t2<P>(t, v, img);
-  __syncthreads();
-  load_t2<P>(t, v, img);
-  cpx w3r[P::R3 - 1];
-  root_powers7(w3b, w3r);
-  if (wave0) pass3_reg<P, true>(t, v, w3r);
-  else pass3_reg<P, false>(t, v, w3r);
-}
-
-// Forward real transform: X[o] = 2 * DFT_N(x)[out_bin(t, o)]; ny (thread 0) = 2 * DFT_N(x)[M], the Nyquist bin post()
-// replaces by bin M/2.
+// Forward real transform (wave_walk.h's passes and split): X[o] = 2 * DFT_N(x)[out_bin(t, o)]; ny (thread 0) =
+// 2 * DFT_N(x)[M], the Nyquist bin post() replaces by bin M/2.
 __device__ __forceinline__ void f0_forward(int t, bool wave0, const cpx (&Y)[FP::E], cpx (&X)[FP::E], float &ny, cpx *img,
                                            const cpx *ltw2, const cpx (&w3b)[3], cpx ulo0, cpx uhi0) {
   using P = FP;
   cpx v[P::E];
-  f0_passes(t, wave0, Y, v, img, ltw2, w3b);
+  walk_passes<P>(t, wave0, Y, v, img, ltw2, w3b);
   ny = 2.0f * (v[0].x - v[0].y);  // X[M] = Re Z[0] - Im Z[0] (thread 0's P-butterfly element 0)
   post_split<P>(t, wave0, ulo0, uhi0, v, X);
 }
@@ -216,11 +193,10 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
   // e^{+2 pi i c/N} for the thread's points c = t + T e: e^{+2 pi i t/N} (ubase[t] = i e^{-2 pi i t/N} = (sin, cos))
   // times e^{2 pi i e/32} (compile-time)
   const cpx wb = mk(a.ubase[t_].y, a.ubase[t_].x);
-  for (int i = t_; i < P::TW2; i += P::T) ltw2[i] = a.tw2[i];
+  fill_ltw2<P>(t_, a.tw2, ltw2);
 
-  const unsigned lb = xcd_block(blockIdx.x, gridDim.x);
-  const int64_t f0 = (int64_t)lb * a.frames_per_block;
-  const int64_t f1 = f0 + a.frames_per_block < a.count ? f0 + a.frames_per_block : a.count;
+  int64_t f0, f1;
+  block_run(a.frames_per_block, a.count, f0, f1);
   if (f0 >= f1) return;
   const float *const base = a.audio + MX_AUDIO_PAD - kF0W;
   cpx xr[P::E];
@@ -298,7 +274,7 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
       Y[e] = mk(E2.x - O2.y, -(E2.y + O2.x));
     });
     cpx v[P::E];
-    f0_passes(t, wave0, Y, v, img, ltw2, w3b);
+    walk_passes<P>(t, wave0, Y, v, img, ltw2, w3b);
     __syncthreads();  // the image is free: d goes there
     // d(tau) at the thread's taus 2m, 2m+1 (m = k0 + NS3 r, r(2m) + i r(2m+1) = conj(v) / (8M)), tau <= W
     const float e0 = sq[sq_idx(kF0W)];
@@ -377,10 +353,9 @@ __global__ __launch_bounds__(FP::T) void f0_yin(const F0Args a) {
 hipError_t launch_f0(const F0Args &a0, hipStream_t s) {
   if (a0.count <= 0) return hipSuccess;
   F0Args a = a0;
-  if (a.frames_per_block <= 0) a.frames_per_block = 8;
-  const int64_t blocks = (a.count + a.frames_per_block - 1) / a.frames_per_block;
-  if (a.cands) hipLaunchKernelGGL(f0_yin<true>, dim3((unsigned)blocks), dim3(FP::T), 0, s, a);
-  else hipLaunchKernelGGL(f0_yin<false>, dim3((unsigned)blocks), dim3(FP::T), 0, s, a);
+  const dim3 grid = walk_grid(a.count, a.frames_per_block, kPlan4096Run), block(FP::T);
+  if (a.cands) hipLaunchKernelGGL(f0_yin<true>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(f0_yin<false>, grid, block, 0, s, a);
   return hipGetLastError();
 }
 

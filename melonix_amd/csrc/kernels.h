@@ -121,6 +121,22 @@ struct PvArgs {
   int64_t frame_base;        // index in the whole signal of local frame `first`
   int sample_rate;
 };
+// The launch side of every kernel that walks runs of consecutive frames (f0_yin, chroma_frames, onset_flux_kernel,
+// sib_features_kernel): `run` frames per workgroup — the caller's, or `fallback` where that is <= 0 —, doubled until the blocks
+// fit the grid's x extent; -> the grid.  No output depends on the run.
+inline dim3 walk_grid(int64_t count, int &run, int fallback) {
+  if (run <= 0) run = fallback;
+  while ((count + run - 1) / run > (1ll << 30)) run *= 2;
+  return dim3((unsigned)((count + run - 1) / run));
+}
+constexpr int kPlan4096Run = 8;  // the fallback of the Plan<4096,16> walkers (f0_yin, chroma_frames)
+// ... and of the one-wavefront walkers of the 1024-point transform: long runs where there are frames enough to fill the device
+// with them (an onset run pays `lag` frames at its head)
+inline int onset_default_run(int64_t count) {
+  const int64_t want = count / 4096;
+  return (int)(want < 1 ? 1 : want > 32 ? 32 : want);
+}
+
 hipError_t launch_pv(const PvArgs &a, hipStream_t s);
 hipError_t launch_pv_analyze(const PvArgs &a, hipStream_t s);
 hipError_t launch_pv_synthesize(const PvArgs &a, hipStream_t s);
@@ -211,7 +227,6 @@ struct OnsetArgs {
   float *flux;
   int run;  // consecutive frames per wavefront; 0: the default.  The output does not depend on it
 };
-int onset_default_run(int64_t count);
 hipError_t launch_onset_flux(const OnsetArgs &a, hipStream_t s);
 // Build-defined sibilant features (sibilant_kernels.hip; definition: include/melonix_amd.h, arithmetic: sibilant_core.h on
 // onset_core.h's transform).  Frames as OnsetArgs; out[f] the record of frame first_frame + f.  1 <= ks <= 512: checked by the caller.

@@ -1,6 +1,8 @@
 // wave_walk.h — what the kernels share that walk a run of consecutive frames on Plan<4096,16> beside stft_kernel:
-// pv_analysis, pv_synthesis (pv_*.hip) and f0_yin (f0_kernels.hip).  Pieces, not a schedule: what a kernel does between
-// its barriers stays its own.  Private to those units.
+// pv_analysis, pv_synthesis (pv_*.hip), f0_yin (f0_kernels.hip) and chroma_frames (chroma_kernels.hip).  Pieces, not a
+// schedule: what a kernel does between its barriers stays its own — but for the three passes of a transform behind a register
+// image (walk_passes), which f0_yin and chroma_frames take barrier for barrier, and the start of their walk (fill_ltw2,
+// block_run).  Their launch side is kernels.h's walk_grid.  Private to those units.
 #pragma once
 #include "stft_core.h"
 #include "stft_kernel_impl.h"  // wave_reduce_u32
@@ -56,6 +58,44 @@ __device__ __forceinline__ void root_powers7(const cpx (&b)[3], cpx *w) {
   w[4] = pk_cmul2(b[2], g1);
   w[5] = pk_cmul2(b[2], b[1]);
   w[6] = pk_cmul2(b[2], w[2]);
+}
+
+// The pass-2 twiddles into the workgroup's LDS copy, once per walk (a barrier before pass 2 reads them is the caller's)
+template <class P>
+__device__ __forceinline__ void fill_ltw2(int t, const cpx *tw2, cpx *ltw2) {
+  for (int i = t; i < P::TW2; i += P::T) ltw2[i] = tw2[i];
+}
+
+// The frames [f0, f1) of a launch of `count` that this block walks, `run` to a block through xcd_block; empty where f0 >= f1
+__device__ __forceinline__ void block_run(int run, int64_t count, int64_t &f0, int64_t &f1) {
+  const unsigned lb = xcd_block(blockIdx.x, gridDim.x);
+  f0 = (int64_t)lb * run;
+  f1 = f0 + run < count ? f0 + run : count;
+}
+
+// The three passes of stft_core.h on the register image Y (thread t's point c = t + T*e in Y[e]): on return v holds
+// the transform in pass 3's layout (v[r] = Z[t + NS3 r], v[q_index(r)] = Z[k0q + NS3 r]).  Four barriers, the first before
+// the image is written: every wave is done with its previous contents.  Leaves the image busy: the caller synchronises
+// before it writes it.  f0_yin runs it three times a frame (two forward transforms and, on the conjugate, the inverse),
+// chroma_frames once.
+template <class P>
+__device__ __forceinline__ void walk_passes(int t, bool wave0, const cpx (&Y)[P::E], cpx (&v)[P::E], cpx *img, const cpx *ltw2,
+                                            const cpx (&w3b)[3]) {
+  pass1<P>(Y, v);
+  __syncthreads();  // every wave is done with the image's previous contents
+  store_t1<P>(t, v, img);
+  __syncthreads();
+  cpx w2[P::R2 - 1];
+  load_t1_tw2<P>(t, v, img, ltw2, w2);
+  __syncthreads();
+  pass2_reg<P>(v, w2);
+  store_t2<P>(t, v, img);
+  __syncthreads();
+  load_t2<P>(t, v, img);
+  cpx w3r[P::R3 - 1];
+  root_powers7(w3b, w3r);
+  if (wave0) pass3_reg<P, true>(t, v, w3r);
+  else pass3_reg<P, false>(t, v, w3r);
 }
 
 // The real-FFT split behind pass 3 (stft_core.h PostFly, post_cplx) from post_bases' values (kept for the walk; their

@@ -1,27 +1,15 @@
 // onset_emu.cpp — the onset-strength kernel's per-lane functions (melonix_amd/csrc/onset_core.h) run lane by lane on the CPU,
-// in the walker's order: a run of consecutive frames, the head frames first, the wavefront's sum in the kernel's exchange
-// order.  tests/test_onset_host.py compares it with the binary64 definition: what the GPU adds is the device's log1pf / sqrtf.
+// in the walker's order: a run of consecutive frames, the head frames first, the transform of onset_walk_emu.h, the wavefront's
+// sum in the kernel's exchange order.  tests/test_onset_host.py compares it with the binary64 definition: what the GPU adds is
+// the device's log1pf / sqrtf.
 //   g++ -std=c++17 -O2 -ffp-contract=off -fPIC -shared onset_emu.cpp -o libonset_emu.so
-#include <cmath>
-#include <cstdint>
-#include <vector>
-
-#include "../../melonix_amd/csrc/onset_core.h"
+#include "onset_walk_emu.h"
 
 using namespace mx::onset;
 
 extern "C" void emu_onset_flux(const float *wav, long n, int hop, long first_frame, long count, int lag, int kmin, int kmax,
                                float compress, int run, float *flux) {
-  std::vector<float2> tw(1024);
-  for (int j = 0; j < 1024; ++j) {
-    const double ang = -2.0 * M_PI * (double)j / 1024.0;
-    tw[(size_t)j].x = (float)std::cos(ang);
-    tw[(size_t)j].y = (float)std::sin(ang);
-  }
-  std::vector<LaneConsts> lc(kLanes);
-  for (int l = 0; l < kLanes; ++l) lane_consts(l, tw.data(), lc[(size_t)l]);
-  auto sample = [&](long i) { return i >= 0 && i < n ? wav[i] : 0.f; };
-  std::vector<float2> img(kImage);
+  emu::Walk walk(wav, n);
   for (long f0 = 0; f0 < count; f0 += run) {
     const long f1 = f0 + run < count ? f0 + run : count;
     float prev[kMaxLag][kLanes][8] = {};
@@ -29,20 +17,8 @@ extern "C" void emu_onset_flux(const float *wav, long n, int hop, long first_fra
     for (long h = hs; h < h1; ++h) {
       float2 v[kLanes][8];
       float cur[kLanes][8];
-      for (int l = 0; l < kLanes; ++l) {
-        float2 x[8];
-        for (int r = 0; r < 8; ++r) {
-          const long i = h * hop - 512 + 128 * r + 2 * l;
-          x[r].x = sample(i);
-          x[r].y = sample(i + 1);
-        }
-        pass1(l, lc[(size_t)l], x, img.data());
-      }
-      for (int l = 0; l < kLanes; ++l) pass2(l, lc[(size_t)l], img.data(), v[l]);
-      for (int l = 0; l < kLanes; ++l) store2(l, v[l], img.data());
-      for (int l = 0; l < kLanes; ++l) pass3(l, img.data(), v[l]);
-      for (int l = 0; l < kLanes; ++l) store3(l, v[l], img.data());
-      for (int l = 0; l < kLanes; ++l) compressed(l, lc[(size_t)l], v[l], img.data(), compress, cur[l]);
+      walk.frame(h, hop, v, [](int, const float2(&)[8]) {});
+      for (int l = 0; l < kLanes; ++l) compressed(l, walk.lc[(size_t)l], v[l], walk.img.data(), compress, cur[l]);
       if (h >= h0) {
         float part[kLanes];
         for (int l = 0; l < kLanes; ++l) part[l] = lane_flux(l, cur[l], prev[lag - 1][l], kmin, kmax);

@@ -1,52 +1,27 @@
 // sibilant_emu.cpp — the sibilant-feature kernel's per-lane functions (melonix_amd/csrc/sibilant_core.h on onset_core.h's
-// transform) run lane by lane on the CPU, in the walker's order: a run of consecutive frames, the wavefront's sums in the
+// transform, onset_walk_emu.h) run lane by lane on the CPU, in the walker's order: a run of consecutive frames, the wavefront's sums in the
 // kernel's exchange order, the neighbour's sign mask where the kernel's lane exchange brings it.  And the source gain's
 // arithmetic (gain_core.h) sample by sample.  tests/test_sibilant_host.py compares both with tests/sibilant_ref.py.
 //   g++ -std=c++17 -O2 -ffp-contract=off -fPIC -shared sibilant_emu.cpp -o libsibilant_emu.so
-#include <cmath>
-#include <cstdint>
-#include <vector>
-
 #include "../../melonix_amd/csrc/gain_core.h"
 #include "../../melonix_amd/csrc/sibilant_core.h"
+#include "onset_walk_emu.h"
 
 using namespace mx::sib;
 
 extern "C" void emu_sib_features(const float *wav, long n, int hop, long first_frame, long count, int ks, int run, mx_sib_feat *out) {
-  std::vector<float2> tw(1024);
-  for (int j = 0; j < 1024; ++j) {
-    const double ang = -2.0 * M_PI * (double)j / 1024.0;
-    tw[(size_t)j].x = (float)std::cos(ang);
-    tw[(size_t)j].y = (float)std::sin(ang);
-  }
-  std::vector<LaneConsts> lc(kLanes);
-  for (int l = 0; l < kLanes; ++l) lane_consts(l, tw.data(), lc[(size_t)l]);
-  auto sample = [&](long i) { return i >= 0 && i < n ? wav[i] : 0.f; };
-  std::vector<float2> img(kImage);
+  emu::Walk walk(wav, n);
   for (long f0 = 0; f0 < count; f0 += run) {
     const long f1 = f0 + run < count ? f0 + run : count;
     for (long h = first_frame + f0; h < first_frame + f1; ++h) {
       float2 v[kLanes][8];
       uint32_t first[kLanes], second[kLanes];
-      for (int l = 0; l < kLanes; ++l) {
-        float2 x[8];
-        for (int r = 0; r < 8; ++r) {
-          const long i = h * hop - 512 + 128 * r + 2 * l;
-          x[r].x = sample(i);
-          x[r].y = sample(i + 1);
-        }
-        sign_masks(x, first[l], second[l]);
-        pass1(l, lc[(size_t)l], x, img.data());
-      }
-      for (int l = 0; l < kLanes; ++l) pass2(l, lc[(size_t)l], img.data(), v[l]);
-      for (int l = 0; l < kLanes; ++l) store2(l, v[l], img.data());
-      for (int l = 0; l < kLanes; ++l) pass3(l, img.data(), v[l]);
-      for (int l = 0; l < kLanes; ++l) store3(l, v[l], img.data());
+      walk.frame(h, hop, v, [&](int l, const float2(&x)[8]) { sign_masks(x, first[l], second[l]); });  // (of the raw samples)
       float low[kLanes], high[kLanes], moment[kLanes];
       int zc = 0;  // (an integer sum: any order)
       for (int l = 0; l < kLanes; ++l) {
         float P[8];
-        powers(l, lc[(size_t)l], v[l], img.data(), P);
+        powers(l, walk.lc[(size_t)l], v[l], walk.img.data(), P);
         const LaneSums s = lane_sums(l, P, ks);
         low[l] = s.low, high[l] = s.high, moment[l] = s.moment;
         zc += lane_crossings(l, first[l], second[l], first[(l + 1) & (kLanes - 1)]);

@@ -4,20 +4,16 @@ tests/contour_ref.py — stage B byte for byte, stage A by the tie rule —, the
 curve against the same reference field for field, the refusals, the chain on a synthetic contour, the kernels' resources."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import contour_ref as R
+import emu_build
 import psola_formant_ref
 import psola_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "melonix_amd", "csrc")
-EMU_SOURCES = [os.path.join(ROOT, "tests", "emu", "contour_emu.cpp"), os.path.join(CSRC, "contour_logic.cpp")]
-EMU_FLAGS = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall"]
+EMU_SOURCES = ["contour_emu.cpp", "contour_logic.cpp"]
 SR, HOP = 48000, 256
 INVALID = -1
 
@@ -60,11 +56,7 @@ class Emu:
 
 @pytest.fixture(scope="module")
 def contour_emu():
-    so = os.path.join(ROOT, "tests", "emu", "libcontour_emu.so")
-    deps = EMU_SOURCES + [os.path.join(CSRC, f) for f in ("contour_core.h", "contour_logic.h")] + [os.path.join(ROOT, "include", "melonix_amd.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(EMU_FLAGS + ["-fPIC", "-shared"] + EMU_SOURCES + ["-o", so])
-    return Emu(so)
+    return Emu(emu_build.shared_object("contour_emu", EMU_SOURCES, ["contour_core.h", "contour_logic.h"]))
 
 
 # ---- stage B: the emulation equals the reference exactly ----
@@ -414,20 +406,12 @@ def test_chain_on_a_synthetic_contour(mxlib, contour_emu):
 
 
 def test_emulation_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "contour_emu_san")
-    subprocess.check_call(EMU_FLAGS + ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                       "-DCONTOUR_EMU_MAIN"] + EMU_SOURCES + ["-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "contour_emu ok" in out.stdout, out.stderr[-3000:]
+    out = emu_build.run_sanitized(tmp_path, "contour_emu_san", EMU_SOURCES, "CONTOUR_EMU_MAIN")
+    assert "contour_emu ok" in out, out
 
 
 def test_kernels_use_no_scratch_and_little_lds(mxlib):
-    from melonix_amd import build
-    out = subprocess.run(build.unit_command("contour_kernels.hip") + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    text = out.stderr
-    assert text.count("Function Name") == 4
-    assert text.count("ScratchSize [bytes/lane]: 0") == 4
-    lds = [int(line.rsplit(":", 1)[1].split()[0]) for line in text.splitlines() if "LDS Size" in line]
+    names, scratch, _, lds = emu_build.resource_usage("contour_kernels.hip")
+    assert len(names) == 4
+    assert scratch == [0] * 4
     assert max(lds) <= 8192, lds

@@ -7,7 +7,7 @@ import pytest
 
 import f0_decode_ref as D
 import yin_ref as Y
-from test_abi import _resource_usage
+from emu_build import resource_usage
 
 CHUNKS = (1, 2, 7, 16, 64)
 
@@ -95,10 +95,10 @@ def test_decode_parameter_checks_need_no_device(mxlib):
 
 def test_f0_kernels_do_not_spill():
     """Both f0_yin instantiations and the five decode kernels are scratch-free."""
-    names, scratch, vgprs = _resource_usage("f0_kernels.hip")
+    names, scratch, vgprs, _ = resource_usage("f0_kernels.hip")
     assert sum("f0_yinILb0" in n for n in names) == 1 and sum("f0_yinILb1" in n for n in names) == 1, names
     assert not [(n, s) for n, s in zip(names, scratch) if s != 0] and max(vgprs) <= 256
-    names, scratch, vgprs = _resource_usage("f0_decode.hip")
+    names, scratch, vgprs, _ = resource_usage("f0_decode.hip")
     for k in ("f0_dec_products", "f0_dec_starts", "f0_dec_walk", "f0_dec_ends", "f0_dec_path"):
         assert any(k in n for n in names), (k, names)
     assert not [(n, s) for n, s in zip(names, scratch) if s != 0] and max(vgprs) <= 256

@@ -5,22 +5,16 @@ mx_key_from_notes and mx_correction_markers_tuned of the library against the ref
 kernels' resources; the reference alone against the truth of the synthetic takes."""
 import ctypes as C
 import math
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bad_samples as B
+import emu_build
 import key_ref as K
 import yin_ref as Y
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "melonix_amd", "csrc")
 SR = K.SR
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "chroma_emu.cpp")
-EMU_FLAGS = ["g++", "-std=c++17", "-O2", "-ffp-contract=off"]
 TAKES = ["c_major", "a_minor", "c_major_446", "c_major_flat_vibrato"]
 KEY_FIELDS = ("tonic", "mode", "scale_mask", "tuning_cents", "tuning_confidence", "correlation", "clarity")
 # Share of a take's frames that the guard may leave out of the parity check (a condition on the reference alone): frames that
@@ -80,11 +74,8 @@ def cases():
 
 @pytest.fixture(scope="module")
 def emu(mxlib):
-    so = os.path.join(ROOT, "tests", "emu", "libchroma_emu.so")
-    deps = [EMU_SRC, os.path.join(ROOT, "include", "melonix_amd.h")] + [os.path.join(CSRC, f) for f in ("chroma_core.h", "stft_core.h", "pk_math.h", "stft_tables.h", "stft_consts.inc")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(EMU_FLAGS + ["-fPIC", "-shared", EMU_SRC, "-o", so])
-    L = C.CDLL(so)
+    L = C.CDLL(emu_build.shared_object("chroma_emu", ["chroma_emu.cpp"],
+                                       ["chroma_core.h", "stft_core.h", "pk_math.h", "stft_tables.h", "stft_consts.inc"]))
     L.emu_chroma.restype = C.c_long
     L.emu_chroma.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                              C.c_void_p]
@@ -349,27 +340,17 @@ def test_refusals(mxlib):
 def test_the_stand_alone_program_under_the_sanitizers(tmp_path):
     """The emulation and the library's host logic with a main of their own over the smallest shapes, the longest peak list and
     the edges of every list, under AddressSanitizer and UBSan."""
-    exe = str(tmp_path / "chroma_emu_san")
-    flags = [f for f in EMU_FLAGS if f != "-O2"] + ["-O1"]  # (the transform's templates at -O2 -g under ASan compile for a minute)
-    subprocess.check_call(flags + ["-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                   "-DCHROMA_EMU_MAIN", EMU_SRC, os.path.join(CSRC, "key_logic.cpp"), os.path.join(CSRC, "f0_notes.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "chroma_emu ok" in out.stdout, out.stdout + out.stderr[-3000:]
+    out = emu_build.run_sanitized(tmp_path, "chroma_emu_san", ["chroma_emu.cpp", "key_logic.cpp", "f0_notes.cpp"], "CHROMA_EMU_MAIN",
+                                  opt=("-O1",))  # (the transform's templates at -O2 -g under ASan compile for a minute)
+    assert "chroma_emu ok" in out, out
 
 
 def test_chroma_kernels_do_not_spill():
     """Both kernels scratch-free inside 256 VGPRs; the frame kernel's LDS is the FFT image, the pass-2 twiddles, the padded
     magnitude image and four words."""
-    from melonix_amd import build
-
-    out = subprocess.run(build.unit_command("chroma_kernels.hip") + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
-    lds = dict(zip(names, (int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out.stderr))))
-    assert len(names) == len(scratch) == len(vgprs) == 2
+    names, scratch, vgprs, lds = emu_build.resource_usage("chroma_kernels.hip")
+    lds = dict(zip(names, lds))
+    assert len(names) == 2
     assert scratch == [0, 0] and max(vgprs) <= 256, (scratch, vgprs)
     frames = next(n for n in names if "chroma_frames" in n)
     assert lds[frames] == 16384 + 8 * 240 + 4 * (2048 + 128) + 16 and lds[next(n for n in names if "chroma_sum" in n)] == 0

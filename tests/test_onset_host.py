@@ -3,16 +3,14 @@ and mx_timing_markers against tests/onset_ref.py field for field, the properties
 refusals — and the kernel's per-lane arithmetic (csrc/onset_core.h) run lane by lane on the CPU against the binary64
 definition.  No GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bad_samples as B
+import emu_build
 import onset_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SR = R.SR
 
 
@@ -221,12 +219,7 @@ def test_refusals(mxlib):
 @pytest.fixture(scope="module")
 def onset_emu():
     """tests/emu/onset_emu.cpp: the kernel's per-lane functions run lane by lane, in the walker's order."""
-    src = os.path.join(ROOT, "tests", "emu", "onset_emu.cpp")
-    so = os.path.join(ROOT, "tests", "emu", "libonset_emu.so")
-    deps = [src, os.path.join(ROOT, "melonix_amd", "csrc", "onset_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", src, "-o", so])
-    L = C.CDLL(so)
+    L = C.CDLL(emu_build.shared_object("onset_emu", ["onset_emu.cpp"], ["onset_walk_emu.h", "onset_core.h"]))
     fp = C.POINTER(C.c_float)
     L.emu_onset_flux.argtypes = [fp, C.c_long, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, fp]
 
@@ -340,16 +333,6 @@ def chain_survivors(clean, bad, n, what, lag=1):
 def test_onset_kernels_do_not_spill():
     """Every instantiation (lag 1 to 4) keeps its rows, twiddles and window in registers: scratch-free, inside 256 VGPRs, and the
     4.5 KiB transposition image is all the LDS it takes."""
-    import re
-
-    from melonix_amd import build
-
-    out = subprocess.run(build.unit_command("onset_kernels.hip") + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out.stderr)]
-    assert len(names) == len(scratch) == len(vgprs) == len(lds) == 4 and all("onset_flux_kernel" in n for n in names)
+    names, scratch, vgprs, lds = emu_build.resource_usage("onset_kernels.hip")
+    assert len(names) == 4 and all("onset_flux_kernel" in n for n in names)
     assert scratch == [0] * 4 and max(vgprs) <= 256 and lds == [4608] * 4

@@ -4,22 +4,16 @@ balance"): the feature kernel's per-lane arithmetic (csrc/sibilant_core.h on ons
 mx_formant_protect and mx_sibilant_gain_points of the library against the reference field for field; the refusals; the
 kernels' resources; the reference alone against the truth of the synthetic take."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bad_samples as B
+import emu_build
 import onset_ref as R
 import sibilant_ref as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "melonix_amd", "csrc")
 SR, HOP = S.SR, S.HOP
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "sibilant_emu.cpp")
-EMU_FLAGS = ["g++", "-std=c++17", "-O2", "-ffp-contract=off"]
 FLOAT_FIELDS = ("low", "high", "centroid")
 
 
@@ -56,11 +50,8 @@ def takes():
 
 @pytest.fixture(scope="module")
 def emu(mxlib):
-    so = os.path.join(ROOT, "tests", "emu", "libsibilant_emu.so")
-    deps = [EMU_SRC, os.path.join(ROOT, "include", "melonix_amd.h")] + [os.path.join(CSRC, f) for f in ("onset_core.h", "sibilant_core.h", "gain_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(EMU_FLAGS + ["-fPIC", "-shared", EMU_SRC, "-o", so])
-    L = C.CDLL(so)
+    L = C.CDLL(emu_build.shared_object("sibilant_emu", ["sibilant_emu.cpp"],
+                                       ["onset_walk_emu.h", "onset_core.h", "sibilant_core.h", "gain_core.h"]))
     L.emu_sib_features.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.emu_audio_gain.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
 
@@ -402,28 +393,17 @@ def test_refusals(mxlib):
 def test_the_stand_alone_program_under_the_sanitizers(tmp_path):
     """The emulation and the library's host logic with a main of their own over the smallest shapes and the edges of every
     list, under AddressSanitizer and UBSan."""
-    exe = str(tmp_path / "sibilant_emu_san")
-    subprocess.check_call(EMU_FLAGS + ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                       "-DSIBILANT_EMU_MAIN", EMU_SRC, os.path.join(CSRC, "sibilant_logic.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "sibilant_emu ok" in out.stdout, out.stdout + out.stderr[-3000:]
+    out = emu_build.run_sanitized(tmp_path, "sibilant_emu_san", ["sibilant_emu.cpp", "sibilant_logic.cpp"], "SIBILANT_EMU_MAIN")
+    assert "sibilant_emu ok" in out, out
 
 
 def test_sibilant_and_gain_kernels_do_not_spill():
     """Both kernels scratch-free inside 256 VGPRs; the feature kernel's LDS is the 4.5 KiB transposition image and nothing else,
     the gain kernel's the tile's first segment."""
-    from melonix_amd import build
-
     seen = {}
     for unit in ("sibilant_kernels.hip", "gain_kernels.hip"):
-        out = subprocess.run(build.unit_command(unit) + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                             capture_output=True, text=True)
-        assert out.returncode == 0, out.stderr[-2000:]
-        names = re.findall(r"Function Name: (\S+)", out.stderr)
-        scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-        vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
-        lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out.stderr)]
-        assert len(names) == len(scratch) == len(vgprs) == len(lds) == 1, unit
+        names, scratch, vgprs, lds = emu_build.resource_usage(unit)
+        assert len(names) == 1, unit
         assert scratch == [0] and vgprs[0] <= 256, (unit, scratch, vgprs)
         seen[unit] = (names[0], lds[0])
     assert "sib_features_kernel" in seen["sibilant_kernels.hip"][0] and seen["sibilant_kernels.hip"][1] == 4608

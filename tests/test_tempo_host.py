@@ -3,20 +3,16 @@
 tests/tempo_ref.py byte for byte; the reference alone against the truth of the synthetic takes; the refusals; the kernels'
 resources."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import onset_ref as R
 import tempo_ref as T
 from tempo_ref import same_estimate
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "melonix_amd", "csrc")
-EMU_SOURCES = [os.path.join(ROOT, "tests", "emu", "tempo_emu.cpp"), os.path.join(CSRC, "tempo_logic.cpp")]
-EMU_FLAGS = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall"]
+EMU_SOURCES = ["tempo_emu.cpp", "tempo_logic.cpp"]
 
 
 class Emu:
@@ -63,11 +59,7 @@ class Emu:
 
 @pytest.fixture(scope="module")
 def tempo_emu():
-    so = os.path.join(ROOT, "tests", "emu", "libtempo_emu.so")
-    deps = EMU_SOURCES + [os.path.join(CSRC, f) for f in ("tempo_core.h", "tempo_logic.h")] + [os.path.join(ROOT, "include", "melonix_amd.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(EMU_FLAGS + ["-fPIC", "-shared"] + EMU_SOURCES + ["-o", so])
-    return Emu(so)
+    return Emu(emu_build.shared_object("tempo_emu", EMU_SOURCES, ["tempo_core.h", "tempo_logic.h"]))
 
 
 def test_smoothing_equals_the_reference(tempo_emu):
@@ -142,11 +134,8 @@ def test_estimate_with_many_windows_a_first_frame_and_other_rates(tempo_emu):
 
 def test_the_stand_alone_program_under_the_sanitizers(tmp_path):
     """The same sources with a main of their own over the smallest shapes, under AddressSanitizer and UBSan."""
-    exe = str(tmp_path / "tempo_emu_san")
-    subprocess.check_call(EMU_FLAGS + ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                       "-DTEMPO_EMU_MAIN"] + EMU_SOURCES + ["-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "tempo_emu ok" in out.stdout, out.stderr[-3000:]
+    out = emu_build.run_sanitized(tmp_path, "tempo_emu_san", EMU_SOURCES, "TEMPO_EMU_MAIN")
+    assert "tempo_emu ok" in out, out
 
 
 @pytest.mark.parametrize("name", list(T.TAKES))
@@ -243,19 +232,10 @@ def test_refusals(tempo_emu, mxlib):
 
 def test_tempo_kernels_do_not_spill():
     """Both kernels are scratch-free and inside 256 VGPRs; the comb's LDS is its row of 4096 scores and the four waves' pairs."""
-    import re
-
-    from melonix_amd import build
-
-    out = subprocess.run(build.unit_command("tempo_kernels.hip") + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", out.stderr)]
-    lds = dict(zip(names, (int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out.stderr))))
+    names, scratch, vgprs, lds = emu_build.resource_usage("tempo_kernels.hip")
+    lds = dict(zip(names, lds))
     print(list(zip(names, scratch, vgprs)), lds)
-    assert len(names) == len(scratch) == len(vgprs) == 2
+    assert len(names) == 2
     assert any("tempo_smooth_kernel" in n for n in names) and any("tempo_comb_kernel" in n for n in names)
     assert scratch == [0, 0] and max(vgprs) <= 256
     assert [v for n, v in lds.items() if "tempo_comb_kernel" in n] == [4096 * 4 + 32]

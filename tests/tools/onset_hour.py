@@ -3,7 +3,8 @@
 audio (172.8 M samples, 675 000 frames at hop 256) of tests/onset_ref.py's six-note take, tiled:
   kernel  between HIP events on the null stream, the median (min, max) of 10 launches after 3: mx_onset_flux_dev and
           mx_f0_track_dev on the same frames, ALTERNATING in one process, and their ratio.  The tracker's launch does three
-          4096-point transforms per frame and is the yardstick: the flux launch should not take longer.
+          4096-point transforms per frame and is the yardstick: the flux launch should not take longer.  Then
+          mx_sib_features_dev and mx_chroma_dev, the other two frame walkers, on the same frames with default parameters.
   runs    the same launch at other run lengths (frames per wavefront; the default is onset_default_run's), each row again
           alternating with the default; the values are asserted byte-equal across the run lengths.
   host    mx_onset_flux, the host form with its download, on the host clock: the median of 5 calls after one.
@@ -38,12 +39,14 @@ class Lib(TimedLib):
         super().__init__(path, d_img, n)
         so = self.so
         so.mx_onset_flux_dev.argtypes = so.mx_onset_flux.argtypes = [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp]
+        so.mx_sib_features_dev.argtypes = so.mx_chroma_dev.argtypes = so.mx_onset_flux_dev.argtypes
         so.mx_f0_track_dev.argtypes = [_vp, _vp, _i, _i, _i64, _i64, _f, _f, _f, _vp]
         so.mx_ctx_set_frames_per_block.argtypes = [_vp, _i]
         so.mx_ctx_destroy.argtypes = [_vp]
         so.mx_audio_free.argtypes = [_vp, _vp]
         self.frames = -(-n // HOP)
         self.flux, self.f0 = DevBuf(self.frames * 4), DevBuf(self.frames * 16)
+        self.sib, self.chroma = DevBuf(self.frames * 16), DevBuf(self.frames * 160)
         self.host_flux, self.host_ms = np.empty(self.frames, dtype=np.float32), []
 
     def onset(self, run=0):
@@ -60,9 +63,15 @@ class Lib(TimedLib):
     def track(self):
         assert self.so.mx_f0_track_dev(self.ctx, self.audio, SR, HOP, 0, self.frames, 55.0, 1760.0, 0.15, _vp(self.f0.ptr)) == 0
 
+    def sibilant(self):
+        assert self.so.mx_sib_features_dev(self.ctx, self.audio, SR, HOP, 0, self.frames, None, _vp(self.sib.ptr)) == 0
+
+    def chroma_records(self):
+        assert self.so.mx_chroma_dev(self.ctx, self.audio, SR, HOP, 0, self.frames, None, _vp(self.chroma.ptr)) == 0
+
     def close(self):
-        self.flux.free()
-        self.f0.free()
+        for buf in (self.flux, self.f0, self.sib, self.chroma):
+            buf.free()
         self.so.mx_audio_free(self.ctx, self.audio)
         self.so.mx_ctx_destroy(self.ctx)
 
@@ -92,7 +101,8 @@ def main():
 
     rows = {}
     timed({**row("onset", "onset"), **row("f0", "track")})
-    flux = np.frombuffer(same_bytes(libs, "flux", "f0")[0], dtype=np.float32)
+    timed({**row("sibilant", "sibilant"), **row("chroma", "chroma_records")})
+    flux = np.frombuffer(same_bytes(libs, "flux", "f0", "sib", "chroma")[0], dtype=np.float32)
     for run in [int(r) for r in args.runs.split(",") if r]:
         timed({**row(f"run_{run}_default", "onset"), **row(f"run_{run}", "onset", run)})
         assert same_bytes(libs, "flux")[0] == flux.tobytes(), run  # (the last launch of the row is the run's)
