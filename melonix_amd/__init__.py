@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from ._capi import records as _records  # tuples, or an array of the dtype -> a contiguous array of the dtype
 from ._capi import (F0_CAND_DTYPE, F0_DTYPE, FORMANT_POINT_DTYPE, MARKER_DTYPE, MX_AUDIO_PAD, NOTE_DTYPE, ONSET_DTYPE, PITCH_DTYPE,  # noqa: F401
                     PSOLA_FGRAIN_DTYPE, PSOLA_GRAIN_DTYPE, STEP_DTYPE, MxError)
 from ._capi import COMB_DTYPE, COMB_JOB_DTYPE, TEMPO_WINDOW_DTYPE  # noqa: F401
@@ -36,8 +37,34 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "bend_params_default", "contour_spans", "contour_vibrato", "contour_bend", "psola_plan_bend", "psola_plan_formant_bend"]
 
 
+# The two pointer forms of an optional argument.  New wrappers use these: _opt for a host array, _dev for a device address.
+def _opt(a):
+    """A host array's pointer; NULL when it is None or empty."""
+    return None if a is None or not len(a) else C.c_void_p(a.ctypes.data)
+
+
+def _dev(p):
+    """A device address (an integer, e.g. a torch tensor's data_ptr()); NULL when it is None or 0."""
+    return C.c_void_p(p or 0)
+
+
 def _ptr(a):
+    """An array's own pointer, even where it is empty; NULL for None only.  Kept where the library's argument checks have
+    always seen it (stft ranges, resynth steps, f0_decode, upload, whole-output buffers): not for new code."""
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget")  # they return a count, or a negative status
+
+
+def _call(name: str, *args):
+    """The entry point `name` with args, its status checked (MxError); the count of the two entry points that return one."""
+    rc = getattr(_capi.lib(), name)(*args)
+    if name in _COUNT_CALLS:
+        if rc < 0:
+            _capi.check(int(rc))
+        return int(rc)
+    _capi.check(rc)
 
 
 def _pcm_pair(n: int, want_f32: bool, want_i16: bool):
@@ -45,19 +72,22 @@ def _pcm_pair(n: int, want_f32: bool, want_i16: bool):
     return np.empty(n, dtype=np.float32) if want_f32 else None, np.empty(n, dtype=np.int16) if want_i16 else None
 
 
-def _render_length(n: int, sr: int, m, nmarkers: int) -> int:
-    """Samples a marker-driven render of n samples writes (the warped duration)."""
-    cnt = _capi.lib().mx_pv_render_length(n, sr, m, nmarkers)
-    if cnt < 0:
-        _capi.check(int(cnt))
-    return cnt
-
-
 def _take_records(p, count: int, dtype):
     """A library-allocated array of `count` records as a numpy array of its own; the allocation goes back (mx_free)."""
     out = np.frombuffer(C.string_at(p, count * dtype.itemsize), dtype=dtype).copy()
     _capi.lib().mx_free(p)
     return out
+
+
+def _handed(dtype, name: str, *args, tail=()):
+    """name(*args, &records, &count, *tail), where the library allocates the records -> them as a numpy array of `dtype`."""
+    out, cnt = C.c_void_p(), C.c_int64()
+    _call(name, *args, C.byref(out), C.byref(cnt), *tail)
+    return _take_records(out, cnt.value, dtype)
+
+
+def _fields(p) -> dict:
+    return {k: getattr(p, k) for k, _ in p._fields_}
 
 
 # the parameter blocks of the build-defined entry points: kind -> (its ctypes struct, the entry point that writes its defaults)
@@ -74,7 +104,7 @@ def _params_default(kind: str) -> dict:
     struct, fn = _PARAMS[kind]
     p = struct()
     getattr(_capi.lib(), fn)(C.byref(p))
-    return {k: getattr(p, k) for k, _ in struct._fields_}
+    return _fields(p)
 
 
 def _params_arg(kind: str, params: dict, never_null: bool = False):
@@ -91,55 +121,27 @@ def _params_arg(kind: str, params: dict, never_null: bool = False):
     return C.byref(struct(**{k: (float if t in (C.c_float, C.c_double) else int)(d[k]) for k, t in struct._fields_}))
 
 
-def f0_decode_params_default() -> dict:
-    return _params_default("decode")
+def _default_fn(kind: str):
+    def fn() -> dict:
+        return _params_default(kind)
+    fn.__name__ = fn.__qualname__ = _PARAMS[kind][1][3:]  # the entry point's name without "mx_"
+    fn.__doc__ = f"The {kind} parameters as {_PARAMS[kind][1]} writes them."
+    return fn
 
 
-def note_params_default() -> dict:
-    return _params_default("note")
-
-
-def psola_params_default() -> dict:
-    return _params_default("psola")
-
-
-def onset_flux_params_default() -> dict:
-    return _params_default("flux")
-
-
-def onset_pick_params_default() -> dict:
-    return _params_default("pick")
-
-
-def timing_params_default() -> dict:
-    return _params_default("timing")
-
-
-def tempo_params_default() -> dict:
-    return _params_default("tempo")
-
-
-def sib_feature_params_default() -> dict:
-    return _params_default("sib_feature")
-
-
-def sibilant_params_default() -> dict:
-    return _params_default("sibilant")
-
-
-def chroma_params_default() -> dict:
-    return _params_default("chroma")
-
-
-def bend_params_default() -> dict:
-    return _params_default("bend")
+# one per kind of _PARAMS, each under its entry point's name (the check: not under a neighbour's, whatever _PARAMS' order becomes)
+_DEFAULT_FNS = tuple(map(_default_fn, _PARAMS))
+(f0_decode_params_default, note_params_default, psola_params_default, onset_flux_params_default, onset_pick_params_default,
+ timing_params_default, tempo_params_default, sib_feature_params_default, sibilant_params_default, chroma_params_default,
+ bend_params_default) = _DEFAULT_FNS
+assert all(globals()[fn.__name__] is fn for fn in _DEFAULT_FNS)
 
 
 def contour_params_default(sr: int, hop: int) -> dict:
     """The split's parameters at sr / hop frames per second: a 250 ms window, lags of 3 .. 12 Hz."""
     p = _capi.ContourParams()
-    _capi.check(_capi.lib().mx_contour_params_default(sr, hop, C.byref(p)))
-    return {k: getattr(p, k) for k, _ in _capi.ContourParams._fields_}
+    _call("mx_contour_params_default", sr, hop, C.byref(p))
+    return _fields(p)
 
 
 def _contour_params(params: dict):
@@ -167,9 +169,7 @@ def pv_plan(n: int, sr: int, markers):
     m = _capi.markers_array(markers)
     pa, pt, pr, pi = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
     F, cnt = C.c_int64(), C.c_int64()
-    L = _capi.lib()
-    _capi.check(L.mx_pv_plan(n, sr, m, len(markers), C.byref(pa), C.byref(pt), C.byref(pr), C.byref(pi),
-                             C.byref(F), C.byref(cnt)))
+    _call("mx_pv_plan", n, sr, m, len(markers), C.byref(pa), C.byref(pt), C.byref(pr), C.byref(pi), C.byref(F), C.byref(cnt))
     f = F.value
     out = (cnt.value,
            np.frombuffer(C.string_at(pa, f * 8), dtype=np.int64).copy(),
@@ -177,24 +177,19 @@ def pv_plan(n: int, sr: int, markers):
            np.frombuffer(C.string_at(pr, f * 8), dtype=np.float64).copy(),
            np.frombuffer(C.string_at(pi, (f + 1) * 8), dtype=np.int64).copy())
     for q in (pa, pt, pr, pi):
-        L.mx_free(q)
+        _capi.lib().mx_free(q)
     return out
 
 
 def pv_shard_frames(n: int, semitones: float, rank: int, world: int):
     """-> (frame_lo, frame_hi, out_lo, out_hi) of one rank of a multi-GPU phase-vocoder run."""
     v = [C.c_int64() for _ in range(4)]
-    _capi.check(_capi.lib().mx_pv_shard_frames(n, float(semitones), rank, world, *[C.byref(x) for x in v]))
+    _call("mx_pv_shard_frames", n, float(semitones), rank, world, *[C.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 
 def frame_count(n: int, hop: int) -> int:
     return _capi.lib().mx_frame_count(n, hop)
-
-
-def _frames_from(audio, hop: int, first: int, count: int | None) -> int:
-    """count, or (None) the frames from `first` to the end of the file."""
-    return frame_count(audio.n, hop) - first if count is None else count
 
 
 # the f0 wrappers' default band (Hz) and threshold
@@ -229,12 +224,12 @@ class KeptRows:
 
     def fetch(self, first: int, count: int):
         out = np.empty((count, self.N // 2), dtype=np.float32)
-        _capi.check(_capi.lib().mx_rows_fetch(self.ctx.handle, self.handle, first, count, _ptr(out)))
+        _call("mx_rows_fetch", self.ctx.handle, self.handle, first, count, _ptr(out))
         return out
 
     def colormap(self, first: int, count: int, k: float):
         out = np.empty((count, self.N // 2, 3), dtype=np.uint8)
-        _capi.check(_capi.lib().mx_rows_colormap(self.ctx.handle, self.handle, first, count, float(k), _ptr(out)))
+        _call("mx_rows_colormap", self.ctx.handle, self.handle, first, count, float(k), _ptr(out))
         return out
 
     def free(self):
@@ -261,7 +256,7 @@ class Context:
 
     def __init__(self, device: int = 0):
         h = C.c_void_p()
-        _capi.check(_capi.lib().mx_ctx_create(device, C.byref(h)))
+        _call("mx_ctx_create", device, C.byref(h))
         self.handle = h
         self.device = device
 
@@ -278,42 +273,50 @@ class Context:
 
     def set_stream(self, hip_stream: int | None):
         """Launch on this hipStream_t (0/None = the HIP null stream, torch's default stream)."""
-        _capi.check(_capi.lib().mx_ctx_set_stream(self.handle, C.c_void_p(hip_stream or 0)))
+        _call("mx_ctx_set_stream", self.handle, _dev(hip_stream))
 
     def use_own_stream(self):
-        _capi.check(_capi.lib().mx_ctx_use_own_stream(self.handle))
+        _call("mx_ctx_use_own_stream", self.handle)
 
     def release_scratch(self):
         """Give back the work buffers the context keeps between calls (staging, phase-vocoder arena)."""
-        _capi.check(_capi.lib().mx_ctx_release_scratch(self.handle))
+        _call("mx_ctx_release_scratch", self.handle)
 
     def set_frames_per_block(self, g: int):
-        _capi.check(_capi.lib().mx_ctx_set_frames_per_block(self.handle, g))
+        _call("mx_ctx_set_frames_per_block", self.handle, g)
 
     def synchronize(self):
-        _capi.check(_capi.lib().mx_ctx_synchronize(self.handle))
+        _call("mx_ctx_synchronize", self.handle)
 
     # ---- audio ----
+    def _audio(self, n: int, name: str, *args, keepalive=None) -> Audio:
+        """name(ctx, *args, &handle) -> the new Audio of n samples."""
+        h = C.c_void_p()
+        _call(name, self.handle, *args, C.byref(h))
+        return Audio(self, h, n, keepalive)
+
     def upload(self, wav) -> Audio:
         wav = np.ascontiguousarray(wav, dtype=np.float32)
-        h = C.c_void_p()
-        _capi.check(_capi.lib().mx_audio_upload(self.handle, _ptr(wav), len(wav), C.byref(h)))
-        return Audio(self, h, len(wav))
+        return self._audio(len(wav), "mx_audio_upload", _ptr(wav), len(wav))
 
     def wrap_device(self, d_padded_ptr: int, n: int, keepalive=None) -> Audio:
-        h = C.c_void_p()
-        _capi.check(_capi.lib().mx_audio_wrap_device(self.handle, C.c_void_p(d_padded_ptr), n, C.byref(h)))
-        return Audio(self, h, n, keepalive)
+        return self._audio(n, "mx_audio_wrap_device", C.c_void_p(d_padded_ptr), n, keepalive=keepalive)
+
+    # ---- the host form of a per-frame track ----
+    def _frame_tracks(self, name: str, audio: Audio, x: int, hop: int, first: int, count: int | None, mid, *outs):
+        """name(ctx, audio, x, hop, first, count, *mid, *outputs) -> the tuple of outputs.  count None: the frames from `first`
+        to the end of the file; each of `outs` is (dtype, *trailing shape) of one output of max(count, 0) records, or None
+        for one not wanted (NULL)."""
+        count = frame_count(audio.n, hop) - first if count is None else count
+        arrays = tuple(None if o is None else np.empty((max(count, 0), *o[1:]), dtype=o[0]) for o in outs)
+        _call(name, self.handle, audio.handle, x, hop, first, count, *mid, *map(_ptr, arrays))
+        return arrays
 
     # ---- STFT, host outputs ----
     def stft_hop(self, audio: Audio, N: int, hop: int, first: int = 0, count: int | None = None, band=(-1, -1),
                  want_mags: bool = True, want_pitch: bool = True):
-        count = _frames_from(audio, hop, first, count)
-        mags = np.empty((count, N // 2), dtype=np.float32) if want_mags else None
-        pitch = np.empty(count, dtype=PITCH_DTYPE) if want_pitch else None
-        _capi.check(_capi.lib().mx_stft_hop(self.handle, audio.handle, N, hop, first, count, band[0], band[1],
-                                            _ptr(mags), _ptr(pitch)))
-        return mags, pitch
+        return self._frame_tracks("mx_stft_hop", audio, N, hop, first, count, (band[0], band[1]),
+                                  (np.float32, N // 2) if want_mags else None, (PITCH_DTYPE,) if want_pitch else None)
 
     def stft_ranges(self, audio: Audio, N: int, ranges, band=(-1, -1), want_mags: bool = True,
                     want_pitch: bool = True):
@@ -321,8 +324,7 @@ class Context:
         count = len(ranges)
         mags = np.empty((count, N // 2), dtype=np.float32) if want_mags else None
         pitch = np.empty(count, dtype=PITCH_DTYPE) if want_pitch else None
-        _capi.check(_capi.lib().mx_stft_ranges(self.handle, audio.handle, N, _ptr(ranges), count, band[0], band[1],
-                                               _ptr(mags), _ptr(pitch)))
+        _call("mx_stft_ranges", self.handle, audio.handle, N, _ptr(ranges), count, band[0], band[1], _ptr(mags), _ptr(pitch))
         return mags, pitch
 
     def stft_ranges_rgb(self, audio: Audio, N: int, ranges, k: float, want_mags: bool = False):
@@ -331,12 +333,10 @@ class Context:
         ranges = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 2)
         rgb = np.empty((len(ranges), N // 2, 3), dtype=np.uint8)
         if not want_mags:
-            _capi.check(_capi.lib().mx_stft_ranges_rgb(self.handle, audio.handle, N, _ptr(ranges), len(ranges),
-                                                       float(k), _ptr(rgb)))
+            _call("mx_stft_ranges_rgb", self.handle, audio.handle, N, _ptr(ranges), len(ranges), float(k), _ptr(rgb))
             return rgb
         mags = np.empty((len(ranges), N // 2), dtype=np.float32)
-        _capi.check(_capi.lib().mx_stft_ranges_rgb_mags(self.handle, audio.handle, N, _ptr(ranges), len(ranges),
-                                                        float(k), _ptr(mags), _ptr(rgb)))
+        _call("mx_stft_ranges_rgb_mags", self.handle, audio.handle, N, _ptr(ranges), len(ranges), float(k), _ptr(mags), _ptr(rgb))
         return rgb, mags
 
     def stft_ranges_keep(self, audio: Audio, N: int, ranges, k: float = 0.0, want_mags: bool = False):
@@ -346,56 +346,44 @@ class Context:
         rgb = np.empty((len(ranges), N // 2, 3), dtype=np.uint8) if k != 0.0 else None
         mags = np.empty((len(ranges), N // 2), dtype=np.float32) if want_mags else None
         h = C.c_void_p()
-        _capi.check(_capi.lib().mx_stft_ranges_keep(self.handle, audio.handle, N, _ptr(ranges), len(ranges), float(k),
-                                                    _ptr(mags) if mags is not None else None,
-                                                    _ptr(rgb) if rgb is not None else None, C.byref(h)))
+        _call("mx_stft_ranges_keep", self.handle, audio.handle, N, _ptr(ranges), len(ranges), float(k), _ptr(mags), _ptr(rgb),
+              C.byref(h))
         return KeptRows(self, h, N), rgb, mags
 
     # ---- STFT, device-resident outputs (raw device pointers, async on the ctx stream) ----
     def stft_hop_dev(self, audio: Audio, N: int, hop: int, first: int, count: int, d_mags: int | None,
                      d_pitch: int | None, band=(-1, -1)):
-        _capi.check(_capi.lib().mx_stft_hop_dev(self.handle, audio.handle, N, hop, first, count, band[0], band[1],
-                                                C.c_void_p(d_mags or 0), C.c_void_p(d_pitch or 0)))
+        _call("mx_stft_hop_dev", self.handle, audio.handle, N, hop, first, count, band[0], band[1], _dev(d_mags), _dev(d_pitch))
 
     def stft_ranges_dev(self, audio: Audio, N: int, d_ranges: int, count: int, d_mags: int | None,
                         d_pitch: int | None, band=(-1, -1)):
-        _capi.check(_capi.lib().mx_stft_ranges_dev(self.handle, audio.handle, N, C.c_void_p(d_ranges), count,
-                                                   band[0], band[1], C.c_void_p(d_mags or 0),
-                                                   C.c_void_p(d_pitch or 0)))
+        _call("mx_stft_ranges_dev", self.handle, audio.handle, N, C.c_void_p(d_ranges), count, band[0], band[1], _dev(d_mags),
+              _dev(d_pitch))
 
     # ---- YIN f0 tracking (build-defined; include/melonix_amd.h) ----
     def f0_track(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, fmin: float = _F0_FMIN,
                  fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """-> F0_DTYPE records of frames [first, first + count) (frame h centred on sample h*hop)."""
-        count = _frames_from(audio, hop, first, count)
-        out = np.empty(max(count, 0), dtype=F0_DTYPE)
-        _capi.check(_capi.lib().mx_f0_track(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
-                                            _ptr(out)))
-        return out
+        return self._frame_tracks("mx_f0_track", audio, sr, hop, first, count, (fmin, fmax, threshold), (F0_DTYPE,))[0]
 
     def f0_track_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_out: int, fmin: float = _F0_FMIN,
                      fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """The records stay in HBM at d_out (count x 16 bytes); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_f0_track_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
-                                                C.c_void_p(d_out or 0)))
+        _call("mx_f0_track_dev", self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold, _dev(d_out))
 
     # ---- candidate ladder and Viterbi decode (build-defined) ----
     def f0_candidates(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
                       fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """-> (track: F0_DTYPE records, exactly f0_track's; cands: count x 4 F0_CAND_DTYPE, the frames' candidate ladders)."""
-        count = _frames_from(audio, hop, first, count)
-        track = np.empty(max(count, 0), dtype=F0_DTYPE)
-        cands = np.empty((max(count, 0), _capi.F0_CANDS), dtype=F0_CAND_DTYPE)
-        _capi.check(_capi.lib().mx_f0_candidates(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
-                                                 _ptr(track), _ptr(cands)))
-        return track, cands
+        return self._frame_tracks("mx_f0_candidates", audio, sr, hop, first, count, (fmin, fmax, threshold),
+                                  (F0_DTYPE,), (F0_CAND_DTYPE, _capi.F0_CANDS))
 
     def f0_candidates_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_track: int | None, d_cands: int,
                           fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD):
         """The ladders stay in HBM at d_cands (count x 64 bytes), the plain records at d_track (count x 16 bytes; None: not
         wanted); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_f0_candidates_dev(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
-                                                     C.c_void_p(d_track or 0), C.c_void_p(d_cands or 0)))
+        _call("mx_f0_candidates_dev", self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold, _dev(d_track),
+              _dev(d_cands))
 
     def f0_decode(self, track, cands, **params):
         """The cheapest path through the frames' candidates and the unvoiced state -> (decoded F0_DTYPE track, uint8 state
@@ -406,48 +394,38 @@ class Context:
             raise ValueError("one row of candidates per frame of the track")
         out = np.empty(len(track), dtype=F0_DTYPE)
         state = np.empty(len(track), dtype=np.uint8)
-        _capi.check(_capi.lib().mx_f0_decode(self.handle, _ptr(track), _ptr(cands), len(track), _params_arg("decode", params),
-                                             _ptr(out), _ptr(state)))
+        _call("mx_f0_decode", self.handle, _ptr(track), _ptr(cands), len(track), _params_arg("decode", params), _ptr(out), _ptr(state))
         return out, state
 
     def f0_decode_dev(self, d_track: int, d_cands: int, count: int, d_out: int, d_state: int | None = None, **params):
         """Device pointers (d_out may be d_track; d_state None: not wanted); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_f0_decode_dev(self.handle, C.c_void_p(d_track or 0), C.c_void_p(d_cands or 0), count,
-                                                 _params_arg("decode", params), C.c_void_p(d_out or 0), C.c_void_p(d_state or 0)))
+        _call("mx_f0_decode_dev", self.handle, _dev(d_track), _dev(d_cands), count, _params_arg("decode", params), _dev(d_out),
+              _dev(d_state))
 
     def f0_track_decoded(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None,
                          fmin: float = _F0_FMIN, fmax: float = _F0_FMAX, threshold: float = _F0_THRESHOLD, **params):
         """Candidates and decode in one call -> the decoded F0_DTYPE track (tau 0: silent or unvoiced)."""
-        count = _frames_from(audio, hop, first, count)
-        out = np.empty(max(count, 0), dtype=F0_DTYPE)
-        _capi.check(_capi.lib().mx_f0_track_decoded(self.handle, audio.handle, sr, hop, first, count, fmin, fmax, threshold,
-                                                    _params_arg("decode", params), _ptr(out)))
-        return out
+        return self._frame_tracks("mx_f0_track_decoded", audio, sr, hop, first, count,
+                                  (fmin, fmax, threshold, _params_arg("decode", params)), (F0_DTYPE,))[0]
 
     def f0_decode_set_chunk(self, frames: int):
         """Frames per chunk of the decode's scans (0 = the default); for tests: the output does not depend on it."""
-        _capi.check(_capi.lib().mx_f0_decode_set_chunk(self.handle, int(frames)))
+        _call("mx_f0_decode_set_chunk", self.handle, int(frames))
 
     # ---- onset strength and onsets (build-defined; include/melonix_amd.h) ----
     def onset_flux(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, **params):
         """-> float32 onset strength of frames [first, first + count) (frame h centred on sample h*hop).  params: fields of
         onset_flux_params_default()."""
-        count = _frames_from(audio, hop, first, count)
-        out = np.empty(max(count, 0), dtype=np.float32)
-        _capi.check(_capi.lib().mx_onset_flux(self.handle, audio.handle, sr, hop, first, count, _params_arg("flux", params), _ptr(out)))
-        return out
+        return self._frame_tracks("mx_onset_flux", audio, sr, hop, first, count, (_params_arg("flux", params),), (np.float32,))[0]
 
     def onset_flux_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_flux: int, **params):
         """The values stay in HBM at d_flux (count x 4 bytes); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_onset_flux_dev(self.handle, audio.handle, sr, hop, first, count, _params_arg("flux", params),
-                                                  C.c_void_p(d_flux or 0)))
+        _call("mx_onset_flux_dev", self.handle, audio.handle, sr, hop, first, count, _params_arg("flux", params), _dev(d_flux))
 
     def onsets_detect(self, audio: Audio, sr: int, hop: int = 256, flux_params: dict | None = None, pick_params: dict | None = None):
         """Flux over the whole file and the picks from it -> ONSET_DTYPE array."""
-        out, cnt = C.c_void_p(), C.c_int64()
-        _capi.check(_capi.lib().mx_onsets_detect(self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
-                                                 _params_arg("pick", pick_params or {}), C.byref(out), C.byref(cnt)))
-        return _take_records(out, cnt.value, ONSET_DTYPE)
+        return _handed(ONSET_DTYPE, "mx_onsets_detect", self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
+                       _params_arg("pick", pick_params or {}))
 
     # ---- sibilant features, segments, protection and balance (build-defined; include/melonix_amd.h) ----
     sib_feature_params_default = staticmethod(sib_feature_params_default)
@@ -456,24 +434,19 @@ class Context:
     def sib_features(self, audio: Audio, sr: int, hop: int = 256, first: int = 0, count: int | None = None, **params):
         """-> SIB_FEAT_DTYPE records of frames [first, first + count) (frame h centred on sample h*hop).  params: fields of
         sib_feature_params_default()."""
-        count = _frames_from(audio, hop, first, count)
-        out = np.empty(max(count, 0), dtype=SIB_FEAT_DTYPE)
-        _capi.check(_capi.lib().mx_sib_features(self.handle, audio.handle, sr, hop, first, count, _params_arg("sib_feature", params),
-                                                _ptr(out)))
-        return out
+        return self._frame_tracks("mx_sib_features", audio, sr, hop, first, count, (_params_arg("sib_feature", params),),
+                                  (SIB_FEAT_DTYPE,))[0]
 
     def sib_features_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_feat: int, **params):
         """The records stay in HBM at d_feat (count x 16 bytes); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_sib_features_dev(self.handle, audio.handle, sr, hop, first, count,
-                                                    _params_arg("sib_feature", params), C.c_void_p(d_feat or 0)))
+        _call("mx_sib_features_dev", self.handle, audio.handle, sr, hop, first, count, _params_arg("sib_feature", params),
+              _dev(d_feat))
 
     def sibilants_detect(self, audio: Audio, sr: int, hop: int = 256, feature_params: dict | None = None, **params):
         """Features over the whole file and the segments from them -> SIBILANT_DTYPE array.  params: fields of
         sibilant_params_default()."""
-        out, cnt = C.c_void_p(), C.c_int64()
-        _capi.check(_capi.lib().mx_sibilants_detect(self.handle, audio.handle, sr, hop, _params_arg("sib_feature", feature_params or {}),
-                                                    _params_arg("sibilant", params), C.byref(out), C.byref(cnt)))
-        return _take_records(out, cnt.value, SIBILANT_DTYPE)
+        return _handed(SIBILANT_DTYPE, "mx_sibilants_detect", self.handle, audio.handle, sr, hop,
+                       _params_arg("sib_feature", feature_params or {}), _params_arg("sibilant", params))
 
     def sibilants(self, feat, hop: int = 256, first: int = 0, **params):
         return sibilants(feat, hop, first, **params)
@@ -484,51 +457,44 @@ class Context:
     def chroma(self, audio: Audio, sr: int, hop: int = 2048, first: int = 0, count: int | None = None, **params):
         """-> (count, 40) float32: the chroma records of frames [first, first + count) (frame h centred on sample h*hop).
         params: fields of chroma_params_default()."""
-        count = _frames_from(audio, hop, first, count)
-        out = np.empty((max(count, 0), CHROMA_COLS), dtype=np.float32)
-        _capi.check(_capi.lib().mx_chroma(self.handle, audio.handle, sr, hop, first, count, _params_arg("chroma", params), _ptr(out)))
-        return out
+        return self._frame_tracks("mx_chroma", audio, sr, hop, first, count, (_params_arg("chroma", params),),
+                                  (np.float32, CHROMA_COLS))[0]
 
     def chroma_dev(self, audio: Audio, sr: int, hop: int, first: int, count: int, d_out: int, **params):
         """The records stay in HBM at d_out (count x 160 bytes); asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_chroma_dev(self.handle, audio.handle, sr, hop, first, count, _params_arg("chroma", params),
-                                              C.c_void_p(d_out or 0)))
+        _call("mx_chroma_dev", self.handle, audio.handle, sr, hop, first, count, _params_arg("chroma", params), _dev(d_out))
 
     def chroma_sum(self, chroma, jobs):
         """Column sums of (count, 40) float32 records over `jobs` ((first_frame, frames) pairs) -> (njobs, 40) float64."""
         rec = np.ascontiguousarray(chroma, dtype=np.float32).reshape(-1, CHROMA_COLS)
         jobs = _records(jobs, CHROMA_JOB_DTYPE)
         out = np.empty((len(jobs), CHROMA_COLS), dtype=np.float64)
-        _capi.check(_capi.lib().mx_chroma_sum(self.handle, _ptr(rec) if len(rec) else None, len(rec), _ptr(jobs) if len(jobs) else None,
-                                              len(jobs), _ptr(out) if len(jobs) else None))
+        _call("mx_chroma_sum", self.handle, _opt(rec), len(rec), _opt(jobs), len(jobs), _opt(out))
         return out
 
     def chroma_sum_dev(self, d_chroma: int, count: int, d_jobs: int, njobs: int, d_out: int):
         """The same with records, jobs and sums (njobs x 320 bytes) in HBM; asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_chroma_sum_dev(self.handle, C.c_void_p(d_chroma or 0), count, C.c_void_p(d_jobs or 0), njobs,
-                                                  C.c_void_p(d_out or 0)))
+        _call("mx_chroma_sum_dev", self.handle, _dev(d_chroma), count, _dev(d_jobs), njobs, _dev(d_out))
 
     def key_detect(self, audio: Audio, sr: int, hop: int = 2048, window_frames: int = 0, window_hop: int = 1, **params):
         """Key, scale and tuning of the whole file -> (dict of KEY_DTYPE's fields, KEY_WINDOW_DTYPE array: one key per window
         of window_frames frames every window_hop; none where window_frames is 0).  params: fields of chroma_params_default()."""
-        key, out, cnt = _capi.Key(), C.c_void_p(), C.c_int64()
-        _capi.check(_capi.lib().mx_key_detect(self.handle, audio.handle, sr, hop, _params_arg("chroma", params), int(window_frames),
-                                              int(window_hop), C.byref(key), C.byref(out), C.byref(cnt)))
-        return _key_dict(key), _take_records(out, cnt.value, KEY_WINDOW_DTYPE)
+        key = _capi.Key()
+        windows = _handed(KEY_WINDOW_DTYPE, "mx_key_detect", self.handle, audio.handle, sr, hop, _params_arg("chroma", params),
+                          int(window_frames), int(window_hop), C.byref(key))
+        return _key_dict(key), windows
 
     # ---- pitch drift and vibrato inside notes (build-defined; include/melonix_amd.h) ----
     def contour_cents(self, track, sr: int, threshold: float = 0.15, rms_floor: float = 1e-3):
         """-> int32[count]: the cents (1/16 cent, 1600 x the note) of F0_DTYPE records, CONTOUR_NONE where unvoiced."""
         track = np.ascontiguousarray(track, dtype=F0_DTYPE)
         out = np.empty(len(track), dtype=np.int32)
-        _capi.check(_capi.lib().mx_contour_cents(self.handle, _ptr(track) if len(track) else None, len(track), sr, threshold,
-                                                 rms_floor, _ptr(out) if len(out) else None))
+        _call("mx_contour_cents", self.handle, _opt(track), len(track), sr, threshold, rms_floor, _opt(out))
         return out
 
     def contour_cents_dev(self, d_track: int, count: int, sr: int, threshold: float, rms_floor: float, d_cents: int):
         """count records at d_track -> count int32 at d_cents, both in HBM; asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_contour_cents_dev(self.handle, C.c_void_p(d_track or 0), count, sr, threshold, rms_floor,
-                                                     C.c_void_p(d_cents or 0)))
+        _call("mx_contour_cents_dev", self.handle, _dev(d_track), count, sr, threshold, rms_floor, _dev(d_cents))
 
     def contour_split(self, cents, spans, want_rec: bool = True, want_stat: bool = True, **params):
         """int32 cents and (first, frames) spans -> (CONTOUR_REC_DTYPE[count] | None, CONTOUR_STAT_DTYPE[nspans] | None).
@@ -537,16 +503,15 @@ class Context:
         spans = _records(spans, CONTOUR_SPAN_DTYPE)
         rec = np.empty(len(cents), dtype=CONTOUR_REC_DTYPE) if want_rec else None
         stat = np.empty(len(spans), dtype=CONTOUR_STAT_DTYPE) if want_stat else None
-        _capi.check(_capi.lib().mx_contour_split(self.handle, _ptr(cents) if len(cents) else None, len(cents),
-                                                 _ptr(spans) if len(spans) else None, len(spans), _contour_params(params),
-                                                 _ptr(rec), _ptr(stat)))
+        _call("mx_contour_split", self.handle, _opt(cents), len(cents), _opt(spans), len(spans), _contour_params(params), _ptr(rec),
+              _ptr(stat))
         return rec, stat
 
     def contour_split_dev(self, d_cents: int, count: int, d_spans: int, nspans: int, d_rec: int | None, d_stat: int | None,
                           **params):
         """Everything in HBM; asynchronous on the context's stream.  The spans are NOT checked (include/melonix_amd.h)."""
-        _capi.check(_capi.lib().mx_contour_split_dev(self.handle, C.c_void_p(d_cents or 0), count, C.c_void_p(d_spans or 0), nspans,
-                                                     _contour_params(params), C.c_void_p(d_rec or 0), C.c_void_p(d_stat or 0)))
+        _call("mx_contour_split_dev", self.handle, _dev(d_cents), count, _dev(d_spans), nspans, _contour_params(params), _dev(d_rec),
+              _dev(d_stat))
 
     def pitch_contour(self, track, sr: int, hop: int, notes, first: int = 0, threshold: float = 0.15, rms_floor: float = 1e-3,
                       **params):
@@ -556,33 +521,9 @@ class Context:
         notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
         rec = np.empty(len(track), dtype=CONTOUR_REC_DTYPE)
         stat = np.empty(len(notes), dtype=CONTOUR_STAT_DTYPE)
-        _capi.check(_capi.lib().mx_pitch_contour(self.handle, _ptr(track) if len(track) else None, len(track), sr, hop, first,
-                                                 _ptr(notes) if len(notes) else None, len(notes), threshold, rms_floor,
-                                                 _contour_params(params) if params else None, _ptr(rec), _ptr(stat)))
+        _call("mx_pitch_contour", self.handle, _opt(track), len(track), sr, hop, first, _opt(notes), len(notes), threshold, rms_floor,
+              _contour_params(params) if params else None, _ptr(rec), _ptr(stat))
         return rec, stat
-
-    def psola_render_bend(self, audio: Audio, sr: int, hop: int, track, markers, bend, points=(), want_f32: bool = True,
-                          want_i16: bool = True, **params):
-        """psola_render_formant following a bend curve (float32 semitones per frame of the track, contour_bend's); no points:
-        the plain records and kernel."""
-        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
-        m = _capi.markers_array(markers)
-        pts, b = _formant_points(points), _bend_arg(bend, len(track))
-        f32, i16 = _pcm_pair(_render_length(audio.n, sr, m, len(markers)), want_f32, want_i16)
-        _capi.check(_capi.lib().mx_psola_render_bend(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
-                                                     len(track), _params_arg("psola", params), m, len(markers), *_points_args(pts),
-                                                     _ptr(b), _ptr(f32), _ptr(i16)))
-        return f32, i16
-
-    def psola_render_bend_dev(self, audio: Audio, sr: int, hop: int, track, markers, bend, points, d_f32: int | None,
-                              d_i16: int | None, **params):
-        """The same with the PCM left in HBM (the render's length each); blocks until the records are uploaded and used."""
-        track = np.ascontiguousarray(track, dtype=F0_DTYPE)
-        m = _capi.markers_array(markers)
-        pts, b = _formant_points(points), _bend_arg(bend, len(track))
-        _capi.check(_capi.lib().mx_psola_render_bend_dev(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
-                                                         len(track), _params_arg("psola", params), m, len(markers),
-                                                         *_points_args(pts), _ptr(b), C.c_void_p(d_f32 or 0), C.c_void_p(d_i16 or 0)))
 
     def formant_protect(self, points, sibs, ramp: int, n: int):
         return formant_protect(points, sibs, ramp, n)
@@ -593,22 +534,18 @@ class Context:
     def audio_gain(self, audio: Audio, points) -> Audio:
         """A new Audio: `audio` through the piecewise-linear gain of `points` ((sample, amp) pairs or a GAIN_POINT_DTYPE array;
         none: a copy).  Blocks."""
-        pts = _gain_points(points)
-        h = C.c_void_p()
-        _capi.check(_capi.lib().mx_audio_gain(self.handle, audio.handle, _ptr(pts) if len(pts) else None, len(pts), C.byref(h)))
-        return Audio(self, h, audio.n)
+        pts = _records(points, GAIN_POINT_DTYPE)
+        return self._audio(audio.n, "mx_audio_gain", audio.handle, _opt(pts), len(pts))
 
     def audio_gain_dev(self, audio: Audio, d_points: int, npts: int) -> Audio:
         """The same with the points in HBM (not validated there); asynchronous on the context's stream."""
-        h = C.c_void_p()
-        _capi.check(_capi.lib().mx_audio_gain_dev(self.handle, audio.handle, C.c_void_p(d_points or 0), npts, C.byref(h)))
-        return Audio(self, h, audio.n)
+        return self._audio(audio.n, "mx_audio_gain_dev", audio.handle, _dev(d_points), npts)
 
     def audio_download(self, audio: Audio, first: int = 0, count: int | None = None):
         """Samples [first, first + count) of an Audio (count None: to the end of the file; the pads are readable) -> float32."""
         count = audio.n - first if count is None else count
         out = np.empty(max(count, 0), dtype=np.float32)
-        _capi.check(_capi.lib().mx_audio_download(self.handle, audio.handle, first, count, _ptr(out)))
+        _call("mx_audio_download", self.handle, audio.handle, first, count, _ptr(out))
         return out
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
@@ -616,93 +553,79 @@ class Context:
         """-> the smoothed float32 curve of a host flux curve (half-width `width`; 0: the sanitising copy)."""
         flux = np.ascontiguousarray(flux, dtype=np.float32)
         out = np.empty(len(flux), dtype=np.float32)
-        _capi.check(_capi.lib().mx_tempo_smooth(self.handle, _ptr(flux) if len(flux) else None, len(flux), width,
-                                                _ptr(out) if len(flux) else None))
+        _call("mx_tempo_smooth", self.handle, _opt(flux), len(flux), width, _opt(out))
         return out
 
     def tempo_smooth_dev(self, d_flux: int, count: int, width: int, d_out: int):
         """count floats at d_flux -> d_out, both in HBM; asynchronous on the context's stream."""
-        _capi.check(_capi.lib().mx_tempo_smooth_dev(self.handle, C.c_void_p(d_flux or 0), count, width, C.c_void_p(d_out or 0)))
+        _call("mx_tempo_smooth_dev", self.handle, _dev(d_flux), count, width, _dev(d_out))
 
     def tempo_comb(self, curve, jobs):
         """COMB_JOB_DTYPE jobs (or (first, frames, period_q16) tuples) over a host curve -> COMB_DTYPE records, one per job."""
         curve = np.ascontiguousarray(curve, dtype=np.float32)
-        jobs = np.ascontiguousarray(jobs if isinstance(jobs, np.ndarray) and jobs.dtype == COMB_JOB_DTYPE
-                                    else np.array([tuple(int(v) for v in j) for j in jobs], dtype=COMB_JOB_DTYPE))
+        jobs = _records(jobs, COMB_JOB_DTYPE)
         out = np.empty(len(jobs), dtype=COMB_DTYPE)
-        _capi.check(_capi.lib().mx_tempo_comb(self.handle, _ptr(curve) if len(curve) else None, len(curve),
-                                              _ptr(jobs) if len(jobs) else None, len(jobs), _ptr(out) if len(jobs) else None))
+        _call("mx_tempo_comb", self.handle, _opt(curve), len(curve), _opt(jobs), len(jobs), _opt(out))
         return out
 
     def tempo_comb_dev(self, d_curve: int, count: int, d_jobs: int, njobs: int, d_out: int):
         """Jobs and curve in HBM -> njobs records at d_out; asynchronous on the context's stream.  The jobs are not checked."""
-        _capi.check(_capi.lib().mx_tempo_comb_dev(self.handle, C.c_void_p(d_curve or 0), count, C.c_void_p(d_jobs or 0), njobs,
-                                                  C.c_void_p(d_out or 0)))
+        _call("mx_tempo_comb_dev", self.handle, _dev(d_curve), count, _dev(d_jobs), njobs, _dev(d_out))
 
     @staticmethod
-    def _tempo_result(t, win, cnt, want_windows: bool):
-        res = {k: getattr(t, k) for k, _ in _capi.Tempo._fields_}
-        return (res, _take_records(win, cnt.value, TEMPO_WINDOW_DTYPE)) if want_windows else res
+    def _tempo(want_windows: bool, name: str, *args):
+        """name(*args, &tempo, &windows | NULL, &count | NULL) -> dict of mx_tempo's fields, with want_windows (dict, windows)."""
+        t, win, cnt = _capi.Tempo(), C.c_void_p(), C.c_int64()
+        _call(name, *args, C.byref(t), C.byref(win) if want_windows else None, C.byref(cnt) if want_windows else None)
+        return (_fields(t), _take_records(win, cnt.value, TEMPO_WINDOW_DTYPE)) if want_windows else _fields(t)
 
     def tempo_from_flux(self, flux, sr: int, hop: int = 256, first_frame: int = 0, want_windows: bool = False, **params):
         """Tempo and grid offset of a host flux curve (flux[0] = frame first_frame) -> dict of mx_tempo's fields, with
         want_windows (dict, TEMPO_WINDOW_DTYPE array).  params: fields of tempo_params_default()."""
         flux = np.ascontiguousarray(flux, dtype=np.float32)
-        t, win, cnt = _capi.Tempo(), C.c_void_p(), C.c_int64()
-        _capi.check(_capi.lib().mx_tempo_from_flux(self.handle, _ptr(flux) if len(flux) else None, len(flux), sr, hop, first_frame,
-                                                   _params_arg("tempo", params), C.byref(t),
-                                                   C.byref(win) if want_windows else None, C.byref(cnt) if want_windows else None))
-        return self._tempo_result(t, win, cnt, want_windows)
+        return self._tempo(want_windows, "mx_tempo_from_flux", self.handle, _opt(flux), len(flux), sr, hop, first_frame,
+                           _params_arg("tempo", params))
 
     def tempo_detect(self, audio: Audio, sr: int, hop: int = 256, flux_params: dict | None = None, want_windows: bool = False,
                      **params):
         """Flux over the whole file, kept in HBM, and the estimate from it; as tempo_from_flux."""
-        t, win, cnt = _capi.Tempo(), C.c_void_p(), C.c_int64()
-        _capi.check(_capi.lib().mx_tempo_detect(self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
-                                                _params_arg("tempo", params), C.byref(t),
-                                                C.byref(win) if want_windows else None, C.byref(cnt) if want_windows else None))
-        return self._tempo_result(t, win, cnt, want_windows)
+        return self._tempo(want_windows, "mx_tempo_detect", self.handle, audio.handle, sr, hop, _params_arg("flux", flux_params or {}),
+                           _params_arg("tempo", params))
 
     # ---- grains / resynthesis ----
     def grains_dev(self, audio: Audio):
         s, l, cnt = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int64()
-        _capi.check(_capi.lib().mx_grains_dev(self.handle, audio.handle, C.byref(s), C.byref(l), C.byref(cnt)))
-        return _take_i32(s, cnt.value), _take_i32(l, cnt.value)
+        _call("mx_grains_dev", self.handle, audio.handle, C.byref(s), C.byref(l), C.byref(cnt))
+        return _take_array(s, cnt.value), _take_array(l, cnt.value)
 
     def grain_table_dev(self, audio: Audio):
         """-> (starts, lens, firsts): the grain chain built on the device, with every grain's first sample."""
         s, l, f, cnt = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_float)(), C.c_int64()
-        _capi.check(_capi.lib().mx_grain_table_dev(self.handle, audio.handle, C.byref(s), C.byref(l), C.byref(f), C.byref(cnt)))
-        firsts = np.ctypeslib.as_array(f, shape=(max(cnt.value, 1),))[:cnt.value].astype(np.float32, copy=True)
-        _capi.lib().mx_free(f)
-        return _take_i32(s, cnt.value), _take_i32(l, cnt.value), firsts
+        _call("mx_grain_table_dev", self.handle, audio.handle, C.byref(s), C.byref(l), C.byref(f), C.byref(cnt))
+        firsts = _take_array(f, cnt.value)
+        return _take_array(s, cnt.value), _take_array(l, cnt.value), firsts
 
     def resynth(self, audio: Audio, steps, nsamples: int, want_f32: bool = True, want_i16: bool = True):
         steps = np.ascontiguousarray(steps, dtype=STEP_DTYPE)
         f32, i16 = _pcm_pair(nsamples, want_f32, want_i16)
-        _capi.check(_capi.lib().mx_resynth(self.handle, audio.handle, _ptr(steps), len(steps), nsamples, _ptr(f32),
-                                           _ptr(i16)))
+        _call("mx_resynth", self.handle, audio.handle, _ptr(steps), len(steps), nsamples, _ptr(f32), _ptr(i16))
         return f32, i16
 
     def resynth_dev(self, audio: Audio, d_steps: int, nsteps: int, nsamples: int, d_f32: int | None,
                     d_i16: int | None):
-        _capi.check(_capi.lib().mx_resynth_dev(self.handle, audio.handle, C.c_void_p(d_steps), nsteps, nsamples,
-                                               C.c_void_p(d_f32 or 0), C.c_void_p(d_i16 or 0)))
+        _call("mx_resynth_dev", self.handle, audio.handle, C.c_void_p(d_steps), nsteps, nsamples, _dev(d_f32), _dev(d_i16))
 
     def pv_set_chunk_frames(self, frames: int):
         """Override of the phase vocoder's arena policy: two-slot chunks of exactly `frames` frames (rounded up to a multiple of
         32); 0 = back to the budget (resident when the call fits, else the longest chunks it holds)."""
-        _capi.check(_capi.lib().mx_pv_set_chunk_frames(self.handle, int(frames)))
+        _call("mx_pv_set_chunk_frames", self.handle, int(frames))
 
     def pv_set_arena_budget(self, nbytes: int):
         """Bytes the phase vocoder's work arena may take; 0 = the default (MELONIX_PV_ARENA_MB, else a quarter of the free memory)."""
-        _capi.check(_capi.lib().mx_pv_set_arena_budget(self.handle, int(nbytes)))
+        _call("mx_pv_set_arena_budget", self.handle, int(nbytes))
 
     def pv_arena_budget(self) -> int:
-        v = int(_capi.lib().mx_pv_arena_budget(self.handle))
-        if v < 0:
-            _capi.check(v)
-        return v
+        return _call("mx_pv_arena_budget", self.handle)
 
     def pv_last_chunks(self) -> int:
         """Chunks the last phase-vocoder run of this context took (1 = resident)."""
@@ -715,45 +638,47 @@ class Context:
     def pv_pitch_shift(self, audio: Audio, semitones: float, want_f32: bool = True, want_i16: bool = True):
         """Build-defined phase-vocoder pitch shift (no reference counterpart) -> (f32 | None, int16 | None)."""
         f32, i16 = _pcm_pair(audio.n, want_f32, want_i16)
-        _capi.check(_capi.lib().mx_pv_pitch_shift(self.handle, audio.handle, float(semitones), _ptr(f32), _ptr(i16)))
+        _call("mx_pv_pitch_shift", self.handle, audio.handle, float(semitones), _ptr(f32), _ptr(i16))
         return f32, i16
 
     def pv_pitch_shift_dev(self, audio: Audio, semitones: float, d_f32: int | None, d_i16: int | None):
-        _capi.check(_capi.lib().mx_pv_pitch_shift_dev(self.handle, audio.handle, float(semitones),
-                                                      C.c_void_p(d_f32) if d_f32 else None,
-                                                      C.c_void_p(d_i16) if d_i16 else None))
+        _call("mx_pv_pitch_shift_dev", self.handle, audio.handle, float(semitones), _dev(d_f32), _dev(d_i16))
 
     def pv_render(self, audio: Audio, sr: int, markers, want_f32: bool = True, want_i16: bool = True):
         """Marker-driven phase vocoder (build-defined) -> (f32 | None, int16 | None) over the warped duration."""
         m = _capi.markers_array(markers)
-        f32, i16 = _pcm_pair(_render_length(audio.n, sr, m, len(markers)), want_f32, want_i16)
-        _capi.check(_capi.lib().mx_pv_render(self.handle, audio.handle, sr, m, len(markers), _ptr(f32), _ptr(i16)))
+        f32, i16 = _pcm_pair(_call("mx_pv_render_length", audio.n, sr, m, len(markers)), want_f32, want_i16)
+        _call("mx_pv_render", self.handle, audio.handle, sr, m, len(markers), _ptr(f32), _ptr(i16))
         return f32, i16
 
     # ---- formant-preserving PSOLA rendering driven by the f0 track, and the independent formant shift on it (build-defined;
     # include/melonix_amd.h).  Each call is written once over the record kind (`formant`: the "_formant" entry point, its
-    # record dtype and, for a plan or a render, its points: _psola_kind) ----
+    # record dtype and, for a plan or a render, its points: _PSOLA_KINDS) and over `bent` (the "_bend" entry point, which takes
+    # a bend curve, or NULL, after the points) ----
     def _psola_synth(self, formant: bool, audio: Audio, grains, nsamples: int, want_f32: bool, want_i16: bool):
         sfx, dtype = _PSOLA_KINDS[formant]
         grains = np.ascontiguousarray(grains, dtype=dtype)
         f32, i16 = _pcm_pair(nsamples, want_f32, want_i16)
-        _capi.check(getattr(_capi.lib(), "mx_psola_synth" + sfx)(self.handle, audio.handle, _ptr(grains) if len(grains) else None,
-                                                                 len(grains), nsamples, _ptr(f32), _ptr(i16)))
+        _call("mx_psola_synth" + sfx, self.handle, audio.handle, _opt(grains), len(grains), nsamples, _ptr(f32), _ptr(i16))
         return f32, i16
 
     def _psola_synth_dev(self, formant: bool, audio: Audio, d_grains, ngrains: int, nsamples: int, d_f32, d_i16):
-        _capi.check(getattr(_capi.lib(), f"mx_psola_synth{_PSOLA_KINDS[formant][0]}_dev")(
-            self.handle, audio.handle, C.c_void_p(d_grains or 0), ngrains, nsamples, C.c_void_p(d_f32 or 0), C.c_void_p(d_i16 or 0)))
+        _call(f"mx_psola_synth{_PSOLA_KINDS[formant][0]}_dev", self.handle, audio.handle, _dev(d_grains), ngrains, nsamples,
+              _dev(d_f32), _dev(d_i16))
 
-    def _psola_render(self, formant: bool, audio: Audio, sr: int, hop: int, track, markers, points, want_f32: bool, want_i16: bool,
-                      params: dict):
+    def _psola_render(self, formant: bool, bent: bool, audio: Audio, sr: int, hop: int, track, markers, points, bend, params: dict,
+                      want=None, dev=None):
+        """mx_psola_render, mx_psola_render_formant (formant) or mx_psola_render_bend (formant and bent: it takes the points
+        and then the curve, or NULL).  want: (want_f32, want_i16), host outputs over the warped duration; dev: (d_f32, d_i16)
+        instead, the "_dev" entry point, nothing returned."""
         track = np.ascontiguousarray(track, dtype=F0_DTYPE)
         m = _capi.markers_array(markers)
-        sfx, _, pts = _psola_kind(formant, points)
-        f32, i16 = _pcm_pair(_render_length(audio.n, sr, m, len(markers)), want_f32, want_i16)
-        _capi.check(getattr(_capi.lib(), "mx_psola_render" + sfx)(self.handle, audio.handle, sr, hop, _ptr(track) if len(track) else None,
-                                                                  len(track), _params_arg("psola", params), m, len(markers),
-                                                                  *_points_args(pts), _ptr(f32), _ptr(i16)))
+        pts = _formant_points(points) if formant else None
+        b = _bend_arg(bend, len(track)) if bent else None  # (held here: it must outlive the call, like pts)
+        name = "mx_psola_render" + ("_bend" if bent else _PSOLA_KINDS[formant][0]) + ("_dev" if dev else "")
+        f32, i16 = (None, None) if dev else _pcm_pair(_call("mx_pv_render_length", audio.n, sr, m, len(markers)), *want)
+        _call(name, self.handle, audio.handle, sr, hop, _opt(track), len(track), _params_arg("psola", params), m, len(markers),
+              *_points_args(pts), *((_ptr(b),) if bent else ()), *(map(_dev, dev) if dev else (_ptr(f32), _ptr(i16))))
         return f32, i16
 
     def psola_synth(self, audio: Audio, grains, nsamples: int, want_f32: bool = True, want_i16: bool = True):
@@ -769,7 +694,7 @@ class Context:
                      **params):
         """Plan and synthesis in one call -> (f32 | None, int16 | None) over the warped duration (pv_render's length).
         track: the F0_DTYPE records of every frame of the file at `hop`; params: fields of psola_params_default()."""
-        return self._psola_render(False, audio, sr, hop, track, markers, None, want_f32, want_i16, params)
+        return self._psola_render(False, False, audio, sr, hop, track, markers, None, None, params, want=(want_f32, want_i16))
 
     def psola_synth_formant(self, audio: Audio, fgrains, nsamples: int, want_f32: bool = True, want_i16: bool = True):
         """psola_synth over PSOLA_FGRAIN_DTYPE records (psola_plan_formant); the records are checked first."""
@@ -784,15 +709,27 @@ class Context:
                              want_i16: bool = True, **params):
         """psola_render with the envelope moved along `points`: (source sample, semitones) pairs, samples strictly
         increasing.  No points: psola_render itself."""
-        return self._psola_render(True, audio, sr, hop, track, markers, points, want_f32, want_i16, params)
+        return self._psola_render(True, False, audio, sr, hop, track, markers, points, None, params,
+                                  want=(want_f32, want_i16))
+
+    def psola_render_bend(self, audio: Audio, sr: int, hop: int, track, markers, bend, points=(), want_f32: bool = True,
+                          want_i16: bool = True, **params):
+        """psola_render_formant following a bend curve (float32 semitones per frame of the track, contour_bend's); no points:
+        the plain records and kernel."""
+        return self._psola_render(True, True, audio, sr, hop, track, markers, points, bend, params,
+                                  want=(want_f32, want_i16))
+
+    def psola_render_bend_dev(self, audio: Audio, sr: int, hop: int, track, markers, bend, points, d_f32: int | None,
+                              d_i16: int | None, **params):
+        """The same with the PCM left in HBM (the render's length each); blocks until the records are uploaded and used."""
+        self._psola_render(True, True, audio, sr, hop, track, markers, points, bend, params, dev=(d_f32, d_i16))
 
     # ---- one rank of a multi-GPU phase-vocoder run (melonix_amd.shard.pv_pitch_shift_rank drives these) ----
     def pv_shard_analyze(self, audio: Audio, semitones: float, rank: int, world: int):
         """Stage 1 -> (tot_sums uint32[2048], tot_org uint16[2048]): this rank's frames as one map of the phase row."""
         sums = np.empty(2048, dtype=np.uint32)
         org = np.empty(2048, dtype=np.uint16)
-        _capi.check(_capi.lib().mx_pv_shard_analyze(self.handle, audio.handle, float(semitones), rank, world,
-                                                    _ptr(sums), _ptr(org)))
+        _call("mx_pv_shard_analyze", self.handle, audio.handle, float(semitones), rank, world, _ptr(sums), _ptr(org))
         return sums, org
 
     def pv_shard_synthesize(self, carry_in):
@@ -800,7 +737,7 @@ class Context:
         head = np.empty(3840, dtype=np.float32)
         tail = np.empty(3840, dtype=np.float32)
         c = None if carry_in is None else np.ascontiguousarray(carry_in, dtype=np.uint32)
-        _capi.check(_capi.lib().mx_pv_shard_synthesize(self.handle, _ptr(c), _ptr(head), _ptr(tail)))
+        _call("mx_pv_shard_synthesize", self.handle, _ptr(c), _ptr(head), _ptr(tail))
         return head, tail
 
     def pv_shard_finish(self, count: int, prev_tail, next_head, want_f32: bool = True, want_i16: bool = True):
@@ -808,27 +745,27 @@ class Context:
         f32, i16 = _pcm_pair(count, want_f32, want_i16)
         pt = None if prev_tail is None else np.ascontiguousarray(prev_tail, dtype=np.float32)
         nh = None if next_head is None else np.ascontiguousarray(next_head, dtype=np.float32)
-        _capi.check(_capi.lib().mx_pv_shard_finish(self.handle, _ptr(pt), _ptr(nh), _ptr(f32), _ptr(i16)))
+        _call("mx_pv_shard_finish", self.handle, _ptr(pt), _ptr(nh), _ptr(f32), _ptr(i16))
         return f32, i16
 
     # (the same stages with everything on the device: pointers are integers, e.g. torch tensors' data_ptr())
     def pv_shard_analyze_dev(self, audio: Audio, semitones: float, rank: int, world: int, d_map_out: int):
-        _capi.check(_capi.lib().mx_pv_shard_analyze_dev(self.handle, audio.handle, float(semitones), int(rank), int(world),
-                                                        C.c_void_p(int(d_map_out))))
+        _call("mx_pv_shard_analyze_dev", self.handle, audio.handle, float(semitones), int(rank), int(world),
+              C.c_void_p(int(d_map_out)))
 
     def pv_shard_synthesize_dev(self, d_maps_all: int, d_f32: int | None, d_i16: int | None, d_seams_out: int):
-        _capi.check(_capi.lib().mx_pv_shard_synthesize_dev(self.handle, C.c_void_p(int(d_maps_all)), C.c_void_p(int(d_f32 or 0)),
-                                                           C.c_void_p(int(d_i16 or 0)), C.c_void_p(int(d_seams_out))))
+        _call("mx_pv_shard_synthesize_dev", self.handle, C.c_void_p(int(d_maps_all)), _dev(int(d_f32 or 0)), _dev(int(d_i16 or 0)),
+              C.c_void_p(int(d_seams_out)))
 
     def pv_shard_finish_dev(self, d_seams_all: int):
-        _capi.check(_capi.lib().mx_pv_shard_finish_dev(self.handle, C.c_void_p(int(d_seams_all))))
+        _call("mx_pv_shard_finish_dev", self.handle, C.c_void_p(int(d_seams_all)))
 
     def minmax_pyramid(self, audio: Audio):
         """App::calcPicks on the GPU -> list of (count_l, 2) float32 arrays {min,max}, one per level."""
         picks = np.empty(2 * max(audio.n, 1), dtype=np.float32)
         counts = np.zeros(64, dtype=np.int64)
         nl = C.c_int()
-        _capi.check(_capi.lib().mx_minmax_pyramid(self.handle, audio.handle, _ptr(picks), _ptr(counts), C.byref(nl)))
+        _call("mx_minmax_pyramid", self.handle, audio.handle, _ptr(picks), _ptr(counts), C.byref(nl))
         out, off = [], 0
         for l in range(nl.value):
             out.append(picks[off:off + 2 * counts[l]].reshape(-1, 2).copy())
@@ -838,14 +775,13 @@ class Context:
     def resynth_to_wav(self, audio: Audio, steps, nsamples: int, sr: int, path: str, strict: bool = True):
         """Resynthesis of a built schedule straight into a WAV file (PCM streamed off the device in pieces)."""
         steps = np.ascontiguousarray(steps)
-        _capi.check(_capi.lib().mx_resynth_to_wav(self.handle, audio.handle, _ptr(steps) if len(steps) else None,
-                                                  len(steps), nsamples, str(path).encode(), sr, 1 if strict else 0))
+        _call("mx_resynth_to_wav", self.handle, audio.handle, _opt(steps), len(steps), nsamples, str(path).encode(), sr,
+              1 if strict else 0)
 
     def export_wav(self, wav, sr: int, markers, path: str, strict: bool = True):
         wav = np.ascontiguousarray(wav, dtype=np.float32)
         m = _capi.markers_array(markers)
-        _capi.check(_capi.lib().mx_export_wav(self.handle, _ptr(wav), len(wav), sr, m, len(markers),
-                                              str(path).encode(), 1 if strict else 0))
+        _call("mx_export_wav", self.handle, _ptr(wav), len(wav), sr, m, len(markers), str(path).encode(), 1 if strict else 0)
 
 
 def _take_steps(p, count):
@@ -862,8 +798,9 @@ def _take_steps(p, count):
     return np.frombuffer(buf, dtype=STEP_DTYPE)
 
 
-def _take_i32(p, cnt):
-    out = np.ctypeslib.as_array(p, shape=(max(cnt, 1),))[:cnt].astype(np.int32, copy=True)
+def _take_array(p, cnt):
+    """A library-allocated array of cnt int32 or float values (p: the typed pointer) as a numpy array of its own; mx_free."""
+    out = np.ctypeslib.as_array(p, shape=(max(cnt, 1),))[:cnt].copy()
     _capi.lib().mx_free(p)
     return out
 
@@ -872,52 +809,48 @@ def _take_i32(p, cnt):
 def grains_host(wav):
     wav = np.ascontiguousarray(wav, dtype=np.float32)
     s, l, cnt = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int64()
-    _capi.check(_capi.lib().mx_grains(_ptr(wav), len(wav), C.byref(s), C.byref(l), C.byref(cnt)))
-    return _take_i32(s, cnt.value), _take_i32(l, cnt.value)
+    _call("mx_grains", _ptr(wav), len(wav), C.byref(s), C.byref(l), C.byref(cnt))
+    return _take_array(s, cnt.value), _take_array(l, cnt.value)
+
+
+def _schedule(name: str, head, starts, lens, firsts, markers, resume=None):
+    """The schedule builder `name`(*head, starts, lens, [firsts,] count, markers, count, [cursor0, need,] &steps, &nsteps,
+    &nsamples, [&cursor_end]) -> (steps, nsamples), with resume = (cursor0, need) (steps, nsamples, cursor_end)."""
+    starts = np.ascontiguousarray(starts, dtype=np.int32)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    grains = (_ptr(starts), _ptr(lens)) if firsts is None else (_ptr(starts), _ptr(lens), _ptr(firsts))
+    m = _capi.markers_array(markers)
+    p, ns, tot, end = C.POINTER(_capi.Step)(), C.c_int64(), C.c_int64(), C.c_double()
+    outs = (C.byref(p), C.byref(ns), C.byref(tot))
+    if resume is None:
+        _call(name, *head, *grains, len(starts), m, len(markers), *outs)
+        return _take_steps(p, ns.value), tot.value
+    _call(name, *head, *grains, len(starts), m, len(markers), float(resume[0]), int(resume[1]), *outs, C.byref(end))
+    return _take_steps(p, ns.value), tot.value, end.value
 
 
 def schedule_build(wav, sr: int, starts, lens, markers):
     """-> (steps structured array, nsamples)"""
     wav = np.ascontiguousarray(wav, dtype=np.float32)
-    starts = np.ascontiguousarray(starts, dtype=np.int32)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    m = _capi.markers_array(markers)
-    p, ns, tot = C.POINTER(_capi.Step)(), C.c_int64(), C.c_int64()
-    _capi.check(_capi.lib().mx_schedule_build(_ptr(wav), len(wav), sr, _ptr(starts), _ptr(lens), len(starts), m,
-                                              len(markers), C.byref(p), C.byref(ns), C.byref(tot)))
-    return _take_steps(p, ns.value), tot.value
+    return _schedule("mx_schedule_build", (_ptr(wav), len(wav), sr), starts, lens, None, markers)
 
 
 def schedule_build_table(n: int, sr: int, starts, lens, firsts, markers, cursor0: float = 0.0, need: int = -1):
     """The export / refill schedule from a grain table (Context.grain_table_dev): no host copy of the audio needed.
     -> (steps, nsamples, cursor_end)"""
-    starts = np.ascontiguousarray(starts, dtype=np.int32)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
     firsts = np.ascontiguousarray(firsts, dtype=np.float32)
-    m = _capi.markers_array(markers)
-    p, ns, tot, end = C.POINTER(_capi.Step)(), C.c_int64(), C.c_int64(), C.c_double()
-    _capi.check(_capi.lib().mx_schedule_build_table(int(n), sr, _ptr(starts), _ptr(lens), _ptr(firsts), len(starts), m,
-                                                    len(markers), float(cursor0), int(need), C.byref(p), C.byref(ns),
-                                                    C.byref(tot), C.byref(end)))
-    return _take_steps(p, ns.value), tot.value, end.value
+    return _schedule("mx_schedule_build_table", (int(n), sr), starts, lens, firsts, markers, (cursor0, need))
 
 
 def schedule_build_from(wav, sr: int, starts, lens, markers, cursor0: float, need: int):
     """App::playback's refill loop from warped time cursor0 -> (steps, nsamples, cursor_end)."""
     wav = np.ascontiguousarray(wav, dtype=np.float32)
-    starts = np.ascontiguousarray(starts, dtype=np.int32)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    m = _capi.markers_array(markers)
-    p, ns, tot, end = C.POINTER(_capi.Step)(), C.c_int64(), C.c_int64(), C.c_double()
-    _capi.check(_capi.lib().mx_schedule_build_from(_ptr(wav), len(wav), sr, _ptr(starts), _ptr(lens), len(starts), m,
-                                                   len(markers), float(cursor0), int(need), C.byref(p), C.byref(ns),
-                                                   C.byref(tot), C.byref(end)))
-    return _take_steps(p, ns.value), tot.value, end.value
+    return _schedule("mx_schedule_build_from", (_ptr(wav), len(wav), sr), starts, lens, None, markers, (cursor0, need))
 
 
 def save_wav(path, pcm16, sr: int, strict: bool = True):
     pcm16 = np.ascontiguousarray(pcm16, dtype=np.int16)
-    _capi.check(_capi.lib().mx_save_wav(str(path).encode(), _ptr(pcm16), len(pcm16), sr, 1 if strict else 0))
+    _call("mx_save_wav", str(path).encode(), _ptr(pcm16), len(pcm16), sr, 1 if strict else 0)
 
 
 def minmax_range(wav, levels, start, end):
@@ -960,9 +893,9 @@ def detect_notes(track, sr: int, hop: int, first: int = 0, **params):
     """Notes of an F0_DTYPE track (track[0] = frame `first`) -> NOTE_DTYPE array.  params: threshold, rms_floor, max_jump,
     max_dev, min_frames (defaults: note_params_default())."""
     track = np.ascontiguousarray(track, dtype=F0_DTYPE)
-    out, cnt = C.POINTER(_capi.Note)(), C.c_int64()
-    _capi.check(_capi.lib().mx_detect_notes(_ptr(track) if len(track) else None, len(track), sr, hop, first,
-                                            _params_arg("note", params, never_null=True), C.byref(out), C.byref(cnt)))
+    out, cnt = C.POINTER(_capi.Note)(), C.c_int64()  # (a typed pointer in this entry point's signature: not _handed)
+    _call("mx_detect_notes", _opt(track), len(track), sr, hop, first, _params_arg("note", params, never_null=True), C.byref(out),
+          C.byref(cnt))
     return _take_records(C.cast(out, C.c_void_p), cnt.value, NOTE_DTYPE)  # (no notes: a null array)
 
 
@@ -970,8 +903,7 @@ def correction_markers(notes, strength: float = 1.0, scale_mask: int = 0):
     """Two markers per note (MARKER_DTYPE): {start, note, 0, b}, {end, note, 0, b}, b = strength * (target - note)."""
     notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
     out = np.zeros(2 * len(notes), dtype=MARKER_DTYPE)
-    _capi.check(_capi.lib().mx_correction_markers(_ptr(notes) if len(notes) else None, len(notes), float(strength),
-                                                  int(scale_mask), _ptr(out) if len(out) else None))
+    _call("mx_correction_markers", _opt(notes), len(notes), float(strength), int(scale_mask), _opt(out))
     return out
 
 
@@ -979,14 +911,13 @@ def correction_markers_tuned(notes, strength: float = 1.0, scale_mask: int = 0, 
     """correction_markers on a grid `tuning_cents` above A = 440 Hz (key_detect's or key_from_notes' tuning_cents)."""
     notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
     out = np.zeros(2 * len(notes), dtype=MARKER_DTYPE)
-    _capi.check(_capi.lib().mx_correction_markers_tuned(_ptr(notes) if len(notes) else None, len(notes), float(strength),
-                                                        int(scale_mask), float(tuning_cents), _ptr(out) if len(out) else None))
+    _call("mx_correction_markers_tuned", _opt(notes), len(notes), float(strength), int(scale_mask), float(tuning_cents), _opt(out))
     return out
 
 
 # ---- key, scale and tuning (host; build-defined) ----
 def _key_dict(key) -> dict:
-    return {k: getattr(key, k) for k, _ in _capi.Key._fields_ if k != "reserved"}
+    return {k: v for k, v in _fields(key).items() if k != "reserved"}
 
 
 def key_from_chroma(sum40) -> dict:
@@ -995,7 +926,7 @@ def key_from_chroma(sum40) -> dict:
     if s.shape != (CHROMA_COLS,):
         raise ValueError("a chroma sum is 40 values")
     key = _capi.Key()
-    _capi.check(_capi.lib().mx_key_from_chroma(_ptr(s), C.byref(key)))
+    _call("mx_key_from_chroma", _ptr(s), C.byref(key))
     return _key_dict(key)
 
 
@@ -1003,58 +934,24 @@ def key_from_notes(notes) -> dict:
     """The key estimate from detect_notes' output (NOTE_DTYPE), each note weighing its frames."""
     notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
     key = _capi.Key()
-    _capi.check(_capi.lib().mx_key_from_notes(_ptr(notes) if len(notes) else None, len(notes), C.byref(key)))
+    _call("mx_key_from_notes", _opt(notes), len(notes), C.byref(key))
     return _key_dict(key)
 
 
 # ---- PSOLA planning (host; build-defined) ----
 def _formant_points(points):
     """(sample, semitones) pairs, or a FORMANT_POINT_DTYPE array -> a contiguous FORMANT_POINT_DTYPE array."""
-    if isinstance(points, np.ndarray) and points.dtype == FORMANT_POINT_DTYPE:
-        return np.ascontiguousarray(points)
-    out = np.zeros(len(points), dtype=FORMANT_POINT_DTYPE)
-    for i, (s, st) in enumerate(points):
-        out[i] = (int(s), np.float32(st))
-    return out
+    return _records(points, FORMANT_POINT_DTYPE)
 
 
 # the two record kinds, by `formant`: the entry points' suffix and the record dtype
 _PSOLA_KINDS = {False: ("", PSOLA_GRAIN_DTYPE), True: ("_formant", PSOLA_FGRAIN_DTYPE)}
 
 
-def _psola_kind(formant: bool, points):
-    """-> (suffix, dtype, the formant entry point's points as a FORMANT_POINT_DTYPE array, or None for the plain kind, which
-    takes no points).  The kind alone picks symbol and dtype: whatever `points` is, the two cannot disagree.  The caller
-    holds the array across the C call and makes the arguments of it there (_points_args)."""
-    return (*_PSOLA_KINDS[formant], _formant_points(points) if formant else None)
-
-
 def _points_args(pts):
-    """The two extra arguments of a formant entry point, (points | NULL, count); () for None.  pts must outlive the call."""
-    return () if pts is None else (_ptr(pts) if len(pts) else None, len(pts))
-
-
-def _psola_plan(formant: bool, n: int, sr: int, hop: int, track, markers, points, params: dict):
-    track = np.ascontiguousarray(track, dtype=F0_DTYPE)
-    m = _capi.markers_array(markers)
-    sfx, dtype, pts = _psola_kind(formant, points)
-    out, cnt, ns = C.c_void_p(), C.c_int64(), C.c_int64()
-    _capi.check(getattr(_capi.lib(), "mx_psola_plan" + sfx)(n, sr, hop, _ptr(track) if len(track) else None, len(track),
-                                                            _params_arg("psola", params), m, len(markers), *_points_args(pts),
-                                                            C.byref(out), C.byref(cnt), C.byref(ns)))
-    return _take_records(out, cnt.value, dtype), ns.value
-
-
-def psola_plan(n: int, sr: int, hop: int, track, markers, **params):
-    """Grain records of a PSOLA render -> (PSOLA_GRAIN_DTYPE array, nsamples).  track: the F0_DTYPE records of the file's
-    frame_count(n, hop) frames; params: fields of psola_params_default()."""
-    return _psola_plan(False, n, sr, hop, track, markers, None, params)
-
-
-def psola_plan_formant(n: int, sr: int, hop: int, track, markers, points, **params):
-    """psola_plan with a formant curve -> (PSOLA_FGRAIN_DTYPE array, nsamples).  points: (source sample, semitones) pairs,
-    samples strictly increasing; none: every record's step is 65536."""
-    return _psola_plan(True, n, sr, hop, track, markers, points, params)
+    """The two extra arguments of an entry point that takes a formant curve, (points | NULL, count); () for None.  pts must
+    outlive the call."""
+    return () if pts is None else (_opt(pts), len(pts))
 
 
 def _bend_arg(bend, count: int):
@@ -1066,26 +963,40 @@ def _bend_arg(bend, count: int):
     return bend
 
 
+def _psola_plan(formant: bool, bent: bool, n: int, sr: int, hop: int, track, markers, points, bend, params: dict):
+    """mx_psola_plan, mx_psola_plan_formant, mx_psola_plan_bend or mx_psola_plan_formant_bend.  The kind alone picks symbol,
+    dtype and whether points are passed: whatever `points` is, they cannot disagree."""
+    track = np.ascontiguousarray(track, dtype=F0_DTYPE)
+    m = _capi.markers_array(markers)
+    sfx, dtype = _PSOLA_KINDS[formant]
+    pts = _formant_points(points) if formant else None
+    b = _bend_arg(bend, len(track)) if bent else None  # (held here: it must outlive the call, like pts)
+    ns = C.c_int64()
+    grains = _handed(dtype, "mx_psola_plan" + sfx + ("_bend" if bent else ""), n, sr, hop, _opt(track), len(track),
+                     _params_arg("psola", params), m, len(markers), *_points_args(pts), *((_ptr(b),) if bent else ()), tail=(C.byref(ns),))
+    return grains, ns.value
+
+
+def psola_plan(n: int, sr: int, hop: int, track, markers, **params):
+    """Grain records of a PSOLA render -> (PSOLA_GRAIN_DTYPE array, nsamples).  track: the F0_DTYPE records of the file's
+    frame_count(n, hop) frames; params: fields of psola_params_default()."""
+    return _psola_plan(False, False, n, sr, hop, track, markers, None, None, params)
+
+
+def psola_plan_formant(n: int, sr: int, hop: int, track, markers, points, **params):
+    """psola_plan with a formant curve -> (PSOLA_FGRAIN_DTYPE array, nsamples).  points: (source sample, semitones) pairs,
+    samples strictly increasing; none: every record's step is 65536."""
+    return _psola_plan(True, False, n, sr, hop, track, markers, points, None, params)
+
+
 def psola_plan_bend(n: int, sr: int, hop: int, track, markers, bend, **params):
     """psola_plan following a bend curve (float32 semitones, one per frame of the track; None: psola_plan itself)."""
-    return _psola_plan_bend(False, n, sr, hop, track, markers, None, bend, params)
+    return _psola_plan(False, True, n, sr, hop, track, markers, None, bend, params)
 
 
 def psola_plan_formant_bend(n: int, sr: int, hop: int, track, markers, points, bend, **params):
     """psola_plan_formant following a bend curve."""
-    return _psola_plan_bend(True, n, sr, hop, track, markers, points, bend, params)
-
-
-def _psola_plan_bend(formant: bool, n: int, sr: int, hop: int, track, markers, points, bend, params: dict):
-    track = np.ascontiguousarray(track, dtype=F0_DTYPE)
-    m = _capi.markers_array(markers)
-    sfx, dtype, pts = _psola_kind(formant, points)
-    b = _bend_arg(bend, len(track))
-    out, cnt, ns = C.c_void_p(), C.c_int64(), C.c_int64()
-    _capi.check(getattr(_capi.lib(), f"mx_psola_plan{sfx}_bend")(n, sr, hop, _ptr(track) if len(track) else None, len(track),
-                                                                  _params_arg("psola", params), m, len(markers), *_points_args(pts),
-                                                                  _ptr(b), C.byref(out), C.byref(cnt), C.byref(ns)))
-    return _take_records(out, cnt.value, dtype), ns.value
+    return _psola_plan(True, True, n, sr, hop, track, markers, points, bend, params)
 
 
 # ---- pitch drift and vibrato inside notes (host; build-defined) ----
@@ -1093,7 +1004,7 @@ def contour_spans(notes, first: int = 0):
     """The spans of detect_notes' output relative to a track whose record 0 is frame `first` -> CONTOUR_SPAN_DTYPE array."""
     notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
     out = np.zeros(len(notes), dtype=CONTOUR_SPAN_DTYPE)
-    _capi.check(_capi.lib().mx_contour_spans(_ptr(notes) if len(notes) else None, len(notes), first, _ptr(out) if len(out) else None))
+    _call("mx_contour_spans", _opt(notes), len(notes), first, _opt(out))
     return out
 
 
@@ -1101,8 +1012,8 @@ def contour_vibrato(stat, frames: int, sr: int, hop: int) -> dict:
     """rate_hz, extent_cents, strength, drift_cents of one CONTOUR_STAT_DTYPE record of a span of `frames` frames."""
     s = np.ascontiguousarray(np.asarray(stat, dtype=CONTOUR_STAT_DTYPE).reshape(1))
     v = _capi.Vibrato()
-    _capi.check(_capi.lib().mx_contour_vibrato(_ptr(s), int(frames), sr, hop, C.byref(v)))
-    return {k: getattr(v, k) for k, _ in _capi.Vibrato._fields_}
+    _call("mx_contour_vibrato", _ptr(s), int(frames), sr, hop, C.byref(v))
+    return _fields(v)
 
 
 def contour_bend(rec, notes, spans, shift=None, **params):
@@ -1117,9 +1028,8 @@ def contour_bend(rec, notes, spans, shift=None, **params):
     if sh is not None and len(sh) != len(notes):
         raise ValueError("one shift per note")
     out = np.zeros(len(rec), dtype=np.float32)
-    _capi.check(_capi.lib().mx_contour_bend(_ptr(rec) if len(rec) else None, len(rec), _ptr(notes) if len(notes) else None,
-                                            _ptr(spans) if len(spans) else None, len(notes), _ptr(sh),
-                                            _params_arg("bend", params), _ptr(out) if len(out) else None))
+    _call("mx_contour_bend", _opt(rec), len(rec), _opt(notes), _opt(spans), len(notes), _ptr(sh), _params_arg("bend", params),
+          _opt(out))
     return out
 
 
@@ -1128,70 +1038,34 @@ def onset_pick(flux, hop: int, first: int = 0, **params):
     """Onsets of an onset-strength curve (flux[0] = frame `first`) -> ONSET_DTYPE array.  params: fields of
     onset_pick_params_default()."""
     flux = np.ascontiguousarray(flux, dtype=np.float32)
-    out, cnt = C.c_void_p(), C.c_int64()
-    _capi.check(_capi.lib().mx_onset_pick(_ptr(flux) if len(flux) else None, len(flux), hop, first, _params_arg("pick", params),
-                                          C.byref(out), C.byref(cnt)))
-    return _take_records(out, cnt.value, ONSET_DTYPE)
+    return _handed(ONSET_DTYPE, "mx_onset_pick", _opt(flux), len(flux), hop, first, _params_arg("pick", params))
 
 
 def timing_markers(anchors, n: int, sr: int, base=None, **params):
     """The markers that move `anchors` (source samples) onto the tempo grid -> MARKER_DTYPE array.  base: a MARKER_DTYPE
     array (correction_markers) or (sample, note, dTime, pitchBend) tuples to merge; params: fields of timing_params_default()."""
     anchors = np.ascontiguousarray(anchors, dtype=np.int32)
-    if base is None:
-        base = np.zeros(0, dtype=MARKER_DTYPE)
-    elif not (isinstance(base, np.ndarray) and base.dtype == MARKER_DTYPE):
-        b = np.zeros(len(base), dtype=MARKER_DTYPE)
-        for i, m in enumerate(base):
-            b[i] = (int(m[0]), float(m[1]), float(m[2]), float(m[3]))
-        base = b
-    base = np.ascontiguousarray(base)
-    out, cnt = C.c_void_p(), C.c_int64()
-    _capi.check(_capi.lib().mx_timing_markers(_ptr(anchors) if len(anchors) else None, len(anchors), int(n), sr,
-                                              _params_arg("timing", params),
-                                              _ptr(base) if len(base) else None, len(base), C.byref(out), C.byref(cnt)))
-    return _take_records(out, cnt.value, MARKER_DTYPE)
+    base = _records(() if base is None else base, MARKER_DTYPE)
+    return _handed(MARKER_DTYPE, "mx_timing_markers", _opt(anchors), len(anchors), int(n), sr, _params_arg("timing", params),
+                   _opt(base), len(base))
 
 
 # ---- sibilant segments, protected formant curves, balance points (host; build-defined) ----
-def _records(items, dtype):
-    """Tuples, or an array of `dtype` -> a contiguous array of `dtype`."""
-    if isinstance(items, np.ndarray) and items.dtype == dtype:
-        return np.ascontiguousarray(items)
-    out = np.zeros(len(items), dtype=dtype)
-    for i, it in enumerate(items):
-        out[i] = tuple(it)
-    return out
-
-
-def _gain_points(points):
-    return _records(points, GAIN_POINT_DTYPE)
-
-
 def sibilants(feat, hop: int = 256, first: int = 0, **params):
     """Segments of SIB_FEAT_DTYPE records (feat[0] = frame `first`) -> SIBILANT_DTYPE array.  params: fields of
     sibilant_params_default()."""
     feat = _records(feat, SIB_FEAT_DTYPE)
-    out, cnt = C.c_void_p(), C.c_int64()
-    _capi.check(_capi.lib().mx_sibilants(_ptr(feat) if len(feat) else None, len(feat), hop, first, _params_arg("sibilant", params),
-                                         C.byref(out), C.byref(cnt)))
-    return _take_records(out, cnt.value, SIBILANT_DTYPE)
+    return _handed(SIBILANT_DTYPE, "mx_sibilants", _opt(feat), len(feat), hop, first, _params_arg("sibilant", params))
 
 
 def formant_protect(points, sibs, ramp: int, n: int):
     """A formant curve ((sample, semitones) pairs) held at 0 st across `sibs` (SIBILANT_DTYPE), `ramp` samples of linear
     return either side -> FORMANT_POINT_DTYPE array that psola_plan_formant takes as it is."""
     pts, sibs = _formant_points(points), _records(sibs, SIBILANT_DTYPE)
-    out, cnt = C.c_void_p(), C.c_int64()
-    _capi.check(_capi.lib().mx_formant_protect(_ptr(pts) if len(pts) else None, len(pts), _ptr(sibs) if len(sibs) else None, len(sibs),
-                                               int(ramp), int(n), C.byref(out), C.byref(cnt)))
-    return _take_records(out, cnt.value, FORMANT_POINT_DTYPE)
+    return _handed(FORMANT_POINT_DTYPE, "mx_formant_protect", _opt(pts), len(pts), _opt(sibs), len(sibs), int(ramp), int(n))
 
 
 def sibilant_gain_points(sibs, db: float, ramp: int, n: int):
     """The gain points of a sibilant balance of `db` decibels -> GAIN_POINT_DTYPE array for Context.audio_gain."""
     sibs = _records(sibs, SIBILANT_DTYPE)
-    out, cnt = C.c_void_p(), C.c_int64()
-    _capi.check(_capi.lib().mx_sibilant_gain_points(_ptr(sibs) if len(sibs) else None, len(sibs), float(db), int(ramp), int(n),
-                                                    C.byref(out), C.byref(cnt)))
-    return _take_records(out, cnt.value, GAIN_POINT_DTYPE)
+    return _handed(GAIN_POINT_DTYPE, "mx_sibilant_gain_points", _opt(sibs), len(sibs), float(db), int(ramp), int(n))

@@ -169,6 +169,10 @@ class ContourParams(C.Structure):
     _fields_ = [("half_width", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32)]
 
 
+class ContourRec(C.Structure):
+    _fields_ = [("smooth", C.c_int32), ("vib", C.c_int32)]
+
+
 class ContourStat(C.Structure):
     _fields_ = [("sum_smooth", C.c_int64), ("min_smooth", C.c_int32), ("max_smooth", C.c_int32), ("r0", C.c_int64),
                 ("lag", C.c_int32), ("reserved", C.c_int32), ("r_lag", C.c_int64)]
@@ -182,53 +186,34 @@ class BendParams(C.Structure):
     _fields_ = [("drift_amount", C.c_double), ("vibrato_scale", C.c_double), ("glide_frames", C.c_int32)]
 
 
-PITCH_DTYPE = np.dtype([("bin", "<i4"), ("mag", "<f4")])
-STEP_DTYPE = np.dtype([("cursor", "<f8"), ("grain_start", "<i4"), ("grain_len", "<i4"), ("rate", "<f4"),
-                       ("next_first", "<f4"), ("sz", "<i4"), ("_pad", "<i4"), ("out_offset", "<i8")])
-F0_DTYPE = np.dtype([("tau", "<i4"), ("period", "<f4"), ("aperiodicity", "<f4"), ("rms", "<f4")])
+# the C type of every record class, in the order of include/melonix_amd.h.  A record is declared here once, as its class: the
+# field names are the header's, the numpy dtypes below are derived from the classes, and tests/test_abi.py compares every
+# class's size, field offsets and field sizes with what a C compiler makes of the header.  (mx_chroma_rec has no class: a
+# chroma record is a row of CHROMA_COLS floats.)
+RECORDS = {
+    "mx_pitch": Pitch, "mx_marker": Marker, "mx_step": Step, "mx_f0": F0, "mx_f0_cand": F0Cand,
+    "mx_f0_decode_params": F0DecodeParams, "mx_note_params": NoteParams, "mx_note": Note, "mx_psola_params": PsolaParams,
+    "mx_psola_grain": PsolaGrain, "mx_formant_point": FormantPoint, "mx_psola_fgrain": PsolaFGrain,
+    "mx_onset_flux_params": OnsetFluxParams, "mx_onset_pick_params": OnsetPickParams, "mx_onset": Onset,
+    "mx_timing_params": TimingParams, "mx_comb_job": CombJob, "mx_comb": Comb, "mx_tempo_params": TempoParams, "mx_tempo": Tempo,
+    "mx_tempo_window": TempoWindow, "mx_sib_feat": SibFeat, "mx_sib_feature_params": SibFeatureParams,
+    "mx_sibilant_params": SibilantParams, "mx_sibilant": Sibilant, "mx_gain_point": GainPoint, "mx_chroma_rec": None,
+    "mx_chroma_params": ChromaParams, "mx_chroma_job": ChromaJob, "mx_key": Key, "mx_key_window": KeyWindow,
+    "mx_contour_span": ContourSpan, "mx_contour_params": ContourParams, "mx_contour_rec": ContourRec,
+    "mx_contour_stat": ContourStat, "mx_vibrato": Vibrato, "mx_bend_params": BendParams,
+}
+
+PITCH_DTYPE, STEP_DTYPE, MARKER_DTYPE = np.dtype(Pitch), np.dtype(Step), np.dtype(Marker)
+F0_DTYPE, F0_CAND_DTYPE, NOTE_DTYPE = np.dtype(F0), np.dtype(F0Cand), np.dtype(Note)
 F0_CANDS = 4
-F0_CAND_DTYPE = np.dtype([("tau", "<i4"), ("period", "<f4"), ("aperiodicity", "<f4"), ("cents", "<i4")])
-NOTE_DTYPE = np.dtype([("start_sample", "<i4"), ("end_sample", "<i4"), ("first_frame", "<i4"), ("frames", "<i4"),
-                       ("note", "<f8"), ("aperiodicity", "<f4"), ("spread", "<f4")])
-MARKER_DTYPE = np.dtype({"names": ["sample", "note", "dTime", "pitchBend"], "formats": ["<i4", "<f8", "<f8", "<f8"],
-                         "offsets": [0, 8, 16, 24], "itemsize": 32})
-PSOLA_GRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_off", "<i4"), ("src_frac", "<f4"), ("centre", "<i4"),
-                              ("centre_frac", "<f4"), ("inv_half", "<f4"), ("mark", "<i4")])
-assert PSOLA_GRAIN_DTYPE.itemsize == C.sizeof(PsolaGrain) == 32
-FORMANT_POINT_DTYPE = np.dtype([("sample", "<i4"), ("semitones", "<f4")])
-PSOLA_FGRAIN_DTYPE = np.dtype([("out_lo", "<i4"), ("out_hi", "<i4"), ("src_idx", "<i4"), ("src_q", "<u4"), ("centre", "<i4"),
-                               ("centre_frac", "<f4"), ("inv_half", "<f4"), ("step", "<u4")])
-assert PSOLA_FGRAIN_DTYPE.itemsize == C.sizeof(PsolaFGrain) == 32 and FORMANT_POINT_DTYPE.itemsize == C.sizeof(FormantPoint) == 8
-ONSET_DTYPE = np.dtype([("sample", "<i4"), ("frame", "<i4"), ("strength", "<f4"), ("margin", "<f4")])
-assert ONSET_DTYPE.itemsize == C.sizeof(Onset) == 16 and C.sizeof(OnsetPickParams) == 40 and C.sizeof(TimingParams) == 48
-COMB_JOB_DTYPE = np.dtype([("first", "<i4"), ("frames", "<i4"), ("period_q16", "<u4")])
-COMB_DTYPE = np.dtype([("score", "<f4"), ("phase", "<i4"), ("prev", "<f4"), ("next", "<f4")])
-TEMPO_WINDOW_DTYPE = np.dtype([("first_frame", "<i4"), ("frames", "<i4"), ("bpm", "<f4"), ("score", "<f4")])
-assert COMB_JOB_DTYPE.itemsize == C.sizeof(CombJob) == 12 and COMB_DTYPE.itemsize == C.sizeof(Comb) == 16
-assert TEMPO_WINDOW_DTYPE.itemsize == C.sizeof(TempoWindow) == 16 and C.sizeof(TempoParams) == 56 and C.sizeof(Tempo) == 40
-SIB_FEAT_DTYPE = np.dtype([("low", "<f4"), ("high", "<f4"), ("centroid", "<f4"), ("zero_crossings", "<i4")])
-SIBILANT_DTYPE = np.dtype([("start_sample", "<i4"), ("end_sample", "<i4"), ("first_frame", "<i4"), ("frames", "<i4"),
-                           ("share", "<f4"), ("level", "<f4")])
-GAIN_POINT_DTYPE = np.dtype([("sample", "<i4"), ("amp", "<f4")])
-assert SIB_FEAT_DTYPE.itemsize == C.sizeof(SibFeat) == 16 and SIBILANT_DTYPE.itemsize == C.sizeof(Sibilant) == 24
-assert GAIN_POINT_DTYPE.itemsize == C.sizeof(GainPoint) == 8 and C.sizeof(SibilantParams) == 40
+PSOLA_GRAIN_DTYPE, FORMANT_POINT_DTYPE, PSOLA_FGRAIN_DTYPE = np.dtype(PsolaGrain), np.dtype(FormantPoint), np.dtype(PsolaFGrain)
+ONSET_DTYPE = np.dtype(Onset)
+COMB_JOB_DTYPE, COMB_DTYPE, TEMPO_WINDOW_DTYPE = np.dtype(CombJob), np.dtype(Comb), np.dtype(TempoWindow)
+SIB_FEAT_DTYPE, SIBILANT_DTYPE, GAIN_POINT_DTYPE = np.dtype(SibFeat), np.dtype(Sibilant), np.dtype(GainPoint)
 CHROMA_COLS = 40  # a chroma record: 36 profile bins, the tuning phasor, the summed weight, the number of peaks
-CHROMA_JOB_DTYPE = np.dtype([("first_frame", "<i8"), ("frames", "<i8")])
-KEY_DTYPE = np.dtype([("tonic", "<i4"), ("mode", "<i4"), ("scale_mask", "<i4"), ("reserved", "<i4"), ("tuning_cents", "<f8"),
-                      ("tuning_confidence", "<f8"), ("correlation", "<f8"), ("clarity", "<f8")])
-KEY_WINDOW_DTYPE = np.dtype([("first_frame", "<i4"), ("frames", "<i4"), ("key", KEY_DTYPE)])
-assert CHROMA_JOB_DTYPE.itemsize == C.sizeof(ChromaJob) == 16 and C.sizeof(ChromaParams) == 16
-assert KEY_DTYPE.itemsize == C.sizeof(Key) == 48 and KEY_WINDOW_DTYPE.itemsize == C.sizeof(KeyWindow) == 56
+CHROMA_JOB_DTYPE, KEY_DTYPE, KEY_WINDOW_DTYPE = np.dtype(ChromaJob), np.dtype(Key), np.dtype(KeyWindow)
 CONTOUR_NONE = -2 ** 31  # MX_CONTOUR_NONE: an unvoiced frame's cents, the smooth value outside every span
-CONTOUR_SPAN_DTYPE = np.dtype([("first", "<i4"), ("frames", "<i4")])
-CONTOUR_REC_DTYPE = np.dtype([("smooth", "<i4"), ("vib", "<i4")])
-CONTOUR_STAT_DTYPE = np.dtype([("sum_smooth", "<i8"), ("min_smooth", "<i4"), ("max_smooth", "<i4"), ("r0", "<i8"), ("lag", "<i4"),
-                               ("reserved", "<i4"), ("r_lag", "<i8")])
-assert CONTOUR_SPAN_DTYPE.itemsize == C.sizeof(ContourSpan) == 8 and CONTOUR_STAT_DTYPE.itemsize == C.sizeof(ContourStat) == 40
-assert C.sizeof(ContourParams) == 12 and C.sizeof(Vibrato) == 32 and C.sizeof(BendParams) == 24
-assert PITCH_DTYPE.itemsize == C.sizeof(Pitch) and STEP_DTYPE.itemsize == C.sizeof(Step)
-assert F0_DTYPE.itemsize == C.sizeof(F0) == 16 and NOTE_DTYPE.itemsize == C.sizeof(Note) == 32
-assert MARKER_DTYPE.itemsize == C.sizeof(Marker) and F0_CAND_DTYPE.itemsize == C.sizeof(F0Cand) == 16
+CONTOUR_SPAN_DTYPE, CONTOUR_REC_DTYPE, CONTOUR_STAT_DTYPE = np.dtype(ContourSpan), np.dtype(ContourRec), np.dtype(ContourStat)
 
 # name -> (restype, argtypes); kept in the order of include/melonix_amd.h
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -453,8 +438,20 @@ def check(rc: int) -> None:
         raise MxError(rc, (lib().mx_last_error() or b"").decode(errors="replace"))
 
 
+def records(items, dtype):
+    """Tuples, or an array of `dtype` -> a contiguous array of `dtype`; each value is cast to its field's type.  The one
+    conversion from tuples to records."""
+    if isinstance(items, np.ndarray) and items.dtype == dtype:
+        return np.ascontiguousarray(items)
+    out = np.zeros(len(items), dtype=dtype)
+    for i, it in enumerate(items):
+        out[i] = tuple(it)
+    return out
+
+
 def markers_array(markers):
-    arr = (Marker * max(1, len(markers)))()
-    for i, m in enumerate(markers):
-        arr[i] = Marker(int(m[0]), float(m[1]), float(m[2]), float(m[3]))
+    """(sample, note, dTime, pitchBend) tuples -> a ctypes array of at least one Marker (never a null pointer), padding zero."""
+    rec = records(markers, MARKER_DTYPE)
+    arr = (Marker * max(1, len(rec)))()
+    C.memmove(arr, rec.ctypes.data, rec.nbytes)
     return arr

@@ -26,6 +26,33 @@ def test_header_compiles_as_c_and_cpp(tmp_path):
         assert subprocess.call([str(exe)]) == 0
 
 
+def test_record_layouts_are_the_headers(tmp_path):
+    """Every record class of _capi.RECORDS against what a C compiler makes of include/melonix_amd.h: the size of the type,
+    and the offset and size of every field, by name.  RECORDS names every `typedef struct { ... }` of the header."""
+    from melonix_amd import _capi
+
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert sorted(_capi.RECORDS) == sorted(re.findall(r"\btypedef\s+struct\s+(mx_[a-z0-9_]+)\s*\{", src))
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "melonix_amd.h"', 'int main(void) {']
+    for ctype, cls in _capi.RECORDS.items():
+        lines.append(f'  printf("{ctype} %zu\\n", sizeof({ctype}));')
+        for name, _ in cls._fields_ if cls else ():
+            lines.append(f'  printf("{ctype}.{name} %zu %zu\\n", offsetof({ctype}, {name}), sizeof((({ctype} *)0)->{name}));')
+    lines += ['  return 0;', '}']
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
+                           str(tmp_path / "layout.c"), "-o", str(exe)])
+    header = {k: tuple(int(x) for x in v.split()) for k, v in
+              (line.split(" ", 1) for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    python = {}
+    for ctype, cls in _capi.RECORDS.items():
+        python[ctype] = (C.sizeof(cls) if cls else 4 * _capi.CHROMA_COLS,)  # (a chroma record: a row of CHROMA_COLS floats)
+        for name, _ in cls._fields_ if cls else ():
+            python[f"{ctype}.{name}"] = (getattr(cls, name).offset, getattr(cls, name).size)
+    assert len(header) > 150 and python == header, sorted(set(python.items()) ^ set(header.items()))
+
+
 def test_every_declared_symbol_is_exported(mxlib):
     from melonix_amd import _capi
     names = _declared()
