@@ -240,7 +240,18 @@ int mx_schedule_build_table(int64_t n, int sampleRate, const int32_t *grain_star
                             double *cursor_end);
 void mx_free(void *p);
 
-/* Gather-lerp resampler + float->int16 (app.cpp:332-343, 1209-1212) over a
+/* PCM conversions.  The two float -> int16 conversions of the library, each defined for EVERY binary32 value
+ * (melonix_amd/csrc/pcm16.h writes them once, for the device and the host):
+ *   reference form  mx_resynth, mx_resynth_dev, mx_resynth_to_wav, mx_export_wav: what the compiled reference's
+ *                   static_cast<int16_t>(v * 32767.) (app.cpp:1212) gives.  With d = (double)v * 32767.:
+ *                     |d| < 2^31 (that is |v| <= 65538)   the low 16 bits of trunc(d), as a two's-complement int16
+ *                                                         (1.5 -> -16386, 2 -> -2, 65537 -> 32767, 65538 -> -2);
+ *                     otherwise, +-Inf and NaN included   0.
+ *   clamped form    the phase vocoder and PSOLA, its formant and contour renders included:
+ *                     NaN -> 0;  otherwise (int16)(clamp(v, -1, 1) * 32767.), the product in binary64, truncated toward
+ *                     zero.  So +-Inf -> +-32767.
+ *
+ * Gather-lerp resampler + float->int16 (app.cpp:332-343, 1209-1212; the reference form above) over a
  * precomputed schedule.  pcm_f32_out / pcm_i16_out: nsamples each (host, either
  * may be NULL).  Bit-exact vs the reference arithmetic (no FMA contraction). */
 int mx_resynth(mx_ctx *ctx, const mx_audio *a, const mx_step *steps, int64_t nsteps,
@@ -273,8 +284,16 @@ int mx_export_wav(mx_ctx *ctx, const float *host_wav, int64_t n, int sampleRate,
  * synthesis windows, time-stretch by r = 2^(semitones/12) with integer phase propagation and identity phase
  * locking (spectral peaks carry the phase, every other bin rides on its nearest peak), overlap-add,
  * linear resampling by r back to the input length (definition: oracle/pv_oracle.py).  Constant shift over
- * the whole file; output has mx_audio_length(a) samples.  int16 = (int16)(clamp(v,-1,1) * 32767.).
- * Parity is unpinned by construction: the only oracle is the build's own CPU restatement. */
+ * the whole file; output has mx_audio_length(a) samples.  int16: the clamped form of "PCM conversions".
+ * Parity is unpinned by construction: the only oracle is the build's own CPU restatement.
+ * Samples that are not finite.  A frame that holds a NaN or an Inf sample — frame f holds the 4096 samples around a_f — has a
+ * spectrum without a finite peak to lock to, and the 4096 stretched samples it covers, [f Hs - N/2, f Hs + N/2), are not
+ * finite; so is every output either of whose two taps lies there (a NaN times a weight of 0 is NaN).  The recurrence only
+ * runs forward: every output before the first such one keeps the bytes it has without the bad sample.  Behind the last one
+ * every output is finite again; behind a NaN the first clean frame restarts every bin from its analysis phase (no bin of
+ * the frame before it is active: NaN >= threshold is false), exactly as the oracle does, and the usual tolerance holds
+ * from there on.  Chunked, sharded and device forms give the resident form's bytes, the NaNs' signs and payloads
+ * included: an overlap-add seam is summed left side + right side in every form.  int16 of such outputs: "PCM conversions". */
 int mx_pv_pitch_shift(mx_ctx *ctx, const mx_audio *a, double semitones, float *pcm_f32_out,
                       int16_t *pcm_i16_out);
 /* Same, outputs stay in HBM (either may be NULL); blocks until done.
@@ -392,7 +411,9 @@ void mx_minmax_range(const float *host_wav, int64_t n, const float *picks, const
  *   period = tau* + parabolic offset on d at tau*-1, tau*, tau*+1 (clamped to +-1/2, 0 if the curvature is <= 0).
  * A frame is silent exactly when its samples are all zero.  The level does not change tau, period or aperiodicity: the
  * kernel scales each frame by a power of two to a fixed binade first (records are bit for bit the same for 2^k x
- * wherever 2^k x is exact in f32, subnormal samples included), and rms scales with it.
+ * wherever 2^k x is exact in f32, subnormal samples included), and rms scales with it.  A frame that holds a NaN or an Inf
+ * sample is never voiced — its aperiodicity is not below the threshold —, its record is the same whatever the launch split,
+ * and every other frame keeps the bytes it has without the bad sample.
  * Defaults fmin = 55, fmax = 1760 Hz (notes 24..84), threshold 0.15.  Note law (mx_bin_note's):
  * note = 24 + 12*log2(sr / period / 55). */
 typedef struct mx_f0 {
@@ -540,7 +561,9 @@ int mx_correction_markers(const mx_note *notes, int64_t count, double strength, 
  *               u = ((float)(i - centre) - centre_frac) * inv_half, the grain skipped if |u| >= 1;
  *               w = 0.5 + 0.5 cos(pi u);  x = (1 - src_frac) * audio[i + src_off] + src_frac * audio[i + src_off + 1]
  *               (zeros outside the file; the resampler's form, no contraction);  S += w * x, W += w;
- *             y_i = W > 0 ? S / max(W, 0.25f) : 0;  int16 = (int16)(clamp(y, -1, 1) * 32767.) as in the phase vocoder.
+ *             y_i = W > 0 ? S / max(W, 0.25f) : 0;  int16: the clamped form of "PCM conversions", as in the phase vocoder.
+ *             A source sample that is NaN or Inf makes exactly the outputs not finite that read it as either tap of a
+ *             grain (whatever the weights); every other output keeps its bytes.
  *             Dividing by the window sum makes a zero-bend, identity-map render the input and keeps the level of a raised
  *             pitch; the floor lets the tails taper where a lowered pitch leaves gaps.  The order is fixed, so the result
  *             does not depend on how the kernel tiles the output. */

@@ -197,7 +197,7 @@ static int pv_shard_finish_core(mx_ctx *ctx, const float *prev_tail, const float
   if (!j.first) {
     // the rank's first N - Hs stretched samples: its head + the previous rank's tail, then their outputs
     PV_TRY(hipMemcpyAsync(p->prev_tail, prev_tail, kPvSeam * 4, hipMemcpyDefault, sm));
-    PV_TRY(launch_pv_edge_sum(p->edge_head, p->head_raw, p->prev_tail, kPvSeam, sm));
+    PV_TRY(launch_pv_edge_sum(p->edge_head, p->prev_tail, p->head_raw, kPvSeam, sm));  // left + right, as pv_fixup
     g.s = p->edge_head;
     g.s_origin = j.F_lo * kPvHs;
     g.out_lo = j.out_lo;

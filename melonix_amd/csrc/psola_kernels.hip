@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "pcm16.h"
 #include "psola_plan.h"
 
 #pragma clang fp contract(off)
@@ -54,11 +55,6 @@ __device__ __forceinline__ void psola_source(const mx_psola_fgrain &g, int i, in
   const unsigned t = g.src_q + g.step * ((unsigned)i - (unsigned)g.centre);
   idx = (int64_t)g.src_idx + (int64_t)((int)t >> 16);
   f = (float)(t & 65535u) * (1.f / 65536.f);
-}
-
-__device__ __forceinline__ int16_t psola_pcm16(float v) {
-  const float c = v < -1.f ? -1.f : (1.f < v ? 1.f : v);
-  return (int16_t)((double)c * 32767.);
 }
 
 template <class Rec>
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(kPsolaThreads) void psola_kernel(const PsolaArgsT<R
     if (i >= a.nsamples) continue;
     const float y = W[q] > 0.f ? S[q] / (W[q] > 0.25f ? W[q] : 0.25f) : 0.f;
     if (a.pcm_f32) a.pcm_f32[i] = y;
-    if (a.pcm_i16) a.pcm_i16[i] = psola_pcm16(y);
+    if (a.pcm_i16) a.pcm_i16[i] = pcm16_clamped(y);
   }
 }
 

@@ -1,5 +1,6 @@
 // pv_synthesis.hip — synthesis, boundary fix-up and resampling of the phase vocoder: pv_synthesis, pv_fixup, pv_resample,
 // pv_resample_frames, pv_edge_sum, and the launchers that compose the stages (the stages: pv_common.h).
+#include "pcm16.h"
 #include "pv_common.h"
 #include "wave_walk.h"
 
@@ -303,8 +304,9 @@ __global__ __launch_bounds__(256) void pv_fixup(const PvArgs a) {
       *reinterpret_cast<f32x4 *>(a.s + i) = *reinterpret_cast<const f32x4 *>(a.prev_final + i);
       return;
     }
+    // (left + right, the order of the interior boundaries below: of two NaN terms the sum keeps the first one's sign and payload)
     f32x4 v = *reinterpret_cast<const f32x4 *>(a.halo + i);
-    if (a.prev_tail) v += *reinterpret_cast<const f32x4 *>(a.prev_tail + i);
+    if (a.prev_tail) v = *reinterpret_cast<const f32x4 *>(a.prev_tail + i) + v;
     *reinterpret_cast<f32x4 *>(a.s + i) = v * kPvNorm;
     return;
   }
@@ -325,10 +327,6 @@ __host__ __device__ inline int64_t pv_resample_start(const PvArgs &a) {
   const int64_t e_lo = a.out_lo - a.pcm_base;  // element of pcm that receives output sample out_lo
   return e_lo - (int64_t)((uint64_t)(e_lo + shift) & 3u);
 }
-__device__ __forceinline__ int16_t pv_pcm16(float v) {
-  const float c = v < -1.f ? -1.f : (1.f < v ? 1.f : v);  // the reference's cast is UB beyond +-1 (app.cpp:1211)
-  return (int16_t)((double)c * 32767.);
-}
 __global__ __launch_bounds__(256) void pv_resample(const PvArgs a) {
   const int64_t e0 = pv_resample_start(a) + ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   const int64_t e_lo = a.out_lo - a.pcm_base, e_hi = a.out_hi - a.pcm_base;
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(256) void pv_resample(const PvArgs a) {
   }
   int16_t w[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) w[q] = pv_pcm16(v[q]);
+  for (int q = 0; q < 4; ++q) w[q] = pcm16_clamped(v[q]);
   const bool whole = e0 >= e_lo && e0 + 4 <= e_hi;
   if (a.pcm_f32) {
     float *o = a.pcm_f32 + e0;
@@ -385,11 +383,12 @@ __global__ __launch_bounds__(256) void pv_resample_frames(const PvArgs a) {
     const float tt = (float)(pos - fl);
     const float v = (1.0f - tt) * a.s[m] + tt * a.s[m + 1];
     if (a.pcm_f32) a.pcm_f32[i - a.pcm_base] = v;
-    if (a.pcm_i16) a.pcm_i16[i - a.pcm_base] = pv_pcm16(v);
+    if (a.pcm_i16) a.pcm_i16[i - a.pcm_base] = pcm16_clamped(v);
   }
 }
 
-// dst[i] = (a[i] + b[i]) * 1/sum w^2 — the two sides of an overlap-add seam, exactly as pv_fixup adds and normalises them
+// dst[i] = (x[i] + y[i]) * 1/sum w^2 — the two sides of an overlap-add seam, exactly as pv_fixup adds and normalises them: x the
+// left side's sums, y the right side's (the order matters where both are NaN: the sum keeps x's sign and payload)
 __global__ __launch_bounds__(256) void pv_edge_sum(float *dst, const float *x, const float *y, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "pcm16.h"
 
 #pragma clang fp contract(off)
 
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(kResynthThreads) void resynth_kernel(const ResynthA
     const float a1 = (idx + 1 < L) ? g[idx + 1] : next;
     const float v = (1.f - f) * a0 + f * a1;  // app.cpp:340-341, no contraction
     if (of) of[i] = v;
-    if (oi) oi[i] = (int16_t)((double)v * 32767.);  // app.cpp:1212: double multiply, truncation
+    if (oi) oi[i] = pcm16_reference(v);  // app.cpp:1212: double multiply, truncation (pcm16.h)
   }
 }
 
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(kResynthThreads) void resynth_kernel_v(const Resynt
       const float a1 = (idx + 1 < L) ? g[idx + 1] : st.next_first;
       const float v = (1.f - f) * g[idx] + f * a1;
       if (of) of[i] = v;
-      if (oi) oi[i] = (int16_t)((double)v * 32767.);
+      if (oi) oi[i] = pcm16_reference(v);
     }
     return;
   }
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(kResynthThreads) void resynth_kernel_v(const Resynt
       unsigned w[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const unsigned lo = (unsigned)(unsigned short)(int16_t)((double)v[2 * k] * 32767.);  // app.cpp:1212
-        const unsigned hi = (unsigned)(unsigned short)(int16_t)((double)v[2 * k + 1] * 32767.);
+        const unsigned lo = (unsigned)(unsigned short)pcm16_reference(v[2 * k]);  // app.cpp:1212
+        const unsigned hi = (unsigned)(unsigned short)pcm16_reference(v[2 * k + 1]);
         w[k] = lo | (hi << 16);
       }
       *reinterpret_cast<uint4 *>(oi + i0) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(kResynthThreads) void resynth_kernel_v(const Resynt
     const int ii = i < head ? i : tail0 + (i - head);
     const float v = lerp_tap(lg, ii, rate);
     if (of) of[ii] = v;
-    if (oi) oi[ii] = (int16_t)((double)v * 32767.);
+    if (oi) oi[ii] = pcm16_reference(v);
   }
 }
 

@@ -9,6 +9,8 @@ import math
 
 import numpy as np
 
+import pcm_extremes
+
 MAX_HALF = 2048
 PAD = 32768
 DEFAULTS = {"threshold": np.float32(0.15), "rms_floor": np.float32(1e-3), "unvoiced_period": np.float32(256.0)}
@@ -187,6 +189,5 @@ def render(wav, grains, nsamples):
 
 
 def pcm16(y):
-    """The int16 the definition takes of a binary32 sample."""
-    y32 = np.asarray(y, dtype=np.float32)
-    return (np.clip(y32, np.float32(-1), np.float32(1)).astype(np.float64) * 32767.0).astype(np.int16)
+    """The int16 the definition takes of a binary32 sample: the clamped form, NaN -> 0."""
+    return pcm_extremes.clamped_i16(y)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pcm_extremes
 import pv_markers
 import yin_ref
 from conftest import SR, accum_sweep, loaded_hip
@@ -46,7 +47,7 @@ def _tonal(n, amp=1.0, fade=True):
 
 
 def _i16_of(f32):
-    return (np.clip(f32, -1.0, 1.0).astype(np.float64) * 32767.0).astype(np.int16)  # truncation, as app.cpp:1211
+    return pcm_extremes.clamped_i16(f32)  # NaN -> 0, clamp, truncation as app.cpp:1211
 
 
 def _bits(x):

@@ -4,6 +4,7 @@ against that oracle on the same inputs, plus properties that need no oracle."""
 import numpy as np
 import pytest
 
+import pcm_extremes
 from conftest import SR, accum_sweep, noisy
 
 
@@ -69,7 +70,7 @@ def test_gpu_matches_oracle(gpu_ctx, pv, st):
         ref = pv.pitch_shift(w.astype(np.float64), st)
         assert f32.shape == ref.shape == w.shape
         assert np.abs(f32 - ref).max() <= 2e-5
-        want16 = (np.clip(f32, -1.0, 1.0).astype(np.float64) * 32767.0).astype(np.int16)  # truncation, as app.cpp:1211
+        want16 = pcm_extremes.clamped_i16(f32)  # truncation, as app.cpp:1211
         assert np.array_equal(i16, want16)
         only16 = gpu_ctx.pv_pitch_shift(a, st, want_f32=False)[1]
         assert np.array_equal(only16, i16)
@@ -96,7 +97,7 @@ def test_gpu_minutes_match_the_oracle(gpu_ctx, pv, st, mix, seconds):
         ref = pv.pitch_shift(w.astype(np.float64), st)
         err = np.abs(f32 - ref)
         assert f32.shape == ref.shape and err.max() <= 2e-5, float(err.max())
-        want16 = (np.clip(f32, -1.0, 1.0).astype(np.float64) * 32767.0).astype(np.int16)
+        want16 = pcm_extremes.clamped_i16(f32)
         assert np.array_equal(i16, want16)
         # ... and the same samples through chunks that cut the recurrence's groups (7 chunks of 4096 frames)
         gpu_ctx.pv_set_chunk_frames(4096)
@@ -173,7 +174,7 @@ def test_gpu_impulse_train_every_bin_a_peak(gpu_ctx, pv, st):
     err = np.abs(f32 - ref)
     # an impulse is all near-ties in time as well (which frame "has" it at its Hann-window edge): bounded like the noisy case
     assert np.sqrt((err ** 2).mean()) < 2e-4 and err.max() < 2e-2, (float(np.sqrt((err ** 2).mean())), float(err.max()))
-    assert np.abs(f32).max() > 0.05 and np.array_equal(i16, (np.clip(f32, -1.0, 1.0).astype(np.float64) * 32767.0).astype(np.int16))
+    assert np.abs(f32).max() > 0.05 and np.array_equal(i16, pcm_extremes.clamped_i16(f32))
     y2, _ = gpu_ctx.pv_pitch_shift(a, st)
     assert np.array_equal(f32.view(np.uint32), y2.view(np.uint32))
     a.free()
@@ -853,7 +854,7 @@ def test_gpu_marker_render_matches_oracle(gpu_ctx, pv, mk):
     ref = pv.render(w.astype(np.float64), SR, mk)
     assert f32.shape == ref.shape
     assert np.abs(f32 - ref).max() <= 5e-5
-    assert np.array_equal(i16, (np.clip(f32, -1.0, 1.0).astype(np.float64) * 32767.0).astype(np.int16))
+    assert np.array_equal(i16, pcm_extremes.clamped_i16(f32))
     a.free()
 
 
@@ -873,7 +874,7 @@ def test_gpu_marker_render_two_minutes_matches_oracle(gpu_ctx, pv):
         ref = pv.render(w.astype(np.float64), SR, mk)
         assert f32.shape == ref.shape and len(ref) > n  # (the markers stretch by one second net)
         assert np.abs(f32 - ref).max() <= 5e-5, float(np.abs(f32 - ref).max())
-        assert np.array_equal(i16, (np.clip(f32, -1.0, 1.0).astype(np.float64) * 32767.0).astype(np.int16))
+        assert np.array_equal(i16, pcm_extremes.clamped_i16(f32))
         gpu_ctx.pv_set_chunk_frames(2048)
         g32, _ = gpu_ctx.pv_render(a, SR, mk, want_i16=False)
         assert gpu_ctx.pv_last_chunks() >= 8 and np.array_equal(g32.view(np.uint32), f32.view(np.uint32))
