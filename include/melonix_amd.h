@@ -1234,6 +1234,106 @@ int mx_psola_render_bend_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int
                              const mx_formant_point *points, int npoints, const float *bend, float *d_pcm_f32,
                              int16_t *d_pcm_i16);
 
+/* ---- Loudness and note levelling (BUILD-DEFINED; restated by tests/loudness_ref.py) ----
+ * The level macro of a vocal editor: how loud a take and each of its notes is, in LUFS (ITU-R BS.1770-4, one channel), the
+ * gain points that even the notes out, and the gain that brings an export to a target loudness.  The output side is
+ * mx_audio_gain (above): applied to the source ahead of any renderer, the f0 track stays valid.  mx_f0.rms and the sibilant
+ * powers are unweighted and window-shaped; neither is a loudness.  The reference has no meter.
+ *
+ * Geometry, all integer, for sampleRate sr in [8000, 384000] and a take of n samples:
+ *   S = (sr + 50) / 100                    a step, 10 ms;
+ *   G = 10                                 steps per group: the 100 ms gating hop of BS.1770;
+ *   W = 4 * ((32 * sr + 1499) / 1500)      warm-up samples (4096 at 48 kHz, 3764 at 44.1 kHz, 32768 = MX_AUDIO_PAD at 384 kHz:
+ *                                          the warm-up never reads outside the left pad);
+ *   steps = ceil(n / S), groups = ceil(steps / G).
+ *
+ * K-weighting, binary64 on the host, once per sample rate (the bilinear re-derivation of the two BS.1770 stages):
+ *   shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / sr),
+ *              Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K K;
+ *              b = {Vh + Vb K/Q + K K, 2 (K K - Vh), Vh - Vb K/Q + K K} / a0,  a1 = 2 (K K - 1) / a0, a2 = (1 - K/Q + K K) / a0;
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 likewise; c = {1, -2, 1}, d1 and d2 as a1 and a2.
+ * At 48 kHz these are the table of BS.1770-4 to the last digit it prints.  mx_loudness_coeffs gives {b0, b1, b2, a1, a2,
+ * c0, c1, c2, d1, d2}; the device receives them as kernel arguments and computes no transcendental.
+ *
+ * Filter: binary64, transposed direct form II, no contraction, this order.  Group g starts with its four states zero at
+ * sample i0 = g G S - W and runs i = i0 .. min((g + 1) G S, n) - 1, with v = (double)x_i and v = 0 for i < 0:
+ *   y = b0*v + s1;  s1 = (b1*v - a1*y) + s2;  s2 = b2*v - a2*y;
+ *   z = c0*y + t1;  t1 = (c1*y - d1*z) + t2;  t2 = c2*y - d2*z;
+ * From i >= g G S on, step k = (i - g G S) / S of the group accumulates  energy += z*z  in ascending i, and  peak = the largest
+ * |x_i| among the step's samples that are not NaN (Inf counts; 0 if there are none).  Samples at or beyond n are not visited
+ * (the right pad is not relied on).  A record depends on the samples [g G S - W, (g + 1) G S) alone: the same bytes whatever
+ * the launch split.  THE TRUNCATED WARM-UP IS PART OF THE DEFINITION.  (For information: at 48 kHz it differs from the
+ * untruncated filter by at most 3.4e-9 relative per 100 ms — a 30 Hz sine; noise 4e-12.)
+ *
+ * Consequences (tests pin all three):
+ *   silence gives energy == +0.0 and peak == 0 exactly, for -0.0f samples too;
+ *   2^k x gives 4^k energy and 2^k peak bit for bit wherever 2^k x is exact in binary32 (and nothing under- or overflows);
+ *   a NaN or +-Inf sample at position p makes energy non-finite (NaN or +Inf) in the groups with
+ *   g G S - W <= p < min((g + 1) G S, n), there in the steps whose last sample is at or after p, and nowhere else: every other
+ *   step keeps the bytes it has without the bad sample. */
+typedef struct mx_loud_step {
+  double energy;   /* sum of z*z over the step's samples */
+  float peak;      /* sample peak of the step (not true peak) */
+  int32_t samples; /* S, or n - b*S for the last, partial step */
+} mx_loud_step;
+/* ceil(n / S); 0 for n < 1 or sampleRate outside [8000, 384000]. */
+int64_t mx_loudness_step_count(int64_t n, int sampleRate);
+/* out10 = {b0, b1, b2, a1, a2} of the shelf, then of the high-pass.  MX_ERR_INVALID (out10 untouched) for sampleRate out of range. */
+int mx_loudness_coeffs(int sampleRate, double *out10);
+/* The records of steps [G*first_group, min(G*(first_group + ngroups), steps)) -> d_steps (in HBM, 16-byte aligned: a record is
+ * written as one 16-byte store).  Asynchronous on the context's stream.  MX_ERR_INVALID, before any launch, for sampleRate out
+ * of range, first_group < 0, ngroups < 0, groups beyond the file, or NULLs (d_steps may be NULL where ngroups is 0). */
+int mx_loudness_steps_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups,
+                          mx_loud_step *d_steps);
+/* Same, host output through the context's staging buffers.  Blocks. */
+int mx_loudness_steps(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups, mx_loud_step *steps_out);
+/* Loudness over a sliding window (host, binary64): for b >= window_steps - 1 with all window_steps steps full (samples == S)
+ *   out[b] = -0.691 + 10 log10((energies of steps b - window_steps + 1 .. b, summed ascending) / (window_steps * S)),
+ * else out[b] = -inf.  steps[0] is step 0 of the take.  window_steps 40: momentary (400 ms); 300: short-term (3 s).
+ * MX_ERR_INVALID for sampleRate out of range, window_steps outside [1, 6000], a step whose samples lie outside [1, S]. */
+int mx_loudness_curve(const mx_loud_step *steps, int64_t nsteps, int sampleRate, int window_steps, double *out);
+/* Integrated loudness (BS.1770-4 gating, decided in the energy domain).  Block j covers steps [10 j, 10 j + 40), all 40 full
+ * (j < blocks = the number of such blocks);  z_j = (their energies, summed ascending) / (40 S).  A block whose z is not finite
+ * is left out and counted (bad_blocks).  Absolute gate: z_j > 0x1.f791ec6e1d5b7p-24 (= 10^((-70 + 0.691) / 10)).  Relative
+ * gate: z_j > 0.1 * ((the z that pass the absolute gate, summed ascending) / passed_abs).
+ *   integrated = -0.691 + 10 log10((the z that pass both gates, summed ascending) / passed_rel); -inf when passed_abs is 0;
+ *   momentary_max, shortterm_max = the largest value of mx_loudness_curve with windows 40 and 300 that is not NaN (-inf: none);
+ *   peak = the largest step peak (sample peak; TRUE PEAK, an oversampled measurement, is out of scope). */
+typedef struct mx_loudness {
+  double integrated, momentary_max, shortterm_max; /* LUFS */
+  float peak;
+  int64_t blocks, passed_abs, passed_rel, bad_blocks;
+} mx_loudness;
+int mx_loudness_integrated(const mx_loud_step *steps, int64_t nsteps, int sampleRate, mx_loudness *out);
+/* The whole take: its records on the GPU, then mx_loudness_integrated.  Blocks. */
+int mx_loudness_measure(mx_ctx *ctx, const mx_audio *a, int sampleRate, mx_loudness *out);
+/* Loudness per note (host, binary64): over the steps b < nsteps that lie inside the note, b*S >= start_sample and
+ * (b + 1)*S - 1 <= end_sample; if there are none, over the step that holds (start_sample + end_sample) / 2:
+ *   lufs = -0.691 + 10 log10(sum of energies, ascending / sum of samples);  -inf for zero energy, NaN if a chosen step's
+ * energy is not finite.  MX_ERR_INVALID (lufs_out untouched) for a note with start_sample < 0, end_sample < start_sample, or
+ * end_sample at or beyond the samples the records cover. */
+int mx_note_loudness(const mx_loud_step *steps, int64_t nsteps, int sampleRate, const mx_note *notes, int64_t nnotes,
+                     double *lufs_out);
+/* Note levelling.  reference = the median of the finite lufs (an even count: the mean of the two middle values; none: NaN).
+ * Per note d = reference - lufs_i, db = clamp((d > 0 ? raise : lower) * d, -max_db, max_db), A = (float)pow(10, db / 20) in
+ * binary64; a note whose lufs is not finite gets A = 1.  out (2*nnotes points): {start_sample, A}, {end_sample, A} per note —
+ * strictly increasing samples, accepted by mx_audio_gain as they are; between notes the gain is its linear ramp.  raise scales
+ * the lift of quiet notes, lower the cut of loud ones.  params NULL: the defaults.  reference_out may be NULL.
+ * MX_ERR_INVALID for notes out of order or overlapping (as mx_correction_markers), raise or lower outside [0, 1], max_db
+ * outside [0, 40]. */
+typedef struct mx_level_params {
+  double raise, lower; /* [0, 1] */
+  double max_db;       /* [0, 40] */
+} mx_level_params;
+/* {1.0, 1.0, 12.0} */
+void mx_level_params_default(mx_level_params *p);
+int mx_level_gain_points(const mx_note *notes, int64_t nnotes, const double *lufs, const mx_level_params *params,
+                         mx_gain_point *out, double *reference_out);
+/* The one gain that brings a measured take to target_lufs without its sample peak passing ceiling_db (dBFS):
+ *   amp = (float)min(10^((target_lufs - integrated) / 20), 10^(ceiling_db / 20) / peak).
+ * MX_ERR_INVALID (amp untouched) when integrated is not finite, peak is 0 or not finite, or an argument is not finite. */
+int mx_normalize_gain(const mx_loudness *m, double target_lufs, double ceiling_db, float *amp);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

@@ -21,6 +21,7 @@ from ._capi import COMB_DTYPE, COMB_JOB_DTYPE, TEMPO_WINDOW_DTYPE  # noqa: F401
 from ._capi import GAIN_POINT_DTYPE, SIB_FEAT_DTYPE, SIBILANT_DTYPE  # noqa: F401
 from ._capi import CHROMA_COLS, CHROMA_JOB_DTYPE, KEY_DTYPE, KEY_WINDOW_DTYPE  # noqa: F401
 from ._capi import CONTOUR_NONE, CONTOUR_REC_DTYPE, CONTOUR_SPAN_DTYPE, CONTOUR_STAT_DTYPE  # noqa: F401
+from ._capi import LOUD_GROUP_STEPS, LOUD_STEP_DTYPE  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
@@ -34,7 +35,9 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "CHROMA_COLS", "CHROMA_JOB_DTYPE", "KEY_DTYPE", "KEY_WINDOW_DTYPE", "chroma_params_default", "key_from_chroma",
            "key_from_notes", "correction_markers_tuned",
            "CONTOUR_NONE", "CONTOUR_SPAN_DTYPE", "CONTOUR_REC_DTYPE", "CONTOUR_STAT_DTYPE", "contour_params_default",
-           "bend_params_default", "contour_spans", "contour_vibrato", "contour_bend", "psola_plan_bend", "psola_plan_formant_bend"]
+           "bend_params_default", "contour_spans", "contour_vibrato", "contour_bend", "psola_plan_bend", "psola_plan_formant_bend",
+           "LOUD_STEP_DTYPE", "LOUD_GROUP_STEPS", "level_params_default", "loudness_step_count", "loudness_coeffs", "loudness_curve",
+           "loudness_integrated", "note_loudness", "level_gain_points", "normalize_gain"]
 
 
 # The two pointer forms of an optional argument.  New wrappers use these: _opt for a host array, _dev for a device address.
@@ -97,7 +100,8 @@ _PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "not
            "tempo": (_capi.TempoParams, "mx_tempo_params_default"),
            "sib_feature": (_capi.SibFeatureParams, "mx_sib_feature_params_default"),
            "sibilant": (_capi.SibilantParams, "mx_sibilant_params_default"),
-           "chroma": (_capi.ChromaParams, "mx_chroma_params_default"), "bend": (_capi.BendParams, "mx_bend_params_default")}
+           "chroma": (_capi.ChromaParams, "mx_chroma_params_default"), "bend": (_capi.BendParams, "mx_bend_params_default"),
+           "level": (_capi.LevelParams, "mx_level_params_default")}
 
 
 def _params_default(kind: str) -> dict:
@@ -133,7 +137,7 @@ def _default_fn(kind: str):
 _DEFAULT_FNS = tuple(map(_default_fn, _PARAMS))
 (f0_decode_params_default, note_params_default, psola_params_default, onset_flux_params_default, onset_pick_params_default,
  timing_params_default, tempo_params_default, sib_feature_params_default, sibilant_params_default, chroma_params_default,
- bend_params_default) = _DEFAULT_FNS
+ bend_params_default, level_params_default) = _DEFAULT_FNS
 assert all(globals()[fn.__name__] is fn for fn in _DEFAULT_FNS)
 
 
@@ -547,6 +551,47 @@ class Context:
         out = np.empty(max(count, 0), dtype=np.float32)
         _call("mx_audio_download", self.handle, audio.handle, first, count, _ptr(out))
         return out
+
+    # ---- loudness records, BS.1770 loudness, note levelling (build-defined; include/melonix_amd.h) ----
+    level_params_default = staticmethod(level_params_default)
+
+    def loudness_steps(self, audio: Audio, sr: int, first_group: int = 0, ngroups: int | None = None):
+        """-> LOUD_STEP_DTYPE records of the steps of groups [first_group, first_group + ngroups) (ten 10 ms steps a group;
+        ngroups None: to the end of the file)."""
+        steps = loudness_step_count(audio.n, sr)
+        ngroups = -(-steps // LOUD_GROUP_STEPS) - first_group if ngroups is None else ngroups
+        count = min(LOUD_GROUP_STEPS * (first_group + ngroups), steps) - LOUD_GROUP_STEPS * first_group if ngroups > 0 else 0
+        out = np.empty(max(count, 0), dtype=LOUD_STEP_DTYPE)
+        _call("mx_loudness_steps", self.handle, audio.handle, sr, first_group, ngroups, _ptr(out))
+        return out
+
+    def loudness_steps_dev(self, audio: Audio, sr: int, first_group: int, ngroups: int, d_steps: int):
+        """The records stay in HBM at d_steps (16 bytes a step, 16-byte aligned); asynchronous on the context's stream."""
+        _call("mx_loudness_steps_dev", self.handle, audio.handle, sr, first_group, ngroups, _dev(d_steps))
+
+    def loudness_measure(self, audio: Audio, sr: int) -> dict:
+        """The whole take -> dict of mx_loudness' fields (integrated, momentary_max, shortterm_max, peak, the gate counts)."""
+        m = _capi.Loudness()
+        _call("mx_loudness_measure", self.handle, audio.handle, sr, C.byref(m))
+        return _fields(m)
+
+    def loudness_coeffs(self, sr: int):
+        return loudness_coeffs(sr)
+
+    def loudness_curve(self, steps, sr: int, window_steps: int = 40):
+        return loudness_curve(steps, sr, window_steps)
+
+    def loudness_integrated(self, steps, sr: int) -> dict:
+        return loudness_integrated(steps, sr)
+
+    def note_loudness(self, steps, sr: int, notes):
+        return note_loudness(steps, sr, notes)
+
+    def level_gain_points(self, notes, lufs, **params):
+        return level_gain_points(notes, lufs, **params)
+
+    def normalize_gain(self, measured: dict, target_lufs: float = -23.0, ceiling_db: float = -1.0) -> float:
+        return normalize_gain(measured, target_lufs, ceiling_db)
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
     def tempo_smooth(self, flux, width: int = 4):
@@ -1069,3 +1114,63 @@ def sibilant_gain_points(sibs, db: float, ramp: int, n: int):
     """The gain points of a sibilant balance of `db` decibels -> GAIN_POINT_DTYPE array for Context.audio_gain."""
     sibs = _records(sibs, SIBILANT_DTYPE)
     return _handed(GAIN_POINT_DTYPE, "mx_sibilant_gain_points", _opt(sibs), len(sibs), float(db), int(ramp), int(n))
+
+
+# ---- loudness curves, gating, note loudness, levelling points, export gain (host; build-defined) ----
+def loudness_step_count(n: int, sr: int) -> int:
+    """ceil(n / S), S = (sr + 50) // 100 the 10 ms step; 0 for n < 1 or a sample rate outside [8000, 384000]."""
+    return int(_capi.lib().mx_loudness_step_count(int(n), int(sr)))
+
+
+def loudness_coeffs(sr: int):
+    """The K-weighting coefficients at sr -> float64[10]: {b0, b1, b2, a1, a2} of the shelf, then of the high-pass."""
+    out = np.empty(10, dtype=np.float64)
+    _call("mx_loudness_coeffs", int(sr), _ptr(out))
+    return out
+
+
+def loudness_curve(steps, sr: int, window_steps: int = 40):
+    """Loudness over a sliding window of LOUD_STEP_DTYPE records (steps[0] = step 0) -> float64[nsteps], -inf where the window
+    is not full.  window_steps 40: momentary; 300: short-term."""
+    steps = _records(steps, LOUD_STEP_DTYPE)
+    out = np.empty(len(steps), dtype=np.float64)
+    _call("mx_loudness_curve", _opt(steps), len(steps), int(sr), int(window_steps), _opt(out))
+    return out
+
+
+def loudness_integrated(steps, sr: int) -> dict:
+    """BS.1770-4 gated loudness of LOUD_STEP_DTYPE records -> dict of mx_loudness' fields."""
+    steps = _records(steps, LOUD_STEP_DTYPE)
+    m = _capi.Loudness()
+    _call("mx_loudness_integrated", _opt(steps), len(steps), int(sr), C.byref(m))
+    return _fields(m)
+
+
+def note_loudness(steps, sr: int, notes):
+    """LUFS per note (NOTE_DTYPE) from LOUD_STEP_DTYPE records -> float64[nnotes]."""
+    steps, notes = _records(steps, LOUD_STEP_DTYPE), np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    out = np.empty(len(notes), dtype=np.float64)
+    _call("mx_note_loudness", _opt(steps), len(steps), int(sr), _opt(notes), len(notes), _opt(out))
+    return out
+
+
+def level_gain_points(notes, lufs, **params):
+    """The gain points that move each note towards the median loudness -> (GAIN_POINT_DTYPE[2 * nnotes] for Context.audio_gain,
+    the reference in LUFS).  params: fields of level_params_default() (`raise` is a Python keyword: pass it as raise_=, or
+    through a dict)."""
+    notes = np.ascontiguousarray(notes, dtype=NOTE_DTYPE)
+    lufs = np.ascontiguousarray(lufs, dtype=np.float64)
+    if len(lufs) != len(notes):
+        raise ValueError("one loudness per note")
+    params = {k[:-1] if k.endswith("_") else k: v for k, v in params.items()}
+    out, ref = np.zeros(2 * len(notes), dtype=GAIN_POINT_DTYPE), C.c_double()
+    _call("mx_level_gain_points", _opt(notes), len(notes), _opt(lufs), _params_arg("level", params), _opt(out), C.byref(ref))
+    return out, ref.value
+
+
+def normalize_gain(measured: dict, target_lufs: float = -23.0, ceiling_db: float = -1.0) -> float:
+    """The gain (as float32) that brings a take measured by loudness_integrated / Context.loudness_measure to target_lufs with
+    its sample peak at most ceiling_db dBFS."""
+    amp = C.c_float()
+    _call("mx_normalize_gain", C.byref(_capi.Loudness(**measured)), float(target_lufs), float(ceiling_db), C.byref(amp))
+    return amp.value

@@ -56,6 +56,9 @@ UNITS = [
     ("chroma_kernels.hip", "hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     # build-defined pitch-contour split: binary64 cents as written, integers after that (contour_core.h), bit for bit numpy's
     ("contour_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined loudness records: the K-weighting recurrence in binary64, every product rounded before its sum
+    # (loudness_core.h), bit for bit numpy's
+    ("loudness_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -71,6 +74,7 @@ UNITS = [
     ("capi_sibilant.cpp", "hip", []),
     ("capi_key.cpp", "hip", []),
     ("capi_contour.cpp", "hip", []),
+    ("capi_loudness.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
@@ -80,6 +84,7 @@ UNITS = [
     ("sibilant_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("key_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("contour_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("loudness_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

@@ -1,0 +1,188 @@
+// capi_loudness.cpp — loudness records (loudness_kernels.hip), the windowed curve, BS.1770 gating, note loudness, the levelling
+// points and the export gain (loudness_logic.cpp): BUILD-DEFINED, the reference has none of it.  One unit of the C-ABI
+// implementation behind include/melonix_amd.h (see capi_internal.h).
+#include "capi_internal.h"
+#include "loudness_core.h"
+#include "loudness_logic.h"
+
+using namespace mx;
+
+namespace {
+
+const mx_level_params kLevelDefaults{1.0, 1.0, 12.0};
+constexpr int kMaxWindow = 6000;
+
+bool rate_ok(int sr) { return sr >= loud::kMinRate && sr <= loud::kMaxRate; }
+int rate_check(int sr) {
+  return rate_ok(sr) ? MX_OK : fail(MX_ERR_INVALID, "sample rate %d outside [%d, %d]", sr, loud::kMinRate, loud::kMaxRate);
+}
+
+// What the two record entry points share: their arguments, checked, and the records they write
+struct StepsCall {
+  mx_ctx *ctx;
+  const mx_audio *a;
+  loud::Geometry geo;
+  int sampleRate;
+  int64_t first_group, ngroups, records;
+};
+
+int steps_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups, const void *out, StepsCall &q) {
+  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = rate_check(sampleRate)) return rc;
+  const loud::Geometry geo = loud::geometry(a->n, sampleRate);
+  if (first_group < 0 || ngroups < 0 || first_group > geo.groups || ngroups > geo.groups - first_group)
+    return fail(MX_ERR_INVALID, "groups [%lld, %lld) outside the file's %lld", (long long)first_group, (long long)(first_group + ngroups),
+                (long long)geo.groups);
+  if (ngroups > 0 && !out) return fail(MX_ERR_INVALID, "null output");
+  const int64_t lo = loud::kGroupSteps * first_group, hi = std::min(loud::kGroupSteps * (first_group + ngroups), geo.steps);
+  q = StepsCall{ctx, a, geo, sampleRate, first_group, ngroups, ngroups > 0 ? hi - lo : 0};
+  return MX_OK;
+}
+
+int steps_launch(const StepsCall &q, mx_loud_step *d_steps) {
+  if (q.ngroups == 0) return MX_OK;
+  if (reinterpret_cast<uintptr_t>(d_steps) % 16) return fail(MX_ERR_INVALID, "device records must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(q.ctx->device));
+  LoudnessArgs g{};
+  g.image = q.a->d_padded;
+  g.n = q.a->n;
+  g.S = q.geo.S;
+  g.W = q.geo.W;
+  g.first_group = q.first_group;
+  g.ngroups = q.ngroups;
+  loudness_coeffs(q.sampleRate, g.coeffs);
+  g.out = d_steps;
+  HIP_TRY(launch_loudness_steps(g, q.ctx->stream));
+  return MX_OK;
+}
+
+// the host form: the records pass through the context's staging buffer of the pitch records
+int steps_host(const StepsCall &q, mx_loud_step *steps_out) {
+  const StagedSlot slots[] = {{kStagePitch, sizeof(mx_loud_step), nullptr, steps_out}};
+  return staged_records(q.ctx, q.records, slots, "loudness records",
+                        [&](void *const *d) { return steps_launch(q, static_cast<mx_loud_step *>(d[0])); });
+}
+
+// what the host entry points check of a record list
+int list_check(const mx_loud_step *steps, int64_t nsteps, int sampleRate) {
+  if (const int rc = rate_check(sampleRate)) return rc;
+  if (nsteps < 0 || (nsteps > 0 && !steps)) return fail(MX_ERR_INVALID, "bad record list");
+  if (const char *why = loud_steps_error(steps, nsteps, loud::geometry(0, sampleRate).S)) return fail(MX_ERR_INVALID, "%s", why);
+  return MX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mx_loudness_step_count(int64_t n, int sampleRate) {
+  return mx_guard([&]() -> int64_t { return rate_ok(sampleRate) ? loud::geometry(n, sampleRate).steps : 0; });
+}
+
+int mx_loudness_coeffs(int sampleRate, double *out10) {
+  return mx_guard([&]() -> int {
+    if (const int rc = rate_check(sampleRate)) return rc;
+    if (!out10) return fail(MX_ERR_INVALID, "null output");
+    loudness_coeffs(sampleRate, out10);
+    return MX_OK;
+  });
+}
+
+int mx_loudness_steps_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups,
+                          mx_loud_step *d_steps) {
+  return mx_guard([&]() -> int {
+    StepsCall q;
+    if (const int rc = steps_parse(ctx, a, sampleRate, first_group, ngroups, d_steps, q)) return rc;
+    return steps_launch(q, d_steps);
+  });
+}
+
+int mx_loudness_steps(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups, mx_loud_step *steps_out) {
+  return mx_guard([&]() -> int {
+    StepsCall q;
+    if (const int rc = steps_parse(ctx, a, sampleRate, first_group, ngroups, steps_out, q)) return rc;
+    return steps_host(q, steps_out);
+  });
+}
+
+int mx_loudness_curve(const mx_loud_step *steps, int64_t nsteps, int sampleRate, int window_steps, double *out) {
+  return mx_guard([&]() -> int {
+    if (const int rc = list_check(steps, nsteps, sampleRate)) return rc;
+    if (window_steps < 1 || window_steps > kMaxWindow) return fail(MX_ERR_INVALID, "window of %d steps outside [1, %d]", window_steps, kMaxWindow);
+    if (nsteps > 0 && !out) return fail(MX_ERR_INVALID, "null output");
+    loudness_curve(steps, nsteps, loud::geometry(0, sampleRate).S, window_steps, out);
+    return MX_OK;
+  });
+}
+
+int mx_loudness_integrated(const mx_loud_step *steps, int64_t nsteps, int sampleRate, mx_loudness *out) {
+  return mx_guard([&]() -> int {
+    if (const int rc = list_check(steps, nsteps, sampleRate)) return rc;
+    if (!out) return fail(MX_ERR_INVALID, "null output");
+    loudness_integrated(steps, nsteps, loud::geometry(0, sampleRate).S, out);
+    return MX_OK;
+  });
+}
+
+int mx_loudness_measure(mx_ctx *ctx, const mx_audio *a, int sampleRate, mx_loudness *out) {
+  return mx_guard([&]() -> int {
+    if (!out) return fail(MX_ERR_INVALID, "null output");
+    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = rate_check(sampleRate)) return rc;
+    const loud::Geometry geo = loud::geometry(a->n, sampleRate);
+    std::vector<mx_loud_step> steps((size_t)std::max<int64_t>(geo.steps, 1));
+    StepsCall q;
+    if (const int rc = steps_parse(ctx, a, sampleRate, 0, geo.groups, steps.data(), q)) return rc;
+    if (const int rc = steps_host(q, steps.data())) return rc;
+    loudness_integrated(steps.data(), geo.steps, geo.S, out);
+    return MX_OK;
+  });
+}
+
+int mx_note_loudness(const mx_loud_step *steps, int64_t nsteps, int sampleRate, const mx_note *notes, int64_t nnotes,
+                     double *lufs_out) {
+  return mx_guard([&]() -> int {
+    if (const int rc = list_check(steps, nsteps, sampleRate)) return rc;
+    if (nnotes < 0 || (nnotes > 0 && (!notes || !lufs_out))) return fail(MX_ERR_INVALID, "null argument");
+    std::vector<double> lufs((size_t)std::max<int64_t>(nnotes, 1));  // (the caller's array stays untouched where a note is refused)
+    int64_t bad = 0;
+    if (!note_loudness(steps, nsteps, loud::geometry(0, sampleRate).S, notes, nnotes, lufs.data(), &bad))
+      return fail(MX_ERR_INVALID, "note %lld is reversed or lies outside the %lld steps", (long long)bad, (long long)nsteps);
+    std::copy(lufs.begin(), lufs.begin() + nnotes, lufs_out);
+    return MX_OK;
+  });
+}
+
+void mx_level_params_default(mx_level_params *p) {
+  mx_guard_void([&] { params_default(p, kLevelDefaults); });
+}
+
+int mx_level_gain_points(const mx_note *notes, int64_t nnotes, const double *lufs, const mx_level_params *params,
+                         mx_gain_point *out, double *reference_out) {
+  return mx_guard([&]() -> int {
+    if (nnotes < 0 || (nnotes > 0 && (!notes || !lufs || !out))) return fail(MX_ERR_INVALID, "null argument");
+    const mx_level_params p = params_or(params, kLevelDefaults);
+    if (!(p.raise >= 0.0 && p.raise <= 1.0) || !(p.lower >= 0.0 && p.lower <= 1.0))
+      return fail(MX_ERR_INVALID, "raise %g / lower %g: both in [0, 1]", p.raise, p.lower);
+    if (!(p.max_db >= 0.0 && p.max_db <= 40.0)) return fail(MX_ERR_INVALID, "max_db %g outside [0, 40]", p.max_db);
+    for (int64_t i = 0; i < nnotes; ++i)
+      if (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample))
+        return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
+    const double ref = level_gain_points(notes, nnotes, lufs, p, out);
+    if (reference_out) *reference_out = ref;
+    return MX_OK;
+  });
+}
+
+int mx_normalize_gain(const mx_loudness *m, double target_lufs, double ceiling_db, float *amp) {
+  return mx_guard([&]() -> int {
+    if (!m || !amp) return fail(MX_ERR_INVALID, "null argument");
+    if (!std::isfinite(m->integrated)) return fail(MX_ERR_INVALID, "the integrated loudness is not finite");
+    if (!std::isfinite(m->peak) || !(m->peak > 0.f)) return fail(MX_ERR_INVALID, "peak %g must be finite and > 0", (double)m->peak);
+    if (!std::isfinite(target_lufs) || !std::isfinite(ceiling_db)) return fail(MX_ERR_INVALID, "target and ceiling must be finite");
+    *amp = (float)normalize_amp(m->integrated, (double)m->peak, target_lufs, ceiling_db);
+    return MX_OK;
+  });
+}
+
+}  // extern "C"

@@ -244,6 +244,18 @@ hipError_t launch_sib_features(const SibArgs &a, hipStream_t s);
 // Build-defined source gain (gain_kernels.hip; definition: include/melonix_amd.h).  dst: samples [0, n) of the new object
 // (16-byte aligned, as src).  The points are not validated on the device: bad ones give wrong samples, no store outside [0, n).
 hipError_t launch_audio_gain(const float *src, float *dst, int64_t n, const mx_gain_point *pts, int64_t npts, hipStream_t s);
+// Build-defined loudness records (loudness_kernels.hip; definition: include/melonix_amd.h, arithmetic: loudness_core.h).  Groups
+// [first_group, first_group + ngroups) of the take, all inside it, S and W the geometry of the sample rate: checked by the
+// caller.  out: the records of step G*first_group on, 16-byte aligned; only records of steps that exist are written.
+struct LoudnessArgs {
+  const float *image;  // padded image (the samples before the file are taken as zeros whatever the pad holds)
+  int64_t n;
+  int S, W;
+  int64_t first_group, ngroups;
+  double coeffs[10];  // mx_loudness_coeffs' order
+  mx_loud_step *out;
+};
+hipError_t launch_loudness_steps(const LoudnessArgs &a, hipStream_t s);
 // Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
 // count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
 // range (the caller's check) gives a wrong record and nothing worse.
