@@ -1273,7 +1273,7 @@ int mx_psola_render_bend_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int
  *   step keeps the bytes it has without the bad sample. */
 typedef struct mx_loud_step {
   double energy;   /* sum of z*z over the step's samples */
-  float peak;      /* sample peak of the step (not true peak) */
+  float peak;      /* sample peak of the step (the true peak: mx_tp_step below) */
   int32_t samples; /* S, or n - b*S for the last, partial step */
 } mx_loud_step;
 /* ceil(n / S); 0 for n < 1 or sampleRate outside [8000, 384000]. */
@@ -1298,7 +1298,7 @@ int mx_loudness_curve(const mx_loud_step *steps, int64_t nsteps, int sampleRate,
  * gate: z_j > 0.1 * ((the z that pass the absolute gate, summed ascending) / passed_abs).
  *   integrated = -0.691 + 10 log10((the z that pass both gates, summed ascending) / passed_rel); -inf when passed_abs is 0;
  *   momentary_max, shortterm_max = the largest value of mx_loudness_curve with windows 40 and 300 that is not NaN (-inf: none);
- *   peak = the largest step peak (sample peak; TRUE PEAK, an oversampled measurement, is out of scope). */
+ *   peak = the largest step peak (sample peak; the oversampled TRUE PEAK is mx_true_peak_measure's, below: DESIGN 5n). */
 typedef struct mx_loudness {
   double integrated, momentary_max, shortterm_max; /* LUFS */
   float peak;
@@ -1333,6 +1333,94 @@ int mx_level_gain_points(const mx_note *notes, int64_t nnotes, const double *luf
  *   amp = (float)min(10^((target_lufs - integrated) / 20), 10^(ceiling_db / 20) / peak).
  * MX_ERR_INVALID (amp untouched) when integrated is not finite, peak is 0 or not finite, or an argument is not finite. */
 int mx_normalize_gain(const mx_loudness *m, double target_lufs, double ceiling_db, float *amp);
+
+/* ---- True peak, limiter and loudness range (BUILD-DEFINED; restated by tests/truepeak_ref.py) ----
+ * The end of the export chain: the inter-sample ("true") peak of a take in the sense of BS.1770-4 annex 2, a look-ahead limiter
+ * that holds a ceiling on it and writes the final int16, and the loudness range of EBU Tech 3342 from the mx_loud_step records.
+ * One arithmetic: the same bytes on the device, in the CPU emulation and in numpy, whatever the launch split.  The reference
+ * has none of it.
+ *
+ * Geometry, for sampleRate sr in [8000, 384000]:  S = (sr + 50) / 100, the 10 ms step of mx_loud_step; steps = ceil(n / S);
+ * oversampling L = 4 for sr < 88200, 2 for 88200 <= sr < 176400, else 1 (true peak = sample peak).
+ *
+ * Taps: T = 12 per fractional offset u in {1/4, 1/2, 3/4}, rate-independent; for d = -5 .. 6 and v = d - u
+ *   c_u[d] = (float)(sinc(v) * (0.42 + 0.5 cos(pi v / 6) + 0.08 cos(2 pi v / 6))),  sinc(v) = sin(pi v) / (pi v), in binary64.
+ * L = 4 uses all three offsets, L = 2 uses 1/2 alone.  Offset 0 is the sample itself (an L-th-band prototype).  The 36 values
+ * are literals of the library (mx_true_peak_taps): no libm between a test and the bytes.
+ *
+ * Per-sample peak, binary32 without contraction, x_j = 0 for j outside [0, n):
+ *   y_{i,u} = sum over d ascending of x_{i+d} * c_u[d], from +0.f, each product rounded, then added;
+ *   p_i = |x_i| if x_i is not NaN, else 0; then for each used u, ascending: p_i = |y_{i,u}| > p_i ? |y_{i,u}| : p_i.
+ * A NaN never enters p_i; +-Inf counts.
+ *
+ * Record of step b (8 bytes): true_peak = the largest p_i, sample_peak = the largest |x_i| that is not NaN (mx_loud_step.peak's
+ * rule) over the step's samples; true_peak >= sample_peak.  It depends on the samples [b S - 5, (b + 1) S + 6) alone.
+ *
+ * Limiter, for a ceiling amplitude c (a normal binary32, 0 < c <= 1) and a look-ahead of A samples (1 <= A <= 1024):
+ *   q_j = 2^30 for j outside [0, n) and wherever !(p_j > c), else (int32)floor(((double)c / (double)p_j) * 2^30)  (0 for Inf);
+ *   m_t = min over j in [t, t + A] of q_j;   s_i = sum over t in [i - A, i] of m_t  (int64);
+ *   g_i = (double)s_i / (double)((int64_t)(A + 1) << 30);   out_i = (float)((double)x_i * g_i);   pcm_i = the clamped int16
+ *   conversion of out_i ("PCM conversions" above).
+ * Everything between p and g is integer: any tiling, scan order or prefix-sum scheme gives the same bytes.
+ *
+ * Consequences (tests pin all five):
+ *   1. |out_i| <= c for every finite input;
+ *   2. out_i has x_i's bytes wherever no j in [i - A, i + A] has p_j > c (g is exactly 1);
+ *   3. limit(2^k x, 2^k c) = 2^k limit(x, c) bit for bit where 2^k scales exactly and nothing under- or overflows; the records
+ *      scale likewise;
+ *   4. silence, of -0.0f samples too, gives records {0, 0} and an output with the input's bytes;
+ *   5. a NaN or +-Inf sample at s changes no record outside the steps that hold samples of [s - 6, s + 5] and no output sample
+ *      outside [s - A - 6, s + A + 6].
+ * The TRUE peak of the output is not bounded by c exactly (a moving gain changes the values between the samples): by how much
+ * is a measurement, DESIGN 5n. */
+typedef struct mx_tp_step {
+  float true_peak;   /* the largest p_i of the step */
+  float sample_peak; /* the largest |x_i| that is not NaN */
+} mx_tp_step;
+/* L; 0 for sampleRate outside [8000, 384000]. */
+int mx_true_peak_oversampling(int sampleRate);
+/* out36 = c_{1/4}[-5 .. 6], c_{1/2}[-5 .. 6], c_{3/4}[-5 .. 6].  MX_ERR_INVALID for NULL. */
+int mx_true_peak_taps(float *out36);
+/* The records of steps [first_step, first_step + nsteps) -> d_steps (in HBM, 8-byte aligned: a record is one 8-byte store).
+ * Asynchronous on the context's stream.  MX_ERR_INVALID, before any launch, for sampleRate out of range, a step range outside
+ * the file's steps, or NULLs (d_steps may be NULL where nsteps is 0). */
+int mx_true_peak_steps_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_step, int64_t nsteps, mx_tp_step *d_steps);
+/* Same, host output through the context's staging buffers.  Blocks. */
+int mx_true_peak_steps(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_step, int64_t nsteps, mx_tp_step *steps_out);
+/* The whole take: the largest true_peak and the largest sample_peak of its records (0 for an empty take).  Either output may
+ * be NULL, not both.  Blocks. */
+int mx_true_peak_measure(mx_ctx *ctx, const mx_audio *a, int sampleRate, float *true_peak, float *sample_peak);
+typedef struct mx_limit_params {
+  float ceiling_amp; /* c: an amplitude, a normal binary32 in (0, 1] */
+  int32_t lookahead; /* A: samples, [1, 1024] */
+} mx_limit_params;
+/* {(float)10^(-1/20) (-1 dBTP), min(1024, (sampleRate + 100) / 200) (5 ms)}.  MX_ERR_INVALID (p untouched) for sampleRate out
+ * of range or NULL. */
+int mx_limit_params_default(int sampleRate, mx_limit_params *p);
+/* The limited take as a new audio object (zeroed pads, as mx_audio_gain_dev; release it with mx_audio_free) and, where
+ * d_pcm16 is not NULL, its n int16 samples in HBM.  params NULL: the defaults.  Asynchronous on the context's stream.
+ * MX_ERR_INVALID, before any launch and with *out untouched, for sampleRate out of range, NULLs, c not normal or outside
+ * (0, 1], A outside [1, 1024].  n = 0 gives an empty object. */
+int mx_audio_limit_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params *params, mx_audio **out,
+                       int16_t *d_pcm16);
+/* Same with a host pcm16_out (n int16, may be NULL).  Blocks. */
+int mx_audio_limit(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params *params, mx_audio **out, int16_t *pcm16_out);
+/* Loudness range (EBU Tech 3342; host, binary64) of mx_loud_step records, steps[0] = step 0.  Short-term mean squares z_k =
+ * (the energies of steps b - 299 .. b, summed ascending) / (300 S) at b = 299 + 10 k, all 300 steps full: 3 s every 100 ms.
+ * A z that is not finite is left out and counted (bad).  Absolute gate: z > 0x1.f791ec6e1d5b7p-24 (mx_loudness_integrated's);
+ * relative gate: z > 0.01 * ((the z that pass the absolute gate, summed ascending) / their count), -20 LU.  The m survivors
+ * sorted ascending:  low = sorted[floor((m - 1) * 0.10 + 0.5)], high = sorted[floor((m - 1) * 0.95 + 0.5)],
+ *   lra = 10 log10(high / low), low_lufs / high_lufs = -0.691 + 10 log10(low / high);  m = 0: lra 0, low_lufs = high_lufs = -inf.
+ * values = the z_k that exist (bad ones included), gated = m.  MX_ERR_INVALID as mx_loudness_integrated. */
+typedef struct mx_loudness_range_result {
+  double lra, low_lufs, high_lufs;
+  int64_t values, gated, bad;
+} mx_loudness_range_result;
+int mx_loudness_range(const mx_loud_step *steps, int64_t nsteps, int sampleRate, mx_loudness_range_result *out);
+/* mx_normalize_gain with a measured true peak in place of m->peak and the ceiling in dBTP:
+ *   amp = (float)min(10^((target_lufs - integrated) / 20), 10^(ceiling_dbtp / 20) / true_peak).
+ * MX_ERR_INVALID (amp untouched) when integrated is not finite, true_peak is 0 or not finite, or an argument is not finite. */
+int mx_normalize_gain_tp(const mx_loudness *m, float true_peak, double target_lufs, double ceiling_dbtp, float *amp);
 
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0

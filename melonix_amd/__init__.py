@@ -22,6 +22,7 @@ from ._capi import GAIN_POINT_DTYPE, SIB_FEAT_DTYPE, SIBILANT_DTYPE  # noqa: F40
 from ._capi import CHROMA_COLS, CHROMA_JOB_DTYPE, KEY_DTYPE, KEY_WINDOW_DTYPE  # noqa: F401
 from ._capi import CONTOUR_NONE, CONTOUR_REC_DTYPE, CONTOUR_SPAN_DTYPE, CONTOUR_STAT_DTYPE  # noqa: F401
 from ._capi import LOUD_GROUP_STEPS, LOUD_STEP_DTYPE  # noqa: F401
+from ._capi import TP_STEP_DTYPE  # noqa: F401
 
 __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_host", "schedule_build",
            "save_wav", "column_range", "time2sample", "sample2time", "time2pitchbend", "duration",
@@ -37,7 +38,8 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "CONTOUR_NONE", "CONTOUR_SPAN_DTYPE", "CONTOUR_REC_DTYPE", "CONTOUR_STAT_DTYPE", "contour_params_default",
            "bend_params_default", "contour_spans", "contour_vibrato", "contour_bend", "psola_plan_bend", "psola_plan_formant_bend",
            "LOUD_STEP_DTYPE", "LOUD_GROUP_STEPS", "level_params_default", "loudness_step_count", "loudness_coeffs", "loudness_curve",
-           "loudness_integrated", "note_loudness", "level_gain_points", "normalize_gain"]
+           "loudness_integrated", "note_loudness", "level_gain_points", "normalize_gain",
+           "TP_STEP_DTYPE", "true_peak_oversampling", "true_peak_taps", "limit_params_default", "loudness_range", "normalize_gain_tp"]
 
 
 # The two pointer forms of an optional argument.  New wrappers use these: _opt for a host array, _dev for a device address.
@@ -293,10 +295,10 @@ class Context:
         _call("mx_ctx_synchronize", self.handle)
 
     # ---- audio ----
-    def _audio(self, n: int, name: str, *args, keepalive=None) -> Audio:
-        """name(ctx, *args, &handle) -> the new Audio of n samples."""
+    def _audio(self, n: int, name: str, *args, keepalive=None, tail=()) -> Audio:
+        """name(ctx, *args, &handle, *tail) -> the new Audio of n samples."""
         h = C.c_void_p()
-        _call(name, self.handle, *args, C.byref(h))
+        _call(name, self.handle, *args, C.byref(h), *tail)
         return Audio(self, h, n, keepalive)
 
     def upload(self, wav) -> Audio:
@@ -592,6 +594,53 @@ class Context:
 
     def normalize_gain(self, measured: dict, target_lufs: float = -23.0, ceiling_db: float = -1.0) -> float:
         return normalize_gain(measured, target_lufs, ceiling_db)
+
+    # ---- true peak, look-ahead limiter, loudness range (build-defined; include/melonix_amd.h) ----
+    def true_peak_steps(self, audio: Audio, sr: int, first_step: int = 0, nsteps: int | None = None):
+        """-> TP_STEP_DTYPE records (true peak, sample peak) of the 10 ms steps [first_step, first_step + nsteps) (nsteps None:
+        to the end of the file)."""
+        nsteps = loudness_step_count(audio.n, sr) - first_step if nsteps is None else nsteps
+        out = np.empty(max(nsteps, 0), dtype=TP_STEP_DTYPE)
+        _call("mx_true_peak_steps", self.handle, audio.handle, sr, first_step, nsteps, _ptr(out))
+        return out
+
+    def true_peak_steps_dev(self, audio: Audio, sr: int, first_step: int, nsteps: int, d_steps: int):
+        """The records stay in HBM at d_steps (8 bytes a step, 8-byte aligned); asynchronous on the context's stream."""
+        _call("mx_true_peak_steps_dev", self.handle, audio.handle, sr, first_step, nsteps, _dev(d_steps))
+
+    def true_peak(self, audio: Audio, sr: int):
+        """The whole take -> (true peak, sample peak), amplitudes as float32 values."""
+        t, s = C.c_float(), C.c_float()
+        _call("mx_true_peak_measure", self.handle, audio.handle, sr, C.byref(t), C.byref(s))
+        return np.float32(t.value), np.float32(s.value)
+
+    @staticmethod
+    def _limit_params(sr: int, ceiling_db: float, lookahead, ceiling_amp):
+        amp = np.float32(10.0 ** (ceiling_db / 20.0)) if ceiling_amp is None else np.float32(ceiling_amp)
+        d = limit_params_default(sr)  # (raises for a sample rate out of range)
+        return C.byref(_capi.LimitParams(float(amp), int(d["lookahead"] if lookahead is None else lookahead)))
+
+    def limit(self, audio: Audio, sr: int, ceiling_db: float = -1.0, lookahead: int | None = None, pcm16: bool = False,
+              ceiling_amp=None):
+        """A new Audio: `audio` through the look-ahead limiter under a ceiling of ceiling_db dBTP (ceiling_amp: the amplitude
+        itself, as a float32) with a look-ahead of `lookahead` samples (None: the default, 5 ms).  pcm16: -> (Audio, the int16
+        samples).  Blocks."""
+        out = np.empty(audio.n, dtype=np.int16) if pcm16 else None
+        b = self._audio(audio.n, "mx_audio_limit", audio.handle, sr, self._limit_params(sr, ceiling_db, lookahead, ceiling_amp),
+                        tail=(_ptr(out),))
+        return (b, out) if pcm16 else b
+
+    def limit_dev(self, audio: Audio, sr: int, ceiling_db: float = -1.0, lookahead: int | None = None, d_pcm16: int | None = None,
+                  ceiling_amp=None) -> Audio:
+        """The same with the int16 samples (d_pcm16 None: none) in HBM; asynchronous on the context's stream."""
+        return self._audio(audio.n, "mx_audio_limit_dev", audio.handle, sr, self._limit_params(sr, ceiling_db, lookahead, ceiling_amp),
+                           tail=(_dev(d_pcm16),))
+
+    def loudness_range(self, steps, sr: int) -> dict:
+        return loudness_range(steps, sr)
+
+    def normalize_gain_tp(self, measured: dict, true_peak: float, target_lufs: float = -23.0, ceiling_dbtp: float = -1.0) -> float:
+        return normalize_gain_tp(measured, true_peak, target_lufs, ceiling_dbtp)
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
     def tempo_smooth(self, flux, width: int = 4):
@@ -1173,4 +1222,40 @@ def normalize_gain(measured: dict, target_lufs: float = -23.0, ceiling_db: float
     its sample peak at most ceiling_db dBFS."""
     amp = C.c_float()
     _call("mx_normalize_gain", C.byref(_capi.Loudness(**measured)), float(target_lufs), float(ceiling_db), C.byref(amp))
+    return amp.value
+
+
+# ---- true peak, limiter parameters, loudness range, export gain under a true-peak ceiling (host; build-defined) ----
+def true_peak_oversampling(sr: int) -> int:
+    """L: 4 below 88.2 kHz, 2 below 176.4 kHz, else 1; 0 for a sample rate outside [8000, 384000]."""
+    return int(_capi.lib().mx_true_peak_oversampling(int(sr)))
+
+
+def true_peak_taps():
+    """The interpolation taps -> float32[3, 12]: offsets 1/4, 1/2, 3/4, d = -5 .. 6."""
+    out = np.empty((3, 12), dtype=np.float32)
+    _call("mx_true_peak_taps", _ptr(out))
+    return out
+
+
+def limit_params_default(sr: int) -> dict:
+    """The limiter's defaults at sr: a ceiling amplitude of -1 dBTP, a look-ahead of 5 ms (at most 1024 samples)."""
+    p = _capi.LimitParams()
+    _call("mx_limit_params_default", int(sr), C.byref(p))
+    return _fields(p)
+
+
+def loudness_range(steps, sr: int) -> dict:
+    """EBU Tech 3342 loudness range of LOUD_STEP_DTYPE records -> dict of mx_loudness_range_result's fields."""
+    steps = _records(steps, LOUD_STEP_DTYPE)
+    r = _capi.LoudnessRange()
+    _call("mx_loudness_range", _opt(steps), len(steps), int(sr), C.byref(r))
+    return _fields(r)
+
+
+def normalize_gain_tp(measured: dict, true_peak: float, target_lufs: float = -23.0, ceiling_dbtp: float = -1.0) -> float:
+    """normalize_gain with a measured true peak (Context.true_peak) in place of the sample peak, the ceiling in dBTP."""
+    amp = C.c_float()
+    _call("mx_normalize_gain_tp", C.byref(_capi.Loudness(**measured)), float(true_peak), float(target_lufs), float(ceiling_dbtp),
+          C.byref(amp))
     return amp.value

@@ -199,6 +199,19 @@ class LevelParams(C.Structure):
     _fields_ = [("raise", C.c_double), ("lower", C.c_double), ("max_db", C.c_double)]
 
 
+class TpStep(C.Structure):
+    _fields_ = [("true_peak", C.c_float), ("sample_peak", C.c_float)]
+
+
+class LimitParams(C.Structure):
+    _fields_ = [("ceiling_amp", C.c_float), ("lookahead", C.c_int32)]
+
+
+class LoudnessRange(C.Structure):
+    _fields_ = [("lra", C.c_double), ("low_lufs", C.c_double), ("high_lufs", C.c_double), ("values", C.c_int64),
+                ("gated", C.c_int64), ("bad", C.c_int64)]
+
+
 # the C type of every record class, in the order of include/melonix_amd.h.  A record is declared here once, as its class: the
 # field names are the header's, the numpy dtypes below are derived from the classes, and tests/test_abi.py compares every
 # class's size, field offsets and field sizes with what a C compiler makes of the header.  (mx_chroma_rec has no class: a
@@ -214,7 +227,8 @@ RECORDS = {
     "mx_chroma_params": ChromaParams, "mx_chroma_job": ChromaJob, "mx_key": Key, "mx_key_window": KeyWindow,
     "mx_contour_span": ContourSpan, "mx_contour_params": ContourParams, "mx_contour_rec": ContourRec,
     "mx_contour_stat": ContourStat, "mx_vibrato": Vibrato, "mx_bend_params": BendParams, "mx_loud_step": LoudStep,
-    "mx_loudness": Loudness, "mx_level_params": LevelParams,
+    "mx_loudness": Loudness, "mx_level_params": LevelParams, "mx_tp_step": TpStep, "mx_limit_params": LimitParams,
+    "mx_loudness_range_result": LoudnessRange,
 }
 
 PITCH_DTYPE, STEP_DTYPE, MARKER_DTYPE = np.dtype(Pitch), np.dtype(Step), np.dtype(Marker)
@@ -230,6 +244,7 @@ CONTOUR_NONE = -2 ** 31  # MX_CONTOUR_NONE: an unvoiced frame's cents, the smoot
 CONTOUR_SPAN_DTYPE, CONTOUR_REC_DTYPE, CONTOUR_STAT_DTYPE = np.dtype(ContourSpan), np.dtype(ContourRec), np.dtype(ContourStat)
 LOUD_STEP_DTYPE = np.dtype(LoudStep)
 LOUD_GROUP_STEPS = 10  # G: steps per group, the unit mx_loudness_steps is asked in
+TP_STEP_DTYPE = np.dtype(TpStep)
 
 # name -> (restype, argtypes); kept in the order of include/melonix_amd.h
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -401,6 +416,16 @@ SIGNATURES = {
     "mx_level_params_default": (None, [C.POINTER(LevelParams)]),
     "mx_level_gain_points": (_i, [_vp, _i64, _vp, C.POINTER(LevelParams), _vp, C.POINTER(_d)]),
     "mx_normalize_gain": (_i, [C.POINTER(Loudness), _d, _d, C.POINTER(_f)]),
+    "mx_true_peak_oversampling": (_i, [_i]),
+    "mx_true_peak_taps": (_i, [_vp]),
+    "mx_true_peak_steps_dev": (_i, [_vp, _vp, _i, _i64, _i64, _vp]),
+    "mx_true_peak_steps": (_i, [_vp, _vp, _i, _i64, _i64, _vp]),
+    "mx_true_peak_measure": (_i, [_vp, _vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    "mx_limit_params_default": (_i, [_i, C.POINTER(LimitParams)]),
+    "mx_audio_limit_dev": (_i, [_vp, _vp, _i, C.POINTER(LimitParams), C.POINTER(_vp), _vp]),
+    "mx_audio_limit": (_i, [_vp, _vp, _i, C.POINTER(LimitParams), C.POINTER(_vp), _vp]),
+    "mx_loudness_range": (_i, [_vp, _i64, _i, C.POINTER(LoudnessRange)]),
+    "mx_normalize_gain_tp": (_i, [C.POINTER(Loudness), _f, _d, _d, C.POINTER(_f)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

@@ -59,6 +59,9 @@ UNITS = [
     # build-defined loudness records: the K-weighting recurrence in binary64, every product rounded before its sum
     # (loudness_core.h), bit for bit numpy's
     ("loudness_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined true-peak records and look-ahead limiter: binary32 taps with every product rounded before its sum, integers
+    # from the peak to the gain (truepeak_core.h), bit for bit numpy's
+    ("truepeak_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -75,6 +78,7 @@ UNITS = [
     ("capi_key.cpp", "hip", []),
     ("capi_contour.cpp", "hip", []),
     ("capi_loudness.cpp", "hip", []),
+    ("capi_truepeak.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),

@@ -1,0 +1,69 @@
+// mastering.cpp — melonix::Mastering over the C-ABI (see mastering.hpp).  A failed call leaves empty vectors, the way the rest
+// of the facade maps errors.
+#include "mastering.hpp"
+
+#include <cmath>
+#include <limits>
+
+#include "capi-glue.hpp"
+
+namespace melonix {
+
+Mastering::Mastering(std::span<const float> wav, int sampleRate, int device)
+    : sampleRate(sampleRate), device_(device), wav_(wav.begin(), wav.end()) {
+  // a step every S samples: the file's steps are its frames at hop S (no S for a sample rate out of range: nothing measured)
+  const int S = mx_loudness_step_count(1, sampleRate) == 1 ? (sampleRate + 50) / 100 : 0;
+  std::vector<mx_loud_step> steps;
+  good = glue::fileTrack(wav, S, device, steps, [&](mx_ctx *ctx, const mx_audio *audio, int64_t count, mx_loud_step *out) {
+    if (const int rc = mx_loudness_steps(ctx, audio, sampleRate, 0, (count + 9) / 10, out)) return rc;
+    if (const int rc = mx_loudness_integrated(out, count, sampleRate, &loudness_)) return rc;
+    if (const int rc = mx_loudness_range(out, count, sampleRate, &range_)) return rc;
+    peaks_.resize((size_t)count);
+    if (const int rc = mx_true_peak_steps(ctx, audio, sampleRate, 0, count, peaks_.data())) return rc;
+    return mx_true_peak_measure(ctx, audio, sampleRate, &truePeak_, &samplePeak_);
+  });
+  if (!good) {
+    loudness_ = mx_loudness{};
+    range_ = mx_loudness_range_result{};
+    peaks_.clear();
+    truePeak_ = samplePeak_ = 0.f;
+  }
+}
+
+double Mastering::truePeakDb() const {
+  return truePeak_ > 0.f ? 20.0 * std::log10((double)truePeak_) : -std::numeric_limits<double>::infinity();
+}
+
+std::vector<int16_t> Mastering::finish(double targetLufs, double ceilingDbtp, double lookaheadMs) const {
+  float amp = 1.f;
+  // (a ceiling far above any take: the loudness term alone)
+  if (!good || mx_normalize_gain_tp(&loudness_, truePeak_, targetLufs, 200.0, &amp) != MX_OK) return {};
+  mx_limit_params p;
+  if (mx_limit_params_default(sampleRate, &p) != MX_OK || !std::isfinite(ceilingDbtp) || !std::isfinite(lookaheadMs)) return {};
+  p.ceiling_amp = (float)std::pow(10.0, ceilingDbtp / 20.0);
+  if (lookaheadMs > 0.0) {
+    const double a = std::floor(lookaheadMs * (double)sampleRate / 1000.0 + 0.5);
+    p.lookahead = a < 1.0 ? 1 : a > 1024.0 ? 1024 : (int32_t)a;
+  }
+  std::vector<int16_t> out(wav_.size());
+  mx_ctx *ctx = nullptr;
+  if (mx_ctx_create(device_, &ctx) != MX_OK) return {};
+  mx_audio *src = nullptr, *gained = nullptr, *limited = nullptr;
+  const mx_gain_point point{0, amp};
+  bool done = mx_audio_upload(ctx, wav_.data(), (int64_t)wav_.size(), &src) == MX_OK;
+  done = done && mx_audio_gain(ctx, src, &point, 1, &gained) == MX_OK;
+  done = done && mx_audio_limit(ctx, gained, sampleRate, &p, &limited, out.data()) == MX_OK;
+  mx_audio_free(ctx, limited);
+  mx_audio_free(ctx, gained);
+  mx_audio_free(ctx, src);
+  mx_ctx_destroy(ctx);
+  if (!done) out.clear();
+  return out;
+}
+
+bool Mastering::exportWav(const std::string &path, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
+  const std::vector<int16_t> pcm = finish(targetLufs, ceilingDbtp, lookaheadMs);
+  return !pcm.empty() && mx_save_wav(path.c_str(), pcm.data(), (int64_t)pcm.size(), sampleRate, 0) == MX_OK;
+}
+
+}  // namespace melonix

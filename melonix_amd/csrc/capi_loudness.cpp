@@ -1,5 +1,5 @@
 // capi_loudness.cpp — loudness records (loudness_kernels.hip), the windowed curve, BS.1770 gating, note loudness, the levelling
-// points and the export gain (loudness_logic.cpp): BUILD-DEFINED, the reference has none of it.  One unit of the C-ABI
+// points, the loudness range and the export gains (loudness_logic.cpp): BUILD-DEFINED, the reference has none of it.  One unit of the C-ABI
 // implementation behind include/melonix_amd.h (see capi_internal.h).
 #include "capi_internal.h"
 #include "loudness_core.h"
@@ -181,6 +181,26 @@ int mx_normalize_gain(const mx_loudness *m, double target_lufs, double ceiling_d
     if (!std::isfinite(m->peak) || !(m->peak > 0.f)) return fail(MX_ERR_INVALID, "peak %g must be finite and > 0", (double)m->peak);
     if (!std::isfinite(target_lufs) || !std::isfinite(ceiling_db)) return fail(MX_ERR_INVALID, "target and ceiling must be finite");
     *amp = (float)normalize_amp(m->integrated, (double)m->peak, target_lufs, ceiling_db);
+    return MX_OK;
+  });
+}
+
+int mx_loudness_range(const mx_loud_step *steps, int64_t nsteps, int sampleRate, mx_loudness_range_result *out) {
+  return mx_guard([&]() -> int {
+    if (const int rc = list_check(steps, nsteps, sampleRate)) return rc;
+    if (!out) return fail(MX_ERR_INVALID, "null output");
+    loudness_range(steps, nsteps, loud::geometry(0, sampleRate).S, out);
+    return MX_OK;
+  });
+}
+
+int mx_normalize_gain_tp(const mx_loudness *m, float true_peak, double target_lufs, double ceiling_dbtp, float *amp) {
+  return mx_guard([&]() -> int {
+    if (!m || !amp) return fail(MX_ERR_INVALID, "null argument");
+    if (!std::isfinite(m->integrated)) return fail(MX_ERR_INVALID, "the integrated loudness is not finite");
+    if (!std::isfinite(true_peak) || !(true_peak > 0.f)) return fail(MX_ERR_INVALID, "true peak %g must be finite and > 0", (double)true_peak);
+    if (!std::isfinite(target_lufs) || !std::isfinite(ceiling_dbtp)) return fail(MX_ERR_INVALID, "target and ceiling must be finite");
+    *amp = (float)normalize_amp(m->integrated, (double)true_peak, target_lufs, ceiling_dbtp);
     return MX_OK;
   });
 }

@@ -256,6 +256,30 @@ struct LoudnessArgs {
   mx_loud_step *out;
 };
 hipError_t launch_loudness_steps(const LoudnessArgs &a, hipStream_t s);
+// Build-defined true-peak records (truepeak_kernels.hip; definition: include/melonix_amd.h, arithmetic: truepeak_core.h).  Steps
+// [first_step, first_step + nsteps) of the take, all inside it, S and L the geometry of the sample rate: checked by the caller.
+// out: the record of step first_step on, 8-byte aligned.
+struct TruePeakArgs {
+  const float *image;  // padded image (the samples outside the file are taken as zeros whatever the pads hold)
+  int64_t n;
+  int S, L;
+  int64_t first_step, nsteps;
+  mx_tp_step *out;
+};
+hipError_t launch_true_peak_steps(const TruePeakArgs &a, hipStream_t s);
+// Build-defined look-ahead limiter (the same unit).  dst: samples [0, n) of the new object (16-byte aligned, as the image);
+// pcm16: n int16 or null.  ceiling a normal binary32 in (0, 1], lookahead in [1, 1024]: checked by the caller.  No store
+// outside [0, n) of either output.
+struct LimitArgs {
+  const float *image;  // padded image, as above
+  int64_t n;
+  int L;
+  float ceiling;
+  int lookahead;
+  float *dst;
+  int16_t *pcm16;
+};
+hipError_t launch_audio_limit(const LimitArgs &a, hipStream_t s);
 // Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
 // count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
 // range (the caller's check) gives a wrong record and nothing worse.

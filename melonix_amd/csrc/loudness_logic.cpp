@@ -108,6 +108,41 @@ void loudness_integrated(const mx_loud_step *steps, int64_t nsteps, int S, mx_lo
   *out = m;
 }
 
+void loudness_range(const mx_loud_step *steps, int64_t nsteps, int S, mx_loudness_range_result *out) {
+  mx_loudness_range_result r{};
+  const double den = (double)((int64_t)kShortSteps * S);
+  std::vector<double> z;
+  int64_t full = 0;  // full steps in a row up to and including b, as loudness_curve counts them
+  for (int64_t b = 0; b < nsteps; ++b) {
+    full = steps[b].samples == S ? full + 1 : 0;
+    if (b < kShortSteps - 1 || (b - (kShortSteps - 1)) % kBlockHop != 0 || full < kShortSteps) continue;
+    ++r.values;
+    const double zk = energy_sum(steps, b - kShortSteps + 1, kShortSteps) / den;
+    if (!std::isfinite(zk)) ++r.bad;
+    else z.push_back(zk);
+  }
+  double sum_abs = 0.0;
+  int64_t passed_abs = 0;
+  for (double zk : z)
+    if (zk > kAbsGate) sum_abs += zk, ++passed_abs;
+  std::vector<double> kept;
+  if (passed_abs > 0) {
+    const double gate = 0.01 * (sum_abs / (double)passed_abs);
+    for (double zk : z)
+      if (zk > kAbsGate && zk > gate) kept.push_back(zk);
+  }
+  std::sort(kept.begin(), kept.end());
+  r.gated = (int64_t)kept.size();
+  r.lra = 0.0, r.low_lufs = r.high_lufs = -kInf;
+  if (r.gated > 0) {
+    const double low = kept[(size_t)std::floor((double)(r.gated - 1) * 0.10 + 0.5)];
+    const double high = kept[(size_t)std::floor((double)(r.gated - 1) * 0.95 + 0.5)];
+    r.lra = 10.0 * std::log10(high / low);
+    r.low_lufs = lufs(low), r.high_lufs = lufs(high);
+  }
+  *out = r;
+}
+
 bool note_loudness(const mx_loud_step *steps, int64_t nsteps, int S, const mx_note *notes, int64_t nnotes, double *out, int64_t *bad) {
   const int64_t total = nsteps > 0 ? (nsteps - 1) * S + steps[nsteps - 1].samples : 0;  // the samples the records cover
   for (int64_t i = 0; i < nnotes; ++i) {
