@@ -79,6 +79,7 @@ UNITS = [
     ("capi_contour.cpp", "hip", []),
     ("capi_loudness.cpp", "hip", []),
     ("capi_truepeak.cpp", "hip", []),
+    ("capi_audio.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),

@@ -27,21 +27,53 @@ std::vector<Out> taken(T *v, int64_t n) {
   return out;
 }
 
-// One per-frame track over a whole file: a context on `device`, the upload, `call(ctx, audio, frames, out.data()) -> status`
-// over the file's frames at `hop`, both handles released.  -> whether the track is there; `out` is empty where it is not.
+// What a call of the facade holds for its own length: a context on `device`, the upload of a take (the second constructor, or
+// upload()), and the audio objects the call makes of it (`made`, filled by the caller).  `ok`: everything asked for so far is
+// there.  The destructor frees what is there: made[1], made[0], the upload, then the context.
+struct Session {
+  mx_ctx *ctx = nullptr;
+  mx_audio *audio = nullptr, *made[2] = {};
+  bool ok;
+  explicit Session(int device) : ok(mx_ctx_create(device, &ctx) == MX_OK) {}
+  Session(int device, std::span<const float> wav) : Session(device) { upload(wav); }
+  Session(const Session &) = delete;
+  Session &operator=(const Session &) = delete;
+  bool upload(std::span<const float> wav) {
+    return ok = ok && mx_audio_upload(ctx, wav.data(), (int64_t)wav.size(), &audio) == MX_OK;
+  }
+  ~Session() {
+    for (mx_audio *a : {made[1], made[0], audio})
+      if (a) mx_audio_free(ctx, a);
+    if (ctx) mx_ctx_destroy(ctx);
+  }
+};
+
+// One per-frame track over a whole file: a session on `device`, `call(ctx, audio, frames, out.data()) -> status` over the
+// file's frames at `hop`.  -> whether the track is there; `out` is empty where it is not.
 template <class T, class Call>
 bool fileTrack(std::span<const float> wav, int hop, int device, std::vector<T> &out, Call call) {
-  mx_ctx *ctx = nullptr;
-  if (mx_ctx_create(device, &ctx) != MX_OK) return false;
-  mx_audio *audio = nullptr;
-  const int64_t n = (int64_t)wav.size(), frames = mx_frame_count(n, hop);
-  const bool up = mx_audio_upload(ctx, wav.data(), n, &audio) == MX_OK;
+  Session s(device);
+  if (!s.ok) return false;
+  const int64_t frames = mx_frame_count((int64_t)wav.size(), hop);
+  const bool up = s.upload(wav);
   if (up && frames >= 0) out.resize((size_t)frames);
-  const bool good = up && frames >= 0 && call(ctx, audio, frames, out.data()) == MX_OK;
+  const bool good = up && frames >= 0 && call(s.ctx, s.audio, frames, out.data()) == MX_OK;
   if (!good) out.clear();
-  if (up) mx_audio_free(ctx, audio);
-  mx_ctx_destroy(ctx);
   return good;
+}
+
+// S, the samples of the 10 ms step of the loudness and true-peak records: a file's steps are its frames at hop S (0 for a sample
+// rate the library refuses: no frames)
+inline int stepSamples(int sampleRate) { return mx_loudness_step_count(1, sampleRate) == 1 ? (sampleRate + 50) / 100 : 0; }
+
+// `wav` through mx_audio_gain with `points`, on a session of its own; empty where a call fails
+inline std::vector<float> gained(std::span<const float> wav, int device, const std::vector<mx_gain_point> &points) {
+  std::vector<float> out(wav.size());
+  Session s(device, wav);
+  const bool done = s.ok && mx_audio_gain(s.ctx, s.audio, points.data(), (int64_t)points.size(), &s.made[0]) == MX_OK &&
+                    mx_audio_download(s.ctx, s.made[0], 0, (int64_t)out.size(), out.data()) == MX_OK;
+  if (!done) out.clear();
+  return out;
 }
 
 }  // namespace melonix::glue

@@ -9,7 +9,7 @@ namespace melonix {
 LoudnessTrack::LoudnessTrack(std::span<const float> wav, int sampleRate, int device)
     : sampleRate(sampleRate), device_(device), wav_(wav.begin(), wav.end()) {
   // a step every S samples: the file's steps are its frames at hop S (no S for a sample rate out of range: no track)
-  const int S = mx_loudness_step_count(1, sampleRate) == 1 ? (sampleRate + 50) / 100 : 0;
+  const int S = glue::stepSamples(sampleRate);
   good = glue::fileTrack(wav, S, device, steps_, [&](mx_ctx *ctx, const mx_audio *audio, int64_t steps, mx_loud_step *out) {
     if (const int rc = mx_loudness_steps(ctx, audio, sampleRate, 0, (steps + 9) / 10, out)) return rc;
     return mx_loudness_integrated(out, steps, sampleRate, &summary_);
@@ -32,20 +32,7 @@ std::vector<double> LoudnessTrack::noteLoudness(const std::vector<mx_note> &note
 
 mx_level_params LoudnessTrack::params() { return glue::defaults(mx_level_params_default); }
 
-std::vector<float> LoudnessTrack::gained(const std::vector<mx_gain_point> &points) const {
-  std::vector<float> out(wav_.size());
-  mx_ctx *ctx = nullptr;
-  if (mx_ctx_create(device_, &ctx) != MX_OK) return {};
-  mx_audio *src = nullptr, *dst = nullptr;
-  bool done = mx_audio_upload(ctx, wav_.data(), (int64_t)wav_.size(), &src) == MX_OK;
-  done = done && mx_audio_gain(ctx, src, points.data(), (int64_t)points.size(), &dst) == MX_OK;
-  done = done && mx_audio_download(ctx, dst, 0, (int64_t)out.size(), out.data()) == MX_OK;
-  mx_audio_free(ctx, dst);
-  mx_audio_free(ctx, src);
-  mx_ctx_destroy(ctx);
-  if (!done) out.clear();
-  return out;
-}
+std::vector<float> LoudnessTrack::gained(const std::vector<mx_gain_point> &points) const { return glue::gained(wav_, device_, points); }
 
 std::vector<float> LoudnessTrack::levelled(const std::vector<mx_note> &notes, const mx_level_params &p) const {
   const std::vector<double> lufs = noteLoudness(notes);

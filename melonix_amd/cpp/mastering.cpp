@@ -12,7 +12,7 @@ namespace melonix {
 Mastering::Mastering(std::span<const float> wav, int sampleRate, int device)
     : sampleRate(sampleRate), device_(device), wav_(wav.begin(), wav.end()) {
   // a step every S samples: the file's steps are its frames at hop S (no S for a sample rate out of range: nothing measured)
-  const int S = mx_loudness_step_count(1, sampleRate) == 1 ? (sampleRate + 50) / 100 : 0;
+  const int S = glue::stepSamples(sampleRate);
   std::vector<mx_loud_step> steps;
   good = glue::fileTrack(wav, S, device, steps, [&](mx_ctx *ctx, const mx_audio *audio, int64_t count, mx_loud_step *out) {
     if (const int rc = mx_loudness_steps(ctx, audio, sampleRate, 0, (count + 9) / 10, out)) return rc;
@@ -46,17 +46,10 @@ std::vector<int16_t> Mastering::finish(double targetLufs, double ceilingDbtp, do
     p.lookahead = a < 1.0 ? 1 : a > 1024.0 ? 1024 : (int32_t)a;
   }
   std::vector<int16_t> out(wav_.size());
-  mx_ctx *ctx = nullptr;
-  if (mx_ctx_create(device_, &ctx) != MX_OK) return {};
-  mx_audio *src = nullptr, *gained = nullptr, *limited = nullptr;
+  glue::Session s(device_, wav_);
   const mx_gain_point point{0, amp};
-  bool done = mx_audio_upload(ctx, wav_.data(), (int64_t)wav_.size(), &src) == MX_OK;
-  done = done && mx_audio_gain(ctx, src, &point, 1, &gained) == MX_OK;
-  done = done && mx_audio_limit(ctx, gained, sampleRate, &p, &limited, out.data()) == MX_OK;
-  mx_audio_free(ctx, limited);
-  mx_audio_free(ctx, gained);
-  mx_audio_free(ctx, src);
-  mx_ctx_destroy(ctx);
+  const bool done = s.ok && mx_audio_gain(s.ctx, s.audio, &point, 1, &s.made[0]) == MX_OK &&
+                    mx_audio_limit(s.ctx, s.made[0], sampleRate, &p, &s.made[1], out.data()) == MX_OK;
   if (!done) out.clear();
   return out;
 }

@@ -42,13 +42,12 @@ mx_tempo_params OnsetTrack::tempoParams() { return glue::defaults(mx_tempo_param
 bool OnsetTrack::estimate(const mx_tempo_params &p, mx_tempo &t, std::vector<mx_tempo_window> *windows) const {
   t = mx_tempo{};
   if (windows) windows->clear();
-  mx_ctx *ctx = nullptr;
-  if (!good || mx_ctx_create(device_, &ctx) != MX_OK) return false;
+  if (!good) return false;
+  glue::Session s(device_);
   mx_tempo_window *v = nullptr;
   int64_t n = 0;
-  const bool done = mx_tempo_from_flux(ctx, flux_.data(), (int64_t)flux_.size(), sampleRate, hop_, 0, &p, &t, windows ? &v : nullptr,
+  const bool done = s.ok && mx_tempo_from_flux(s.ctx, flux_.data(), (int64_t)flux_.size(), sampleRate, hop_, 0, &p, &t, windows ? &v : nullptr,
                                        windows ? &n : nullptr) == MX_OK;
-  mx_ctx_destroy(ctx);
   if (!done) t = mx_tempo{};
   else if (windows) *windows = glue::taken<mx_tempo_window>(v, n);
   return done;

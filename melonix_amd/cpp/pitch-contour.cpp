@@ -63,16 +63,11 @@ std::vector<float> PitchContour::correct(float drift, float vibrato, std::span<c
   if (len < 0) return {};
   mx_psola_params pp = glue::defaults(mx_psola_params_default);
   pp.threshold = kVoicing;
-  mx_ctx *ctx = nullptr;
-  if (mx_ctx_create(device_, &ctx) != MX_OK) return {};
-  mx_audio *audio = nullptr;
   std::vector<float> pcm((size_t)len);
-  const bool up = mx_audio_upload(ctx, wav_.data(), n, &audio) == MX_OK;
-  const bool done = up && mx_psola_render_bend(ctx, audio, sampleRate, hop_, track.data(), (int64_t)track.size(), &pp, m,
-                                               (int)markers.size(), points.data(), (int)points.size(), curve.data(), pcm.data(),
-                                               nullptr) == MX_OK;
-  if (up) mx_audio_free(ctx, audio);
-  mx_ctx_destroy(ctx);
+  glue::Session s(device_, wav_);
+  const bool done = s.ok && mx_psola_render_bend(s.ctx, s.audio, sampleRate, hop_, track.data(), (int64_t)track.size(), &pp, m,
+                                                 (int)markers.size(), points.data(), (int)points.size(), curve.data(), pcm.data(),
+                                                 nullptr) == MX_OK;
   if (!done) pcm.clear();
   return pcm;
 }

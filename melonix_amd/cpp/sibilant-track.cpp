@@ -38,19 +38,7 @@ std::vector<float> SibilantTrack::balanced(float db, int rampSamples) const {
   mx_gain_point *pts = nullptr;
   int64_t npts = 0;
   if (mx_sibilant_gain_points(s.data(), (int64_t)s.size(), (double)db, rampSamples, (int64_t)wav_.size(), &pts, &npts) != MX_OK) return {};
-  const std::vector<mx_gain_point> points = glue::taken<mx_gain_point>(pts, npts);
-  std::vector<float> out(wav_.size());
-  mx_ctx *ctx = nullptr;
-  if (mx_ctx_create(device_, &ctx) != MX_OK) return {};
-  mx_audio *src = nullptr, *dst = nullptr;
-  bool done = mx_audio_upload(ctx, wav_.data(), (int64_t)wav_.size(), &src) == MX_OK;
-  done = done && mx_audio_gain(ctx, src, points.data(), (int64_t)points.size(), &dst) == MX_OK;
-  done = done && mx_audio_download(ctx, dst, 0, (int64_t)out.size(), out.data()) == MX_OK;
-  mx_audio_free(ctx, dst);
-  mx_audio_free(ctx, src);
-  mx_ctx_destroy(ctx);
-  if (!done) out.clear();
-  return out;
+  return glue::gained(wav_, device_, glue::taken<mx_gain_point>(pts, npts));
 }
 
 }  // namespace melonix

@@ -1,0 +1,165 @@
+// capi_audio.cpp — the audio objects made from another one on the device: the source gain (gain_kernels.hip) and the look-ahead
+// limiter (truepeak_kernels.hip), and the download of an audio object's samples: BUILD-DEFINED, the reference has none of it.  One
+// unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).  (mx_audio_upload, _wrap_device, _free:
+// capi_ctx.cpp.)
+#include "capi_internal.h"
+#include "sibilant_logic.h"
+#include "truepeak_core.h"
+
+using namespace mx;
+
+namespace {
+
+// A new audio object of a's length at *out: zeroed pads, and the samples that `fill(dst) -> hipError_t` queues behind the two
+// clears (not called for an empty take).  Queued on the context's stream; nothing is left allocated where it fails.  `what` names
+// the call in a device error.
+template <class F>
+int derived_audio(mx_ctx *ctx, const mx_audio *a, const char *what, F &&fill, mx_audio **out) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::unique_ptr<mx_audio> b(new mx_audio());
+  const size_t n = (size_t)a->n, pad = (size_t)MX_AUDIO_PAD;
+  hipError_t e = hipMalloc(&b->d_padded, (n + 2 * pad) * sizeof(float));
+  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "audio buffer: %s", hipGetErrorString(e));
+  e = hipMemsetAsync(b->d_padded, 0, pad * sizeof(float), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(b->d_padded + pad + n, 0, pad * sizeof(float), ctx->stream);
+  if (e == hipSuccess && n > 0) e = fill(b->d_padded + pad);
+  if (e != hipSuccess) {
+    hipStreamSynchronize(ctx->stream);
+    hipFree(b->d_padded);
+    return fail(MX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+  }
+  b->n = a->n;
+  b->owned = true;
+  *out = b.release();
+  return MX_OK;
+}
+
+// The blocking form: `d`, the call's device array (may be empty), stays allocated until the stream has drained; its elements
+// reach `host` (may be null: nothing) behind the fill; one synchronise; where that fails the new object goes the way
+// mx_audio_free releases one and *out is left alone.
+template <class T, class F>
+int derived_audio_host(mx_ctx *ctx, const mx_audio *a, const char *what, const DeviceArray<T> &d, T *host, F &&fill, mx_audio **out) {
+  mx_audio *b = nullptr;
+  if (const int rc = derived_audio(ctx, a, what, fill, &b)) return rc;
+  hipError_t e = d.download(host);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    mx_audio_free(ctx, b);
+    return fail(MX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+  }
+  *out = b;
+  return MX_OK;
+}
+
+// the samples a's (npts == 0) or a's through the gain of `d_pts`
+auto gain_fill(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_pts, int64_t npts) {
+  return [=](float *dst) {
+    if (npts == 0) return hipMemcpyAsync(dst, a->d_padded + MX_AUDIO_PAD, (size_t)a->n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+    return launch_audio_gain(a->d_padded + MX_AUDIO_PAD, dst, a->n, d_pts, npts, ctx->stream);
+  };
+}
+
+mx_limit_params limit_defaults(int sr) {
+  const int a = (sr + 100) / 200;
+  return mx_limit_params{0x1.c8520ap-1f /* (float)10^(-1/20) */, a < tp::kMaxLookahead ? a : tp::kMaxLookahead};
+}
+
+// what the two limiter entry points check of their arguments -> p, the parameters in force
+int limit_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params *params, mx_audio **out, mx_limit_params &p) {
+  if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+  if (const int rc = step_rate_check(sampleRate)) return rc;
+  p = params_or(params, limit_defaults(sampleRate));
+  if (!std::isnormal(p.ceiling_amp) || !(p.ceiling_amp > 0.f && p.ceiling_amp <= 1.f))
+    return fail(MX_ERR_INVALID, "ceiling amplitude %g: a normal number in (0, 1]", (double)p.ceiling_amp);
+  if (p.lookahead < 1 || p.lookahead > tp::kMaxLookahead)
+    return fail(MX_ERR_INVALID, "look-ahead of %d samples outside [1, %d]", p.lookahead, tp::kMaxLookahead);
+  return MX_OK;
+}
+
+// the samples a's through the limiter; d_pcm16 (may be null): their int16
+auto limit_fill(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params &p, int16_t *d_pcm16) {
+  return [=](float *dst) {
+    LimitArgs g{};
+    g.image = a->d_padded;
+    g.n = a->n;
+    g.L = tp::oversampling(sampleRate);
+    g.ceiling = p.ceiling_amp;
+    g.lookahead = p.lookahead;
+    g.dst = dst;
+    g.pcm16 = d_pcm16;
+    return launch_audio_limit(g, ctx->stream);
+  };
+}
+
+}  // namespace
+
+extern "C" {
+
+int mx_audio_gain_dev(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_points, int64_t npts, mx_audio **out) {
+  return mx_guard([&]() -> int {
+    if (!ctx || !a || !out || npts < 0 || (npts > 0 && !d_points)) return fail(MX_ERR_INVALID, "bad argument");
+    return derived_audio(ctx, a, "audio gain", gain_fill(ctx, a, d_points, npts), out);
+  });
+}
+
+int mx_audio_gain(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *points, int64_t npts, mx_audio **out) {
+  return mx_guard([&]() -> int {
+    if (!ctx || !a || !out || npts < 0 || (npts > 0 && !points)) return fail(MX_ERR_INVALID, "bad argument");
+    if (const char *why = gain_points_error(points, npts)) return fail(MX_ERR_INVALID, "%s", why);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DeviceArray<mx_gain_point> d;
+    hipError_t e = d.alloc(ctx->stream, (size_t)npts);
+    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "gain points: %s", hipGetErrorString(e));
+    if (npts) e = hipMemcpyAsync(d.p, points, (size_t)npts * sizeof(mx_gain_point), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return fail(MX_ERR_DEVICE, "gain points upload: %s", hipGetErrorString(e));
+    return derived_audio_host(ctx, a, "audio gain", d, (mx_gain_point *)nullptr, gain_fill(ctx, a, d.p, npts), out);
+  });
+}
+
+int mx_audio_download(mx_ctx *ctx, const mx_audio *a, int64_t first, int64_t count, float *host_out) {
+  return mx_guard([&]() -> int {
+    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (count < 0 || first < -(int64_t)MX_AUDIO_PAD || first > a->n + MX_AUDIO_PAD || count > a->n + MX_AUDIO_PAD - first)
+      return fail(MX_ERR_INVALID, "samples [%lld, %lld) outside the padded audio", (long long)first, (long long)(first + count));
+    if (count > 0 && !host_out) return fail(MX_ERR_INVALID, "null output");
+    if (count == 0) return MX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(host_out, a->d_padded + MX_AUDIO_PAD + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MX_OK;
+  });
+}
+
+int mx_limit_params_default(int sampleRate, mx_limit_params *p) {
+  return mx_guard([&]() -> int {
+    if (const int rc = step_rate_check(sampleRate)) return rc;
+    if (!p) return fail(MX_ERR_INVALID, "null output");
+    *p = limit_defaults(sampleRate);
+    return MX_OK;
+  });
+}
+
+int mx_audio_limit_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params *params, mx_audio **out,
+                       int16_t *d_pcm16) {
+  return mx_guard([&]() -> int {
+    mx_limit_params p;
+    if (const int rc = limit_parse(ctx, a, sampleRate, params, out, p)) return rc;
+    return derived_audio(ctx, a, "audio limit", limit_fill(ctx, a, sampleRate, p, d_pcm16), out);
+  });
+}
+
+int mx_audio_limit(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params *params, mx_audio **out, int16_t *pcm16_out) {
+  return mx_guard([&]() -> int {
+    mx_limit_params p;
+    if (const int rc = limit_parse(ctx, a, sampleRate, params, out, p)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DeviceArray<int16_t> d;
+    const hipError_t e = d.alloc(ctx->stream, pcm16_out ? (size_t)a->n : 0);
+    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device PCM buffer: %s", hipGetErrorString(e));
+    return derived_audio_host(ctx, a, "audio limit", d, pcm16_out, limit_fill(ctx, a, sampleRate, p, d.p), out);
+  });
+}
+
+}  // extern "C"

@@ -147,7 +147,7 @@ int mx_f0_track(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t
   return mx_guard([&]() -> int {
     F0Call q;
     if (const int rc = f0_parse(ctx, a, sampleRate, hop, first_frame, count, fmin, fmax, threshold, out, q)) return rc;
-    return staged_track(q, kStagePitch, "f0", out, [&](mx_f0 *d_track) { return f0_launch(q, d_track, nullptr); });
+    return staged_track(q.ctx, q.count, kStagePitch, "f0", out, [&](mx_f0 *d_track) { return f0_launch(q, d_track, nullptr); });
   });
 }
 

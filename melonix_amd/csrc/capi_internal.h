@@ -3,8 +3,10 @@
 // memory (DeviceArray for a call, GrowBuf for a context), the chunked host-staged loop (staged_batch), the PCM download
 // (pcm_to_host), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING phase clock (PhaseClock); and for
 // the per-frame tracks (f0, onset strength, sibilant features, chroma): the frame-span check (frame_span), the staged host form
-// (staged_records), a call's common head, its parse and its one-record host form (TrackCall, track_parse, staged_track), the
-// parameters in force and their defaults (params_or, params_default), the device tables built on the host (upload_table).
+// (staged_records), a call's common head, its parse and its one-record host form (TrackCall, track_parse, staged_track); for the
+// step records (loudness, true peak): their rate check, span check, head and parse (step_rate_check, unit_span, StepsCall,
+// steps_parse); a whole take's records reduced on the host (whole_take); the parameters in force and their defaults (params_or,
+// params_default), the device tables built on the host (upload_table).
 // Not installed; include/melonix_amd.h is the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +28,7 @@
 #include "../../include/melonix_amd.h"
 #include "host_logic.h"
 #include "kernels.h"
+#include "step_core.h"
 
 namespace mx {
 
@@ -255,8 +258,9 @@ struct mx_ctx {
   std::mutex zc_mu;
   mx::ZcBitmaps zc_scratch;
   // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
-  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_chroma, mx_contour_cents,
-  // mx_contour_split, mx_pitch_contour), kept between calls.  One host-staged call per context at a time.
+  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_sibilants_detect, mx_chroma,
+  // mx_contour_cents, mx_contour_split, mx_pitch_contour, mx_loudness_steps, mx_loudness_measure, mx_true_peak_steps,
+  // mx_true_peak_measure), kept between calls.  One host-staged call per context at a time.
   std::mutex stage_mu;
   mx::GrowBuf stage[mx::kStageSlots];
   // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)
@@ -444,12 +448,55 @@ inline int track_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, 
 }
 // the context's pinned run length (0: the kernel's default); no track's bytes depend on it
 inline int pinned_run(const mx_ctx *ctx) { return ctx->frames_per_block > 0 ? ctx->frames_per_block : 0; }
-// The host form of a track with one kind of record (staged_records): q.count records of Rec pass through staging buffer `slot`
+// The host form of a call with one kind of record (staged_records): `count` records of Rec pass through staging buffer `slot`
 // to `out`; `launch(d_out) -> status` is the device form.
 template <class Rec, class F>
-int staged_track(const TrackCall &q, StageSlot slot, const char *what, Rec *out, F &&launch) {
+int staged_track(mx_ctx *ctx, int64_t count, StageSlot slot, const char *what, Rec *out, F &&launch) {
   const StagedSlot slots[] = {{slot, sizeof(Rec), nullptr, out}};
-  return staged_records(q.ctx, q.count, slots, what, [&](void *const *d) { return launch(static_cast<Rec *>(d[0])); });
+  return staged_records(ctx, count, slots, what, [&](void *const *d) { return launch(static_cast<Rec *>(d[0])); });
+}
+
+// The head of the step-record calls (loudness records: groups of ten steps; true-peak records: steps — step_core.h): the arguments
+// their two forms share, checked; `records`: how many the call writes (steps_parse: `count`; the loudness unit counts its groups').
+struct StepsCall {
+  mx_ctx *ctx;
+  const mx_audio *a;
+  int sampleRate;
+  int64_t first, count, records;
+};
+inline bool step_rate_ok(int sr) { return sr >= step::kMinRate && sr <= step::kMaxRate; }
+inline int step_rate_check(int sr) {
+  return step_rate_ok(sr) ? MX_OK : fail(MX_ERR_INVALID, "sample rate %d outside [%d, %d]", sr, step::kMinRate, step::kMaxRate);
+}
+// what frame_span checks of frames, of a span of `unit`s ("groups", "steps"): [first, first + count) inside the file's `total`,
+// and `out` null only where count is 0
+inline int unit_span(const char *unit, int64_t first, int64_t count, int64_t total, const void *out) {
+  if (first < 0 || count < 0 || first > total || count > total - first)
+    return fail(MX_ERR_INVALID, "%s [%lld, %lld) outside the file's %lld", unit, (long long)first, (long long)(first + count),
+                (long long)total);
+  if (count > 0 && !out) return fail(MX_ERR_INVALID, "null output");
+  return MX_OK;
+}
+// the handles, the sample rate, then the span against `total(n, sampleRate)` units
+template <class Total>
+int steps_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, const char *unit, Total &&total, int64_t first, int64_t count,
+                const void *out, StepsCall &q) {
+  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = step_rate_check(sampleRate)) return rc;
+  if (const int rc = unit_span(unit, first, count, total(a->n, sampleRate), out)) return rc;
+  q = StepsCall{ctx, a, sampleRate, first, count, count};
+  return MX_OK;
+}
+
+// A measure of a whole take: room for `count` records on the host (at least one), `parse(rec, q) -> status` the unit's parse of
+// the whole file into its call head, `host(q, rec) -> status` its host form, then `reduce(rec) -> status` on the host.
+template <class Call, class Rec, class Parse, class Host, class Reduce>
+int whole_take(int64_t count, Parse &&parse, Host &&host, Reduce &&reduce) {
+  std::vector<Rec> rec((size_t)std::max<int64_t>(count, 1));
+  Call q;
+  if (const int rc = parse(rec.data(), q)) return rc;
+  if (const int rc = host(q, rec.data())) return rc;
+  return reduce(rec.data());
 }
 
 }  // namespace mx

@@ -62,7 +62,7 @@ int chroma_launch(const ChromaCall &q, mx_chroma_rec *d_out) {
 
 // the host form: the records pass through the context's staging buffer of the magnitude rows
 int chroma_host(const ChromaCall &q, mx_chroma_rec *out) {
-  return staged_track(q, kStageMags, "chroma records", out, [&](mx_chroma_rec *d_out) { return chroma_launch(q, d_out); });
+  return staged_track(q.ctx, q.count, kStageMags, "chroma records", out, [&](mx_chroma_rec *d_out) { return chroma_launch(q, d_out); });
 }
 
 int sum_args(const mx_ctx *ctx, const void *chroma, int64_t count, const void *jobs, int64_t njobs, const void *out) {

@@ -12,44 +12,27 @@ namespace {
 const mx_level_params kLevelDefaults{1.0, 1.0, 12.0};
 constexpr int kMaxWindow = 6000;
 
-bool rate_ok(int sr) { return sr >= loud::kMinRate && sr <= loud::kMaxRate; }
-int rate_check(int sr) {
-  return rate_ok(sr) ? MX_OK : fail(MX_ERR_INVALID, "sample rate %d outside [%d, %d]", sr, loud::kMinRate, loud::kMaxRate);
-}
-
-// What the two record entry points share: their arguments, checked, and the records they write
-struct StepsCall {
-  mx_ctx *ctx;
-  const mx_audio *a;
-  loud::Geometry geo;
-  int sampleRate;
-  int64_t first_group, ngroups, records;
-};
-
-int steps_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups, const void *out, StepsCall &q) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-  if (const int rc = rate_check(sampleRate)) return rc;
-  const loud::Geometry geo = loud::geometry(a->n, sampleRate);
-  if (first_group < 0 || ngroups < 0 || first_group > geo.groups || ngroups > geo.groups - first_group)
-    return fail(MX_ERR_INVALID, "groups [%lld, %lld) outside the file's %lld", (long long)first_group, (long long)(first_group + ngroups),
-                (long long)geo.groups);
-  if (ngroups > 0 && !out) return fail(MX_ERR_INVALID, "null output");
-  const int64_t lo = loud::kGroupSteps * first_group, hi = std::min(loud::kGroupSteps * (first_group + ngroups), geo.steps);
-  q = StepsCall{ctx, a, geo, sampleRate, first_group, ngroups, ngroups > 0 ? hi - lo : 0};
+// the groups [first_group, first_group + ngroups) of a call, checked, and the records they hold
+int groups_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups, const void *out, StepsCall &q) {
+  const auto groups = [](int64_t n, int sr) { return loud::geometry(n, sr).groups; };
+  if (const int rc = steps_parse(ctx, a, sampleRate, "groups", groups, first_group, ngroups, out, q)) return rc;
+  const int64_t lo = loud::kGroupSteps * first_group, hi = std::min(loud::kGroupSteps * (first_group + ngroups), step::step_count(a->n, sampleRate));
+  q.records = ngroups > 0 ? hi - lo : 0;
   return MX_OK;
 }
 
 int steps_launch(const StepsCall &q, mx_loud_step *d_steps) {
-  if (q.ngroups == 0) return MX_OK;
+  if (q.count == 0) return MX_OK;
   if (reinterpret_cast<uintptr_t>(d_steps) % 16) return fail(MX_ERR_INVALID, "device records must be 16-byte aligned");
   HIP_TRY(hipSetDevice(q.ctx->device));
+  const loud::Geometry geo = loud::geometry(q.a->n, q.sampleRate);
   LoudnessArgs g{};
   g.image = q.a->d_padded;
   g.n = q.a->n;
-  g.S = q.geo.S;
-  g.W = q.geo.W;
-  g.first_group = q.first_group;
-  g.ngroups = q.ngroups;
+  g.S = geo.S;
+  g.W = geo.W;
+  g.first_group = q.first;
+  g.ngroups = q.count;
   loudness_coeffs(q.sampleRate, g.coeffs);
   g.out = d_steps;
   HIP_TRY(launch_loudness_steps(g, q.ctx->stream));
@@ -58,14 +41,12 @@ int steps_launch(const StepsCall &q, mx_loud_step *d_steps) {
 
 // the host form: the records pass through the context's staging buffer of the pitch records
 int steps_host(const StepsCall &q, mx_loud_step *steps_out) {
-  const StagedSlot slots[] = {{kStagePitch, sizeof(mx_loud_step), nullptr, steps_out}};
-  return staged_records(q.ctx, q.records, slots, "loudness records",
-                        [&](void *const *d) { return steps_launch(q, static_cast<mx_loud_step *>(d[0])); });
+  return staged_track(q.ctx, q.records, kStagePitch, "loudness records", steps_out, [&](mx_loud_step *d_steps) { return steps_launch(q, d_steps); });
 }
 
 // what the host entry points check of a record list
 int list_check(const mx_loud_step *steps, int64_t nsteps, int sampleRate) {
-  if (const int rc = rate_check(sampleRate)) return rc;
+  if (const int rc = step_rate_check(sampleRate)) return rc;
   if (nsteps < 0 || (nsteps > 0 && !steps)) return fail(MX_ERR_INVALID, "bad record list");
   if (const char *why = loud_steps_error(steps, nsteps, loud::geometry(0, sampleRate).S)) return fail(MX_ERR_INVALID, "%s", why);
   return MX_OK;
@@ -76,12 +57,12 @@ int list_check(const mx_loud_step *steps, int64_t nsteps, int sampleRate) {
 extern "C" {
 
 int64_t mx_loudness_step_count(int64_t n, int sampleRate) {
-  return mx_guard([&]() -> int64_t { return rate_ok(sampleRate) ? loud::geometry(n, sampleRate).steps : 0; });
+  return mx_guard([&]() -> int64_t { return step_rate_ok(sampleRate) ? loud::geometry(n, sampleRate).steps : 0; });
 }
 
 int mx_loudness_coeffs(int sampleRate, double *out10) {
   return mx_guard([&]() -> int {
-    if (const int rc = rate_check(sampleRate)) return rc;
+    if (const int rc = step_rate_check(sampleRate)) return rc;
     if (!out10) return fail(MX_ERR_INVALID, "null output");
     loudness_coeffs(sampleRate, out10);
     return MX_OK;
@@ -92,7 +73,7 @@ int mx_loudness_steps_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_
                           mx_loud_step *d_steps) {
   return mx_guard([&]() -> int {
     StepsCall q;
-    if (const int rc = steps_parse(ctx, a, sampleRate, first_group, ngroups, d_steps, q)) return rc;
+    if (const int rc = groups_parse(ctx, a, sampleRate, first_group, ngroups, d_steps, q)) return rc;
     return steps_launch(q, d_steps);
   });
 }
@@ -100,7 +81,7 @@ int mx_loudness_steps_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_
 int mx_loudness_steps(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_group, int64_t ngroups, mx_loud_step *steps_out) {
   return mx_guard([&]() -> int {
     StepsCall q;
-    if (const int rc = steps_parse(ctx, a, sampleRate, first_group, ngroups, steps_out, q)) return rc;
+    if (const int rc = groups_parse(ctx, a, sampleRate, first_group, ngroups, steps_out, q)) return rc;
     return steps_host(q, steps_out);
   });
 }
@@ -128,14 +109,11 @@ int mx_loudness_measure(mx_ctx *ctx, const mx_audio *a, int sampleRate, mx_loudn
   return mx_guard([&]() -> int {
     if (!out) return fail(MX_ERR_INVALID, "null output");
     if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-    if (const int rc = rate_check(sampleRate)) return rc;
+    if (const int rc = step_rate_check(sampleRate)) return rc;
     const loud::Geometry geo = loud::geometry(a->n, sampleRate);
-    std::vector<mx_loud_step> steps((size_t)std::max<int64_t>(geo.steps, 1));
-    StepsCall q;
-    if (const int rc = steps_parse(ctx, a, sampleRate, 0, geo.groups, steps.data(), q)) return rc;
-    if (const int rc = steps_host(q, steps.data())) return rc;
-    loudness_integrated(steps.data(), geo.steps, geo.S, out);
-    return MX_OK;
+    return whole_take<StepsCall, mx_loud_step>(
+        geo.steps, [&](mx_loud_step *rec, StepsCall &q) { return groups_parse(ctx, a, sampleRate, 0, geo.groups, rec, q); }, steps_host,
+        [&](const mx_loud_step *rec) -> int { return loudness_integrated(rec, geo.steps, geo.S, out), MX_OK; });
   });
 }
 

@@ -57,7 +57,7 @@ int flux_launch(const FluxCall &q, float *d_flux) {
 
 // the host form: the values pass through the context's staging buffer of the pitch records
 int flux_host(const FluxCall &q, float *flux_out) {
-  return staged_track(q, kStagePitch, "flux", flux_out, [&](float *d_flux) { return flux_launch(q, d_flux); });
+  return staged_track(q.ctx, q.count, kStagePitch, "flux", flux_out, [&](float *d_flux) { return flux_launch(q, d_flux); });
 }
 
 // the parameters in force (p null: the defaults), checked

@@ -1,6 +1,6 @@
 // capi_sibilant.cpp — sibilant features (sibilant_kernels.hip), segments, protected formant curves and balance points
-// (sibilant_logic.cpp), the source gain (gain_kernels.hip): BUILD-DEFINED, the reference has none of it.  One unit of the
-// C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).
+// (sibilant_logic.cpp): BUILD-DEFINED, the reference has none of it.  One unit of the C-ABI implementation behind
+// include/melonix_amd.h (see capi_internal.h).  (The source gain that takes the balance points: capi_audio.cpp.)
 #include "capi_internal.h"
 #include "sibilant_logic.h"
 
@@ -45,7 +45,7 @@ int feature_launch(const FeatureCall &q, mx_sib_feat *d_feat) {
 
 // the host form: the records pass through the context's staging buffer of the pitch records
 int feature_host(const FeatureCall &q, mx_sib_feat *feat_out) {
-  return staged_track(q, kStagePitch, "sibilant features", feat_out, [&](mx_sib_feat *d_feat) { return feature_launch(q, d_feat); });
+  return staged_track(q.ctx, q.count, kStagePitch, "sibilant features", feat_out, [&](mx_sib_feat *d_feat) { return feature_launch(q, d_feat); });
 }
 
 // the parameters in force (p null: the defaults), checked
@@ -66,33 +66,6 @@ int span_args(const mx_sibilant *sibs, int64_t nsib, int32_t ramp, int64_t n) {
   if (n < 1 || n > INT32_MAX) return fail(MX_ERR_INVALID, "%lld samples outside [1, INT32_MAX]", (long long)n);
   if (ramp < 1 || ramp > (1 << 30)) return fail(MX_ERR_INVALID, "ramp of %d samples outside [1, 2^30]", ramp);
   if (const char *why = sibilant_list_error(sibs, nsib, n)) return fail(MX_ERR_INVALID, "%s", why);
-  return MX_OK;
-}
-
-// A new audio object of a's length: zeroed pads, the samples a's (npts == 0) or a's through the gain of `d_pts`.  Queued on the
-// context's stream; nothing is left allocated where it fails.
-int gained_audio(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_pts, int64_t npts, mx_audio **out) {
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::unique_ptr<mx_audio> b(new mx_audio());
-  const size_t n = (size_t)a->n, pad = (size_t)MX_AUDIO_PAD;
-  hipError_t e = hipMalloc(&b->d_padded, (n + 2 * pad) * sizeof(float));
-  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "audio buffer: %s", hipGetErrorString(e));
-  e = hipMemsetAsync(b->d_padded, 0, pad * sizeof(float), ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(b->d_padded + pad + n, 0, pad * sizeof(float), ctx->stream);
-  if (e == hipSuccess && n > 0) {
-    if (npts == 0)
-      e = hipMemcpyAsync(b->d_padded + pad, a->d_padded + pad, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-    else
-      e = launch_audio_gain(a->d_padded + pad, b->d_padded + pad, a->n, d_pts, npts, ctx->stream);
-  }
-  if (e != hipSuccess) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(b->d_padded);
-    return fail(MX_ERR_DEVICE, "audio gain: %s", hipGetErrorString(e));
-  }
-  b->n = a->n;
-  b->owned = true;
-  *out = b.release();
   return MX_OK;
 }
 
@@ -149,11 +122,9 @@ int mx_sibilants_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop,
     int64_t count = 0;  // (the whole file)
     if (const int rc = file_frames(ctx, a, hop, count)) return rc;
     if (count * (int64_t)hop > INT32_MAX) return fail(MX_ERR_INVALID, "frame centres beyond int32 samples");
-    std::vector<mx_sib_feat> feat((size_t)std::max<int64_t>(count, 1));
-    FeatureCall q;
-    if (const int rc = feature_parse(ctx, a, sampleRate, hop, 0, count, feature_params, feat.data(), q)) return rc;
-    if (const int rc = feature_host(q, feat.data())) return rc;
-    return hand_over(sibilant_segments(feat.data(), count, hop, 0, p), out, nout);
+    return whole_take<FeatureCall, mx_sib_feat>(
+        count, [&](mx_sib_feat *feat, FeatureCall &q) { return feature_parse(ctx, a, sampleRate, hop, 0, count, feature_params, feat, q); },
+        feature_host, [&](const mx_sib_feat *feat) { return hand_over(sibilant_segments(feat, count, hop, 0, p), out, nout); });
   });
 }
 
@@ -174,51 +145,6 @@ int mx_sibilant_gain_points(const mx_sibilant *sibs, int64_t nsib, double db, in
     if (const int rc = span_args(sibs, nsib, ramp_samples, n)) return rc;
     if (!(db >= -120.0 && db <= 40.0)) return fail(MX_ERR_INVALID, "balance of %g dB outside [-120, 40]", db);
     return hand_over(sibilant_gain_points(sibs, nsib, db, ramp_samples, n), out, nout);
-  });
-}
-
-int mx_audio_gain_dev(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_points, int64_t npts, mx_audio **out) {
-  return mx_guard([&]() -> int {
-    if (!ctx || !a || !out || npts < 0 || (npts > 0 && !d_points)) return fail(MX_ERR_INVALID, "bad argument");
-    return gained_audio(ctx, a, d_points, npts, out);
-  });
-}
-
-int mx_audio_gain(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *points, int64_t npts, mx_audio **out) {
-  return mx_guard([&]() -> int {
-    if (!ctx || !a || !out || npts < 0 || (npts > 0 && !points)) return fail(MX_ERR_INVALID, "bad argument");
-    if (const char *why = gain_points_error(points, npts)) return fail(MX_ERR_INVALID, "%s", why);
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeviceArray<mx_gain_point> d;  // (freed once the stream has drained)
-    hipError_t e = d.alloc(ctx->stream, (size_t)npts);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "gain points: %s", hipGetErrorString(e));
-    if (npts) e = hipMemcpyAsync(d.p, points, (size_t)npts * sizeof(mx_gain_point), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return fail(MX_ERR_DEVICE, "gain points upload: %s", hipGetErrorString(e));
-    mx_audio *b = nullptr;
-    if (const int rc = gained_audio(ctx, a, d.p, npts, &b)) return rc;
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      hipFree(b->d_padded);
-      delete b;
-      return fail(MX_ERR_DEVICE, "audio gain: %s", hipGetErrorString(e));
-    }
-    *out = b;
-    return MX_OK;
-  });
-}
-
-int mx_audio_download(mx_ctx *ctx, const mx_audio *a, int64_t first, int64_t count, float *host_out) {
-  return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-    if (count < 0 || first < -(int64_t)MX_AUDIO_PAD || first > a->n + MX_AUDIO_PAD || count > a->n + MX_AUDIO_PAD - first)
-      return fail(MX_ERR_INVALID, "samples [%lld, %lld) outside the padded audio", (long long)first, (long long)(first + count));
-    if (count > 0 && !host_out) return fail(MX_ERR_INVALID, "null output");
-    if (count == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(host_out, a->d_padded + MX_AUDIO_PAD + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return MX_OK;
   });
 }
 

@@ -5,19 +5,12 @@
 #include <stdint.h>
 
 #include "../../include/melonix_amd.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define MX_LOUD_HD __host__ __device__ __forceinline__
-#else
-#define MX_LOUD_HD inline
-#endif
+#include "step_core.h"
 
 namespace mx {
 namespace loud {
 
-constexpr int kGroupSteps = 10;                  // G
-constexpr int kMinRate = 8000, kMaxRate = 384000;
+constexpr int kGroupSteps = 10;  // G
 
 // S, W and the step / group counts of a take (sr in range: the caller's check)
 struct Geometry {
@@ -25,12 +18,12 @@ struct Geometry {
   int S, W;
   int64_t steps, groups;
 };
-MX_LOUD_HD Geometry geometry(int64_t n, int sr) {
+MX_STEP_HD Geometry geometry(int64_t n, int sr) {
   Geometry q;
   q.n = n;
-  q.S = (sr + 50) / 100;
+  q.S = step::step_samples(sr);
   q.W = 4 * ((32 * sr + 1499) / 1500);
-  q.steps = n > 0 ? (n + q.S - 1) / q.S : 0;
+  q.steps = step::step_count(n, sr);
   q.groups = (q.steps + kGroupSteps - 1) / kGroupSteps;
   return q;
 }
@@ -45,11 +38,11 @@ struct Lane {
   double s1, s2, t1, t2, energy;
   float peak;
 };
-MX_LOUD_HD Lane lane_zero() { return Lane{0.0, 0.0, 0.0, 0.0, 0.0, 0.f}; }
-MX_LOUD_HD void step_zero(Lane &l) { l.energy = 0.0, l.peak = 0.f; }
+MX_STEP_HD Lane lane_zero() { return Lane{0.0, 0.0, 0.0, 0.0, 0.0, 0.f}; }
+MX_STEP_HD void step_zero(Lane &l) { l.energy = 0.0, l.peak = 0.f; }
 
 // one sample through both stages -> z
-MX_LOUD_HD double filter(const Coeffs &c, Lane &l, float x) {
+MX_STEP_HD double filter(const Coeffs &c, Lane &l, float x) {
   const double v = (double)x;
   const double y = c.b0 * v + l.s1;
   l.s1 = (c.b1 * v - c.a1 * y) + l.s2;
@@ -60,12 +53,12 @@ MX_LOUD_HD double filter(const Coeffs &c, Lane &l, float x) {
   return z;
 }
 // a sample of a step: the energy in ascending order, the peak over what is not NaN (a NaN compares false)
-MX_LOUD_HD void accumulate(Lane &l, float x, double z) {
+MX_STEP_HD void accumulate(Lane &l, float x, double z) {
   l.energy += z * z;
   const float m = x < 0.f ? -x : x;
   if (m > l.peak) l.peak = m;
 }
-MX_LOUD_HD mx_loud_step record(const Lane &l, int32_t samples) {
+MX_STEP_HD mx_loud_step record(const Lane &l, int32_t samples) {
   mx_loud_step r;
   r.energy = l.energy;
   r.peak = l.peak;

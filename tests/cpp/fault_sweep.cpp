@@ -316,6 +316,65 @@ void host_entries() {
   });
   mx_free(gs);
   mx_free(gl);
+  // the host logic of the mastering chain over a record list: 321 steps of S = 480 — 300 whole steps and two more gating hops, so
+  // that the range has its 3 s windows —, the last one partial
+  const int S = 480;
+  std::vector<mx_loud_step> rec(321);
+  for (size_t b = 0; b < rec.size(); ++b) rec[b] = mx_loud_step{(double)S * 1e-3 * (double)(1 + b * 7 % 13), 0.1f * (float)(1 + b % 5), S};
+  rec.back().samples = 129;
+  const int64_t nrec = (int64_t)rec.size(), covered = (nrec - 1) * S + 129;
+  std::vector<double> curve((size_t)nrec);
+  sweep("mx_loudness_curve", [&]() -> Result {
+    const int rc = mx_loudness_curve(rec.data(), nrec, sr, 40, curve.data());
+    return {rc, rc < 0 ? 0 : fnv(curve.data(), curve.size() * 8)};
+  });
+  sweep("mx_loudness_integrated", [&]() -> Result {
+    mx_loudness m{};
+    m.blocks = -7;
+    const int rc = mx_loudness_integrated(rec.data(), nrec, sr, &m);
+    if (rc < 0) CHECK(m.blocks == -7, "mx_loudness_integrated: output written on failure");
+    const double v[5] = {m.integrated, m.momentary_max, m.shortterm_max, (double)m.peak, (double)(m.blocks * 1000 + m.passed_rel)};
+    return {rc, rc < 0 ? 0 : fnv(v, sizeof v)};
+  });
+  sweep("mx_loudness_range", [&]() -> Result {
+    mx_loudness_range_result r{};
+    r.values = -7;
+    const int rc = mx_loudness_range(rec.data(), nrec, sr, &r);
+    if (rc < 0) CHECK(r.values == -7, "mx_loudness_range: output written on failure");
+    const double v[4] = {r.lra, r.low_lufs, r.high_lufs, (double)(r.values * 1000 + r.gated)};
+    return {rc, rc < 0 ? 0 : fnv(v, sizeof v)};
+  });
+  // three notes: whole steps inside, shorter than a step (the step that holds its middle), up to the last covered sample
+  const std::vector<mx_note> notes = {{1000, 30000, 0, 0, 60., 0.f, 0.f}, {40000, 40100, 0, 0, 62., 0.f, 0.f},
+                                      {90000, (int32_t)covered - 1, 0, 0, 64., 0.f, 0.f}};
+  const int64_t nnotes = (int64_t)notes.size();
+  sweep("mx_note_loudness", [&]() -> Result {
+    double lufs[3] = {-7., -7., -7.};
+    const int rc = mx_note_loudness(rec.data(), nrec, sr, notes.data(), nnotes, lufs);
+    if (rc < 0) CHECK(lufs[0] == -7. && lufs[2] == -7., "mx_note_loudness: output written on failure");
+    return {rc, rc < 0 ? 0 : fnv(lufs, sizeof lufs)};
+  });
+  sweep("mx_level_gain_points", [&]() -> Result {
+    const double lufs[3] = {-30., std::nan(""), -18.};  // (a note without a loudness keeps amp 1)
+    mx_gain_point pts[6] = {};
+    double ref = -7.;
+    const int rc = mx_level_gain_points(notes.data(), nnotes, lufs, nullptr, pts, &ref);
+    if (rc < 0) CHECK(ref == -7. && pts[0].amp == 0.f, "mx_level_gain_points: output written on failure");
+    return {rc, rc < 0 ? 0 : fnv(pts, sizeof pts, fnv(&ref, 8))};
+  });
+  sweep("mx_sibilant_gain_points", [&]() -> Result {
+    const mx_sibilant sibs[2] = {{5000, 9000, 0, 0, 0.8f, 0.1f}, {20000, 20400, 0, 0, 0.7f, 0.1f}};
+    mx_gain_point *pts = nullptr;
+    int64_t npts = -5;
+    const int rc = mx_sibilant_gain_points(sibs, 2, -6.0, 64, covered, &pts, &npts);
+    if (rc < 0) {
+      CHECK(pts == nullptr && npts == -5, "mx_sibilant_gain_points: outputs set on failure");
+      return {rc, 0};
+    }
+    const uint64_t h = fnv(pts, (size_t)npts * sizeof(mx_gain_point));
+    mx_free(pts);
+    return {rc, h};
+  });
 }
 
 void device_entries() {
@@ -553,6 +612,84 @@ void device_entries() {
     const int rc = mx_f0_track(ctx, a, sr, hop, 0, F, 55.f, 1760.f, 0.15f, f0.data());
     return {rc, rc < 0 ? 0 : fnv(f0.data(), f0.size() * sizeof(mx_f0))};
   });
+  // the mastering chain at the smallest sizes that take every branch: 2049 samples at 48 kHz (one limiter tile plus one sample, 5
+  // steps, one group) and one sample
+  for (const int64_t len : {(int64_t)2049, (int64_t)1}) {
+    mx_audio *s = nullptr;
+    CHECK(mx_audio_upload(ctx, w.data() + 1000, len, &s) == MX_OK, "upload of %lld: %s", (long long)len, mx_last_error());
+    const int64_t steps = mx_loudness_step_count(len, sr);
+    char label[64];
+    auto named = [&](const char *what) {
+      snprintf(label, sizeof label, "%s (n = %lld)", what, (long long)len);
+      return label;
+    };
+    sweep(named("mx_loudness_steps"), [&]() -> Result {
+      std::vector<mx_loud_step> rec((size_t)steps);
+      const int rc = mx_loudness_steps(ctx, s, sr, 0, (steps + 9) / 10, rec.data());
+      uint64_t h = 0;
+      for (const mx_loud_step &r : rec) h = fnv(&r.samples, 4, fnv(&r.peak, 4, fnv(&r.energy, 8, h)));
+      return {rc, rc < 0 ? 0 : h};
+    });
+    sweep(named("mx_loudness_measure"), [&]() -> Result {
+      mx_loudness m{};
+      m.blocks = -7;
+      const int rc = mx_loudness_measure(ctx, s, sr, &m);
+      if (rc < 0) CHECK(m.blocks == -7, "mx_loudness_measure: output written on failure");
+      const double v[5] = {m.integrated, m.momentary_max, m.shortterm_max, (double)m.peak, (double)m.blocks};
+      return {rc, rc < 0 ? 0 : fnv(v, sizeof v)};
+    });
+    sweep(named("mx_true_peak_steps"), [&]() -> Result {
+      std::vector<mx_tp_step> rec((size_t)steps);
+      const int rc = mx_true_peak_steps(ctx, s, sr, 0, steps, rec.data());
+      return {rc, rc < 0 ? 0 : fnv(rec.data(), rec.size() * sizeof(mx_tp_step))};
+    });
+    sweep(named("mx_true_peak_measure"), [&]() -> Result {
+      float v[2] = {-7.f, -7.f};
+      const int rc = mx_true_peak_measure(ctx, s, sr, &v[0], &v[1]);
+      if (rc < 0) CHECK(v[0] == -7.f && v[1] == -7.f, "mx_true_peak_measure: outputs written on failure");
+      return {rc, rc < 0 ? 0 : fnv(v, sizeof v)};
+    });
+    // a derived audio object: its handle is set only on success; its samples and both pads are the checksum
+    auto derived = [&](int rc, mx_audio *b, const std::vector<int16_t> *pcm) -> Result {
+      if (rc < 0) {
+        CHECK(b == nullptr, "derived audio: handle set on failure");
+        return {rc, 0};
+      }
+      std::vector<float> all((size_t)(len + 2 * MX_AUDIO_PAD));
+      rc = mx_audio_length(b) == len ? mx_audio_download(ctx, b, -(int64_t)MX_AUDIO_PAD, (int64_t)all.size(), all.data()) : -100;
+      mx_audio_free(ctx, b);
+      return {rc, rc < 0 ? 0 : fnv(all.data(), all.size() * 4, pcm ? fnv(pcm->data(), pcm->size() * 2) : 0)};
+    };
+    sweep(named("mx_audio_gain (0 points)"), [&]() -> Result {
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_gain(ctx, s, nullptr, 0, &b);
+      return derived(rc, b, nullptr);
+    });
+    sweep(named("mx_audio_gain (2 points)"), [&]() -> Result {
+      const mx_gain_point pts[2] = {{0, 0.5f}, {(int32_t)len, 2.f}};
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_gain(ctx, s, pts, 2, &b);
+      return derived(rc, b, nullptr);
+    });
+    const mx_limit_params lp{0.25f, 64};  // (the sweep peaks at 0.5: the limiter works)
+    sweep(named("mx_audio_limit"), [&]() -> Result {
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_limit(ctx, s, sr, &lp, &b, nullptr);
+      return derived(rc, b, nullptr);
+    });
+    sweep(named("mx_audio_limit (int16)"), [&]() -> Result {
+      std::vector<int16_t> pcm((size_t)len, (int16_t)0x5A5A);
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_limit(ctx, s, sr, &lp, &b, pcm.data());
+      return derived(rc, b, &pcm);
+    });
+    sweep(named("mx_audio_download"), [&]() -> Result {
+      std::vector<float> all((size_t)(len + 2 * MX_AUDIO_PAD));
+      const int rc = mx_audio_download(ctx, s, -(int64_t)MX_AUDIO_PAD, (int64_t)all.size(), all.data());
+      return {rc, rc < 0 ? 0 : fnv(all.data(), all.size() * 4)};
+    });
+    mx_audio_free(ctx, s);
+  }
   sweep("mx_ctx_release_scratch", [&]() -> Result { return {mx_ctx_release_scratch(ctx), 0}; });
   mx_free(steps);
   mx_free(gs);

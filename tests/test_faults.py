@@ -68,7 +68,7 @@ def test_allocation_fault_sweep_host_entry_points_under_asan(mxlib, tmp_path):
     tail = r.stdout[-3000:] + r.stderr[-4000:]
     assert r.returncode == 0, tail
     m = re.search(r"fault_sweep host: (\d+) faults injected, 0 failed checks", r.stdout)
-    assert m and int(m.group(1)) >= 100, tail
+    assert m and int(m.group(1)) >= 120, tail
     for word in ("AddressSanitizer", "LeakSanitizer", "FAIL "):
         assert word not in r.stderr, tail
     # every host entry family was swept, and those that allocate were actually faulted
@@ -87,7 +87,7 @@ def test_malloc_fault_sweep_host_entry_points(mxlib, tmp_path):
     tail = r.stdout[-3000:] + r.stderr[-3000:]
     assert r.returncode == 0, tail
     m = re.search(r"fault_sweep host-malloc: (\d+) faults injected, 0 failed checks", r.stdout)
-    assert m and int(m.group(1)) >= 9 and "FAIL " not in r.stderr, tail
+    assert m and int(m.group(1)) >= 10 and "FAIL " not in r.stderr, tail
     for name, n in (("mx_grains", 2), ("mx_schedule_build", 1), ("mx_schedule_build_table", 1), ("mx_pv_plan", 4)):
         mm = re.search(r"^\s+" + name + r"\s+(\d+) allocation", r.stdout, flags=re.M)
         assert mm and int(mm.group(1)) == n, (name, tail)
@@ -104,7 +104,7 @@ def test_allocation_fault_sweep_device_entry_points(mxlib, tmp_path):
     tail = r.stdout[-5000:] + r.stderr[-4000:]
     assert r.returncode == 0, tail
     m = re.search(r"fault_sweep device: (\d+) faults injected, 0 failed checks", r.stdout)
-    assert m and int(m.group(1)) >= 150, tail
+    assert m and int(m.group(1)) >= 170, tail
     for name in ("mx_ctx_create / destroy", "mx_stft_hop", "mx_stft_ranges_keep / rows", "mx_grain_table_dev", "mx_resynth_to_wav",
                  "mx_pv_pitch_shift", "mx_pv_render", "mx_pv_shard_* (rank 1 of 2)", "mx_minmax_pyramid"):
         assert re.search(r"^\s+" + re.escape(name) + r"\s+\d+ allocation", r.stdout, flags=re.M), (name, tail)

@@ -257,6 +257,35 @@ def test_guard_bands(gpu_ctx, taps):
             a.free()
 
 
+@pytest.mark.parametrize("n", (1, 3, 2047, 2048, 2049))
+def test_every_derived_audio_has_its_length_and_zero_pads(mxlib, gpu_ctx, taps, n):
+    """The gain's copy (no points), the gain with points, the limiter without and with the int16: each a new object of n samples
+    whose two pads — every one of their MX_AUDIO_PAD samples, read back through audio_download — are +0.0f, at lengths below a
+    quad, one short of the limiter's tile, on it and one past it; freeing the object leaves the context and the source usable."""
+    sr, A, pad = 48000, 64, mxlib.MX_AUDIO_PAD
+    w = T.clicks(n, seed=n)
+    limited = T.limit(w, sr, taps, C1, A)[0]
+    a = gpu_ctx.upload(w)
+    try:
+        forms = (("copy", lambda: gpu_ctx.audio_gain(a, []), w),
+                 ("gain", lambda: gpu_ctx.audio_gain(a, [(0, 0.5), (n, 2.0)]), None),
+                 ("limit", lambda: gpu_ctx.limit(a, sr, lookahead=A), limited),
+                 ("limit + int16", lambda: gpu_ctx.limit(a, sr, lookahead=A, pcm16=True)[0], limited))
+        for name, make, want in forms:
+            b = make()
+            try:
+                assert b.n == n and mxlib._capi.lib().mx_audio_length(b.handle) == n, name
+                left, body, right = gpu_ctx.audio_download(b, -pad, pad), gpu_ctx.audio_download(b), gpu_ctx.audio_download(b, n, pad)
+            finally:
+                b.free()
+            assert len(left) == pad == len(right) and len(body) == n, name
+            assert not left.view(np.uint32).any() and not right.view(np.uint32).any(), name  # +0.0f throughout
+            assert want is None or body.tobytes() == want.tobytes(), name
+            assert gpu_ctx.audio_download(a).tobytes() == w.tobytes(), name
+    finally:
+        a.free()
+
+
 def test_bad_arguments_are_refused_before_any_launch(mxlib, gpu_ctx, taps):
     sr, n = 48000, 4801
     w = T.clicks(n)

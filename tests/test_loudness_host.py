@@ -21,7 +21,7 @@ def as_lib(mx, st):
 
 @pytest.fixture(scope="module")
 def emu(mxlib):
-    lib = C.CDLL(emu_build.shared_object("loudness_emu", ["loudness_emu.cpp"], ["loudness_core.h"]))
+    lib = C.CDLL(emu_build.shared_object("loudness_emu", ["loudness_emu.cpp"], ["loudness_core.h", "step_core.h"]))
     lib.emu_loudness_steps.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]
 
     def steps(w, sr, k, first_group=0, ngroups=None):

@@ -24,7 +24,7 @@ def taps(mxlib):
 
 @pytest.fixture(scope="module")
 def emu(mxlib):
-    lib = C.CDLL(emu_build.shared_object("truepeak_emu", ["truepeak_emu.cpp"], ["truepeak_core.h", "pcm16.h"]))
+    lib = C.CDLL(emu_build.shared_object("truepeak_emu", ["truepeak_emu.cpp"], ["truepeak_core.h", "step_core.h", "pcm16.h"]))
     lib.emu_true_peak_steps.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_void_p]
     lib.emu_limit.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
 
