@@ -875,8 +875,8 @@ int mx_tempo_from_flux(mx_ctx *ctx, const float *flux, int64_t count, int sample
                        const mx_tempo_params *p, mx_tempo *out, mx_tempo_window **windows, int64_t *nwindows);
 /* The whole file: mx_onset_flux_dev into the context's work memory, the smoothing and the comb launches there; what comes back
  * is the smoothed curve once (4 bytes per frame, for the mean behind clarity) and the job records.  fp / p NULL: the defaults.
- * The work memory (two curves, jobs, records) is the context's, kept between calls, released by mx_ctx_release_scratch;
- * MX_ERR_NOMEM when it cannot be had, nothing of it left allocated.  Blocks. */
+ * The work memory (two curves; jobs and records in the context's job buffers) is the context's, kept between calls, released by
+ * mx_ctx_release_scratch; MX_ERR_NOMEM when it cannot be had, nothing of the set that failed left allocated.  Blocks. */
 int mx_tempo_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const mx_onset_flux_params *fp,
                     const mx_tempo_params *p, mx_tempo *out, mx_tempo_window **windows, int64_t *nwindows);
 

@@ -13,8 +13,8 @@ namespace {
 int cents_check(const mx_ctx *ctx, const void *track, int64_t count, int sampleRate, float threshold, float rms_floor,
                 const void *out) {
   if (!ctx) return fail(MX_ERR_INVALID, "null context");
-  if (count < 0 || count > INT32_MAX) return fail(MX_ERR_INVALID, "%lld frames outside [0, INT32_MAX]", (long long)count);
-  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  if (const int rc = frames_i32(count)) return rc;
+  if (const int rc = rate_check(sampleRate)) return rc;
   if (!std::isfinite(threshold) || !std::isfinite(rms_floor)) return fail(MX_ERR_INVALID, "threshold / rms_floor is not finite");
   if (count > 0 && (!track || !out)) return fail(MX_ERR_INVALID, "null argument");
   return MX_OK;
@@ -23,7 +23,7 @@ int cents_check(const mx_ctx *ctx, const void *track, int64_t count, int sampleR
 // what the two split forms check alike: everything but the spans themselves
 int split_check(const mx_ctx *ctx, const void *cents, int64_t count, const void *spans, int64_t nspans, const mx_contour_params *p) {
   if (!ctx) return fail(MX_ERR_INVALID, "null context");
-  if (count < 0 || count > INT32_MAX) return fail(MX_ERR_INVALID, "%lld frames outside [0, INT32_MAX]", (long long)count);
+  if (const int rc = frames_i32(count)) return rc;
   if (nspans < 0 || nspans > count) return fail(MX_ERR_INVALID, "%lld spans over %lld frames", (long long)nspans, (long long)count);
   if (!p) return fail(MX_ERR_INVALID, "null parameters");
   if (!contour::params_ok(*p))
@@ -33,34 +33,29 @@ int split_check(const mx_ctx *ctx, const void *cents, int64_t count, const void 
   return MX_OK;
 }
 
-// queues stage B on the context's stream; its work memory is the context's (contour_mu).  d_rec null: the records go to work
+// queues stage B on the context's stream; its work memory is the context's contour set.  d_rec null: the records go to work
 // memory.  Nothing wanted: nothing queued.
 int split_launch(mx_ctx *ctx, const int32_t *d_cents, int64_t count, const mx_contour_span *d_spans, int64_t nspans,
                  const mx_contour_params &p, mx_contour_rec *d_rec, mx_contour_stat *d_stat) {
   if (count == 0 || (!d_rec && (!d_stat || nspans == 0))) return MX_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> lk(ctx->contour_mu);
+  Hold work(ctx, ctx->contour);
+  const char *what = "contour work memory";
   void *d_part = nullptr;
-  hipError_t e = hipSuccess;
-  if (d_stat && nspans > 0) e = ctx->contour[kContourPart].get(contour_part_bytes(count, nspans, p), &d_part);
-  if (e == hipSuccess && !d_rec) e = ctx->contour[kContourRec].get((size_t)count * sizeof(mx_contour_rec), &d_rec);
-  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "contour work memory: %s", hipGetErrorString(e));
+  if (const int rc = d_stat && nspans > 0 ? work.get(kContourPart, contour_part_bytes(count, nspans, p), &d_part, what) : MX_OK) return rc;
+  if (const int rc = d_rec ? MX_OK : work.get(kContourRec, (size_t)count, &d_rec, what)) return rc;
   HIP_TRY(launch_contour_split(d_cents, count, d_spans, nspans, p, d_rec, d_stat, d_part, ctx->stream));
   return MX_OK;
 }
 
-// Stage B of a staged call (inside staged_records' run): the host spans up, the statistics back, in device memory of the call
+// Stage B of a staged call (inside staged_records' run): the host spans up, the statistics back (job_pass; stat null: the
+// records alone).  No spans: the smoothing alone.
 int split_staged(mx_ctx *ctx, const int32_t *d_cents, int64_t count, const mx_contour_span *spans, int64_t nspans,
                  const mx_contour_params &p, mx_contour_rec *d_rec, mx_contour_stat *stat) {
-  DeviceArray<mx_contour_span> d_spans;  // (freed once the stream has drained)
-  DeviceArray<mx_contour_stat> d_stat;
-  hipError_t e = d_spans.alloc(ctx->stream, (size_t)nspans);
-  if (e == hipSuccess) e = d_stat.alloc(ctx->stream, stat ? (size_t)nspans : 0);
-  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "contour spans: %s", hipGetErrorString(e));
-  if (nspans) HIP_TRY(hipMemcpyAsync(d_spans.p, spans, (size_t)nspans * sizeof(mx_contour_span), hipMemcpyHostToDevice, ctx->stream));
-  if (const int rc = split_launch(ctx, d_cents, count, d_spans.p, nspans, p, d_rec, d_stat.p)) return rc;
-  HIP_TRY(d_stat.download(stat));
-  return MX_OK;
+  if (nspans == 0) return split_launch(ctx, d_cents, count, nullptr, 0, p, d_rec, nullptr);
+  return job_pass(ctx, "contour spans", spans, nspans, 1, stat, [&](const mx_contour_span *d_spans, mx_contour_stat *d_stat) {
+    return split_launch(ctx, d_cents, count, d_spans, nspans, p, d_rec, d_stat);
+  });
 }
 
 }  // namespace
@@ -70,8 +65,8 @@ extern "C" {
 int mx_contour_params_default(int sampleRate, int hop, mx_contour_params *p) {
   return mx_guard([&]() -> int {
     if (!p) return fail(MX_ERR_INVALID, "null argument");
-    if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
-    if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+    if (const int rc = rate_check(sampleRate)) return rc;
+    if (const int rc = hop_check(hop)) return rc;
     *p = contour_params_default(sampleRate, hop);
     return MX_OK;
   });
@@ -132,8 +127,8 @@ int mx_contour_spans(const mx_note *notes, int64_t nnotes, int64_t first_frame, 
 int mx_contour_vibrato(const mx_contour_stat *stat, int32_t frames, int sampleRate, int hop, mx_vibrato *out) {
   return mx_guard([&]() -> int {
     if (!stat || !out) return fail(MX_ERR_INVALID, "null argument");
-    if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
-    if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+    if (const int rc = rate_check(sampleRate)) return rc;
+    if (const int rc = hop_check(hop)) return rc;
     if (frames < 1 || stat->lag < 0 || frames <= stat->lag)
       return fail(MX_ERR_INVALID, "a span of %d frames with lag %d", frames, stat->lag);
     *out = contour_vibrato(*stat, frames, sampleRate, hop);
@@ -153,9 +148,9 @@ int mx_contour_bend(const mx_contour_rec *rec, int64_t count, const mx_note *not
     const mx_bend_params q = params_or(p, kBendDefaults);
     if (const char *why = bend_params_error(q)) return fail(MX_ERR_INVALID, "bend parameters: %s", why);
     if (const char *why = contour_spans_error(spans, nnotes, count, nullptr)) return fail(MX_ERR_INVALID, "spans: %s", why);
-    for (int64_t i = 0; i < nnotes; ++i)
-      if (!std::isfinite(notes[i].note) || (shift && !std::isfinite(shift[i])))
-        return fail(MX_ERR_INVALID, "note %lld: the note or its shift is not finite", (long long)i);
+    if (const int rc = notes_check(notes, nnotes, /*finite=*/true, /*ordered=*/false)) return rc;
+    if (shift && !std::all_of(shift, shift + nnotes, [](double v) { return std::isfinite(v); }))
+      return fail(MX_ERR_INVALID, "a note's shift is not finite");
     contour_bend(rec, count, notes, spans, nnotes, shift, q, bend_out);
     return MX_OK;
   });
@@ -166,7 +161,7 @@ int mx_pitch_contour(mx_ctx *ctx, const mx_f0 *track, int64_t count, int sampleR
                      mx_contour_rec *rec_out, mx_contour_stat *stat_out) {
   return mx_guard([&]() -> int {
     if (const int rc = cents_check(ctx, track, count, sampleRate, threshold, rms_floor, track)) return rc;
-    if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+    if (const int rc = hop_check(hop)) return rc;
     if (nnotes < 0 || nnotes > count || (nnotes > 0 && !notes)) return fail(MX_ERR_INVALID, "%lld notes over %lld frames", (long long)nnotes, (long long)count);
     const mx_contour_params p = params_or(params, contour_params_default(sampleRate, hop));
     std::vector<mx_contour_span> spans((size_t)nnotes);

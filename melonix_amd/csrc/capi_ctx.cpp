@@ -105,7 +105,7 @@ int check_common(mx_ctx *ctx, const mx_audio *a, int N, int64_t count, int &kmin
 
 int file_frames(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t &frames) {
   if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-  if (hop < 1 || hop > 16384) return fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop);
+  if (const int rc = hop_check(hop)) return rc;
   frames = (a->n + hop - 1) / hop;
   return MX_OK;
 }
@@ -165,12 +165,6 @@ int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_
 // frames per host-staging chunk: keep the device staging buffer <= ~1 GiB
 int64_t chunk_frames(int N) { return std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)(N / 2) * 4)); }
 
-// Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.
-void stage_trim(mx_ctx *ctx) {
-  for (auto &st : ctx->stage)
-    if (st.cap > ((size_t)256 << 20)) st.drop();
-}
-
 }  // namespace mx
 
 extern "C" {
@@ -221,11 +215,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
     hipFree(ctx->onset_tw);
     hipFree(ctx->chroma_hann);
-    for (auto &st : ctx->stage) st.drop();
-    for (auto &st : ctx->chain) st.drop();
-    for (auto &st : ctx->f0dec) st.drop();
-    for (auto &st : ctx->tempo) st.drop();
-    for (auto &st : ctx->contour) st.drop();
+    for_each_work(ctx, [](auto &set) { set.drop(); });  // (no locks: the context is the caller's alone)
     pv_release(ctx);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -260,32 +250,16 @@ int mx_ctx_release_scratch(mx_ctx *ctx) {
   return mx_guard([&]() -> int {
     if (!ctx) return fail(MX_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
+    for_each_work(ctx, [&](auto &set) { Hold(ctx, set).mem.drop(); });  // (each under its lock)
     {
-      std::lock_guard<std::mutex> lk(ctx->stage_mu);
-      for (auto &st : ctx->stage) st.drop();
+      Hold chain(ctx, ctx->chain);
+      ctx->zc_scratch = ZcBitmaps{};
     }
     {
       std::lock_guard<std::mutex> lk(ctx->pv_mu);
       pv_release(ctx);  // (a staged multi-GPU job lives in that arena: it ends here)
       ctx->pv_budget_auto = 0;  // (the automatic budget is taken again from what is free at the next first use)
       ctx->pv_rec_full = false;
-    }
-    {
-      std::lock_guard<std::mutex> lk(ctx->zc_mu);
-      ctx->zc_scratch = ZcBitmaps{};
-      for (auto &st : ctx->chain) st.drop();
-    }
-    {
-      std::lock_guard<std::mutex> lk(ctx->f0_mu);
-      for (auto &st : ctx->f0dec) st.drop();
-    }
-    {
-      std::lock_guard<std::mutex> lk(ctx->tempo_mu);
-      for (auto &st : ctx->tempo) st.drop();
-    }
-    {
-      std::lock_guard<std::mutex> lk(ctx->contour_mu);
-      for (auto &st : ctx->contour) st.drop();
     }
     return MX_OK;
   });

@@ -11,7 +11,7 @@ constexpr int kF0W = 2048;
 
 // the search range of (sr, fmin, fmax), or a failed status
 int f0_range(int sampleRate, float fmin, float fmax, int &tmin, int &tmax) {
-  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  if (const int rc = rate_check(sampleRate)) return rc;
   if (!(fmin > 0.f) || !(fmax > 0.f) || !std::isfinite(fmin) || !std::isfinite(fmax))
     return fail(MX_ERR_INVALID, "f0 band [%g, %g] Hz: both ends must be positive and finite", (double)fmin, (double)fmax);
   const double lo = std::floor((double)sampleRate / (double)fmax), hi = std::ceil((double)sampleRate / (double)fmin);
@@ -88,12 +88,12 @@ int decode_parse(mx_ctx *ctx, const void *track, const void *cands, int64_t coun
 
 int64_t q16(float x) { return (int64_t)std::rint((double)x * 65536.0); }
 
-// queues the decode of `count` frames on the context's stream; its work buffers are the context's (f0_mu)
+// queues the decode of `count` frames on the context's stream; its work buffers are the context's f0dec set
 int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, int64_t count, const mx_f0_decode_params &p,
                   mx_f0 *d_out, uint8_t *d_state) {
   if (count == 0) return MX_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> lk(ctx->f0_mu);
+  Hold work(ctx, ctx->f0dec);
   F0DecodeArgs g{};
   g.track = d_track;
   g.cands = d_cands;
@@ -104,10 +104,13 @@ int decode_launch(mx_ctx *ctx, const mx_f0 *d_track, const mx_f0_cand *d_cands, 
   g.max_jump_cents = p.max_jump_cents;
   g.chunk = ctx->f0_chunk > 0 ? ctx->f0_chunk : f0_decode_default_chunk(count);
   const F0DecodeScratch need = f0_decode_scratch(count, g.chunk);
-  hipError_t e = ctx->f0dec[kF0DecBp].get(need.bp, &g.bp);
-  if (e == hipSuccess) e = ctx->f0dec[kF0DecProd].get(need.prod, &g.prod);
-  if (e == hipSuccess) e = ctx->f0dec[kF0DecMap].get(need.map, &g.map);
-  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "f0 decode work buffers: %s", hipGetErrorString(e));
+  void *bp = nullptr, *prod = nullptr, *map = nullptr;  // (f0_decode_scratch counts bytes)
+  if (const int rc = work.get(kF0DecBp, need.bp, &bp, "f0 decode work buffers")) return rc;
+  if (const int rc = work.get(kF0DecProd, need.prod, &prod, "f0 decode work buffers")) return rc;
+  if (const int rc = work.get(kF0DecMap, need.map, &map, "f0 decode work buffers")) return rc;
+  g.bp = static_cast<uint16_t *>(bp);
+  g.prod = static_cast<int64_t *>(prod);
+  g.map = static_cast<uint16_t *>(map);
   g.out = d_out;
   g.state = d_state;
   HIP_TRY(launch_f0_decode(g, ctx->stream));
@@ -211,7 +214,7 @@ int mx_f0_track_decoded(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop,
 int mx_f0_decode_set_chunk(mx_ctx *ctx, int64_t frames) {
   return mx_guard([&]() -> int {
     if (!ctx || frames < 0) return fail(MX_ERR_INVALID, "bad argument");
-    std::lock_guard<std::mutex> lk(ctx->f0_mu);
+    Hold work(ctx, ctx->f0dec);
     ctx->f0_chunk = frames;
     return MX_OK;
   });
@@ -241,11 +244,7 @@ int mx_correction_markers(const mx_note *notes, int64_t count, double strength, 
     if (count < 0 || (count > 0 && (!notes || !out))) return fail(MX_ERR_INVALID, "null argument");
     if (!(strength >= 0.0 && strength <= 1.0)) return fail(MX_ERR_INVALID, "strength %g outside [0, 1]", strength);
     if (scale_mask < 0 || scale_mask > 0xFFF) return fail(MX_ERR_INVALID, "scale mask 0x%x beyond the twelve classes", scale_mask);
-    for (int64_t i = 0; i < count; ++i) {
-      if (!std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
-      if (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample))
-        return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
-    }
+    if (const int rc = notes_check(notes, count, /*finite=*/true, /*ordered=*/true)) return rc;
     correction_markers(notes, count, strength, scale_mask, out);
     return MX_OK;
   });

@@ -1,12 +1,13 @@
-// capi_internal.h — what the units of the C-ABI implementation (capi_*.cpp) share: the context and audio handle
-// types, the error slot behind mx_last_error, the per-N table cache, and the sequences written once: the owners of device
-// memory (DeviceArray for a call, GrowBuf for a context), the chunked host-staged loop (staged_batch), the PCM download
-// (pcm_to_host), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING phase clock (PhaseClock); and for
-// the per-frame tracks (f0, onset strength, sibilant features, chroma): the frame-span check (frame_span), the staged host form
-// (staged_records), a call's common head, its parse and its one-record host form (TrackCall, track_parse, staged_track); for the
-// step records (loudness, true peak): their rate check, span check, head and parse (step_rate_check, unit_span, StepsCall,
-// steps_parse); a whole take's records reduced on the host (whole_take); the parameters in force and their defaults (params_or,
-// params_default), the device tables built on the host (upload_table).
+// capi_internal.h — what the units of the C-ABI implementation (capi_*.cpp) share: the context and audio handle types, the error
+// slot behind mx_last_error, the per-N table cache, and the sequences written once: the owners of device memory (DeviceArray for a
+// call; WorkMem, a locked set of GrowBufs, for a context), the chunked host-staged loop (staged_batch), the host form of a job-list
+// call (job_pass), the PCM download (pcm_to_host), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING
+// phase clock (PhaseClock); for the per-frame tracks (f0, onset strength, sibilant features, chroma): the frame-span check
+// (frame_span), the staged host form (staged_records), a call's common head, its parse and its one-record host form (TrackCall,
+// track_parse, staged_track), the small argument checks (hop_check, rate_check, frames_i32, notes_check); for the step records
+// (loudness, true peak): their rate check, span check, head and parse (step_rate_check, unit_span, StepsCall, steps_parse); a whole
+// take's records reduced on the host (whole_take); the parameters in force and their defaults (params_or, params_default), the
+// device tables built on the host (upload_table).
 // Not installed; include/melonix_amd.h is the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/melonix_amd.h"
@@ -124,7 +126,7 @@ struct DeviceArray {
 };
 
 // Device memory a context keeps between calls: grows to the largest request, never shrinks until dropped — a screen-sized
-// batch otherwise spends more time in hipMalloc/hipFree than in the kernel.  The mutex of its array guards it.
+// batch otherwise spends more time in hipMalloc/hipFree than in the kernel.  The lock of its set (WorkMem) guards it.
 struct GrowBuf {
   void *p = nullptr;
   size_t cap = 0;
@@ -133,29 +135,26 @@ struct GrowBuf {
     p = nullptr;
     cap = 0;
   }
-  template <class T>
-  hipError_t get(size_t bytes, T **out) {  // room for `bytes`, contents undefined
-    if (cap < bytes) {
-      drop();
-      const hipError_t e = hipMalloc(&p, bytes);
-      if (e != hipSuccess) return e;
-      cap = bytes;
-    }
-    *out = static_cast<T *>(p);
-    return hipSuccess;
-  }
 };
-// staging of the host-pointer entry points (mx_ctx::stage, under stage_mu) and work buffers of the grain chain (mx_ctx::chain,
-// under zc_mu): the two predicate bitmaps, the rank tables, the lifting tables
+// The one form of a context's kept device memory: K buffers behind one lock.  A call holds the set (Hold) while anything it queued
+// may use the buffers and asks for each with get(): room for n elements of T (bytes where T is void), contents undefined.  Where a
+// buffer cannot be had the stream is drained and the WHOLE set is given back — nothing of it stays allocated behind an
+// MX_ERR_NOMEM — and `what` names the set in the message.
+// LOCK ORDER, the one every path keeps: the staging set (staged_batch, staged_records), then a family's own set (tempo), then `jobs`
+// (job_pass); a set that only a device form takes (contour inside job_pass's launch, f0dec inside staged_records' run) comes last.  No path takes two sets
+// in two orders, and job_pass is never entered from inside its own launch.
+template <int K>
+struct WorkMem {
+  std::mutex mu;
+  GrowBuf buf[K];
+  void drop() { for (GrowBuf &b : buf) b.drop(); }  // (the caller holds the set or owns the context outright)
+};
 enum StageSlot { kStageMags, kStagePitch, kStageRanges, kStageTexels, kStageSlots };
 enum ChainSlot { kChainBitmap7, kChainBitmap3, kChainRanks, kChainTables, kChainSlots };
-// work buffers of the f0 decode (mx_ctx::f0dec, under f0_mu): bp rows, chunk products, chunk maps
 enum F0DecSlot { kF0DecBp, kF0DecProd, kF0DecMap, kF0DecSlots };
-// work buffers of the tempo estimate (mx_ctx::tempo, under tempo_mu): the flux curve, the smoothed curve, jobs, records
-enum TempoSlot { kTempoFlux, kTempoCurve, kTempoJobs, kTempoRecords, kTempoSlots };
-// work buffers of the pitch-contour split (mx_ctx::contour, under contour_mu): the pieces' partial sums, and the records where
-// the caller wants the statistics alone
-enum ContourSlot { kContourPart, kContourRec, kContourSlots };
+enum TempoSlot { kTempoFlux, kTempoCurve, kTempoSlots };
+enum ContourSlot { kContourPart, kContourRec, kContourSlots };  // (the records: where the caller wants the statistics alone)
+enum JobSlot { kJobsIn, kJobsOut, kJobSlots };
 
 // Arrays handed to the caller, who frees them with mx_free.  add(): a fresh malloc block of n elements (at least one, so an
 // empty result is not a null pointer), copied from src or, src null, left for a download.  give(): every block is there and
@@ -253,29 +252,24 @@ struct mx_ctx {
   float2 *onset_tw = nullptr;  // the 1024-point transform's twiddles (onset_table), built on first use under mu
   float *chroma_hann = nullptr;  // the chroma frame's window (chroma_window), built on first use under mu
   std::mutex mu;
-  // host landing zone of the zero-crossing bitmaps (mx_grains_dev), kept between calls: a copy into
-  // pages that are already mapped runs at PCIe rate, a fresh 2 x n/8-byte buffer pays ~3 ms of faults
-  std::mutex zc_mu;
+  // Device memory kept between calls, one WorkMem each (for_each_work names them all; mx_ctx_release_scratch gives them back).
+  // stage: staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap, mx_f0_track,
+  // mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_sibilants_detect, mx_chroma, mx_contour_cents,
+  // mx_contour_split, mx_pitch_contour, mx_loudness_steps, mx_loudness_measure, mx_true_peak_steps, mx_true_peak_measure): one
+  // host-staged call per context at a time
+  mx::WorkMem<mx::kStageSlots> stage;
+  // chain: work buffers of the grain chain (mx_grains_dev).  Its lock also guards zc_scratch, the host landing zone of the zero-
+  // crossing bitmaps: a copy into pages that are already mapped runs at PCIe rate, a fresh 2 x n/8-byte buffer pays ~3 ms of faults
+  mx::WorkMem<mx::kChainSlots> chain;
   mx::ZcBitmaps zc_scratch;
-  // device staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap,
-  // mx_f0_track, mx_f0_candidates, mx_f0_decode, mx_f0_track_decoded, mx_onset_flux, mx_sib_features, mx_sibilants_detect, mx_chroma,
-  // mx_contour_cents, mx_contour_split, mx_pitch_contour, mx_loudness_steps, mx_loudness_measure, mx_true_peak_steps,
-  // mx_true_peak_measure), kept between calls.  One host-staged call per context at a time.
-  std::mutex stage_mu;
-  mx::GrowBuf stage[mx::kStageSlots];
-  // device work buffers of the grain chain (mx_grains_dev), kept between calls like the staging buffers (guarded by zc_mu)
-  mx::GrowBuf chain[mx::kChainSlots];
-  // device work buffers of the f0 decode (mx_f0_decode*), kept between calls like the staging buffers; f0_chunk = 0: the default
-  // chunk length
-  std::mutex f0_mu;
-  mx::GrowBuf f0dec[mx::kF0DecSlots];
+  // f0dec: work buffers of the f0 decode (mx_f0_decode*).  Its lock also guards f0_chunk (0: the default chunk length)
+  mx::WorkMem<mx::kF0DecSlots> f0dec;
   int64_t f0_chunk = 0;
-  // device work buffers of the tempo estimate (capi_tempo.cpp), kept between calls like the staging buffers
-  std::mutex tempo_mu;
-  mx::GrowBuf tempo[mx::kTempoSlots];
-  // device work buffers of the pitch-contour split (capi_contour.cpp), kept between calls like the staging buffers
-  std::mutex contour_mu;
-  mx::GrowBuf contour[mx::kContourSlots];
+  // tempo, contour: work buffers of the tempo estimate (capi_tempo.cpp) and of the pitch-contour split (capi_contour.cpp); jobs: the
+  // job list and the results of a job-list call (job_pass: combs, chroma sums, contour spans)
+  mx::WorkMem<mx::kTempoSlots> tempo;
+  mx::WorkMem<mx::kContourSlots> contour;
+  mx::WorkMem<mx::kJobSlots> jobs;
   // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;
@@ -317,8 +311,45 @@ int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_
                 int run_length = 0);
 // frames per host-staging chunk: keep the device staging buffer <= ~1 GiB
 int64_t chunk_frames(int N);
-// Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.  Caller holds ctx->stage_mu.
-void stage_trim(mx_ctx *ctx);
+template <int K>
+struct Hold {
+  mx_ctx *ctx;
+  WorkMem<K> &mem;
+  std::lock_guard<std::mutex> lk;
+  Hold(mx_ctx *c, WorkMem<K> &m) : ctx(c), mem(m), lk(m.mu) {}
+  template <class T>
+  int get(int slot, size_t n, T **out, const char *what) {
+    GrowBuf &b = mem.buf[slot];
+    const size_t bytes = n * sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+    if (b.cap < bytes) {
+      b.drop();
+      const hipError_t e = hipMalloc(&b.p, bytes);
+      if (e != hipSuccess) {
+        hipStreamSynchronize(ctx->stream);
+        mem.drop();
+        return fail(MX_ERR_NOMEM, "%s: %s", what, hipGetErrorString(e));
+      }
+      b.cap = bytes;
+    }
+    *out = static_cast<T *>(b.p);
+    return MX_OK;
+  }
+};
+// Bulk jobs stage up to 1 GiB per buffer: give those back, keep what a screen of columns needs.
+inline void stage_trim(Hold<kStageSlots> &stage) {
+  for (GrowBuf &b : stage.mem.buf)
+    if (b.cap > ((size_t)256 << 20)) b.drop();
+}
+// every WorkMem of a context: a new family's set is one more line here
+template <class F>
+void for_each_work(mx_ctx *ctx, F &&f) {
+  f(ctx->stage);
+  f(ctx->chain);
+  f(ctx->f0dec);
+  f(ctx->tempo);
+  f(ctx->contour);
+  f(ctx->jobs);
+}
 // gives the phase vocoder's arena, stream and events back (capi_pv_arena.cpp); the caller holds ctx->pv_mu or owns the context
 // outright (mx_ctx_destroy)
 void pv_release(mx_ctx *ctx);
@@ -346,13 +377,14 @@ int staged_batch(mx_ctx *ctx, const StagedBatch &b, F &&run) {
   mx_pitch *d_pitch = nullptr;
   int32_t *d_ranges = nullptr;
   uint8_t *d_rgb = nullptr;
-  std::lock_guard<std::mutex> slk(ctx->stage_mu);
+  Hold stage(ctx, ctx->stage);
+  const char *what = "device staging buffers";
+  int rc = MX_OK;
+  if (b.mags_out && !b.d_rows) rc = stage.get(kStageMags, (size_t)chunk * row, &d_mags, what);
+  if (rc == MX_OK && b.pitch_out) rc = stage.get(kStagePitch, (size_t)chunk, &d_pitch, what);
+  if (rc == MX_OK && b.ranges) rc = stage.get(kStageRanges, (size_t)chunk * 2, &d_ranges, what);
+  if (rc == MX_OK && b.rgb_out) rc = stage.get(kStageTexels, (size_t)chunk * row * 3, &d_rgb, what);
   hipError_t e = hipSuccess;
-  if (b.mags_out && !b.d_rows) e = ctx->stage[kStageMags].get((size_t)chunk * row * sizeof(float), &d_mags);
-  if (e == hipSuccess && b.pitch_out) e = ctx->stage[kStagePitch].get((size_t)chunk * sizeof(mx_pitch), &d_pitch);
-  if (e == hipSuccess && b.ranges) e = ctx->stage[kStageRanges].get((size_t)chunk * 2 * sizeof(int32_t), &d_ranges);
-  if (e == hipSuccess && b.rgb_out) e = ctx->stage[kStageTexels].get((size_t)chunk * row * 3, &d_rgb);
-  int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
   for (int64_t done = 0; done < b.count && rc == MX_OK; done += chunk) {
     const int64_t c = std::min(chunk, b.count - done);
     if (b.d_rows) d_mags = b.d_rows + (size_t)done * row;
@@ -371,7 +403,7 @@ int staged_batch(mx_ctx *ctx, const StagedBatch &b, F &&run) {
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) rc = fail(MX_ERR_DEVICE, "result download: %s", hipGetErrorString(e));
   }
-  stage_trim(ctx);
+  stage_trim(stage);
   return rc;
 }
 
@@ -402,19 +434,19 @@ struct StagedSlot {
   void *out;
 };
 // The host-pointer form of a per-frame track entry point: `count` frames of every slot pass through the context's staging
-// buffers, held (stage_mu) for the whole call.  `run(d) -> status` queues the device form on the context's stream, d[i] the
+// buffers, held for the whole call.  `run(d) -> status` queues the device form on the context's stream, d[i] the
 // device records of slot i; the results come back only if it succeeded.  `what` names the call in a device error.  Blocks, on
 // the failure path too: the uploads read the caller's memory.
 template <size_t K, class F>
 int staged_records(mx_ctx *ctx, int64_t count, const StagedSlot (&slots)[K], const char *what, F &&run) {
   if (count == 0) return MX_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> lk(ctx->stage_mu);
+  Hold stage(ctx, ctx->stage);
   void *d[K] = {};
+  int rc = MX_OK;
+  for (size_t i = 0; i < K && rc == MX_OK; ++i)
+    if (slots[i].frame_bytes) rc = stage.get(slots[i].slot, (size_t)count * slots[i].frame_bytes, &d[i], "device staging buffers");
   hipError_t e = hipSuccess;
-  for (size_t i = 0; i < K && e == hipSuccess; ++i)
-    if (slots[i].frame_bytes) e = ctx->stage[slots[i].slot].get((size_t)count * slots[i].frame_bytes, &d[i]);
-  int rc = e == hipSuccess ? MX_OK : fail(MX_ERR_NOMEM, "device staging buffers: %s", hipGetErrorString(e));
   for (size_t i = 0; i < K && rc == MX_OK && e == hipSuccess; ++i)
     if (d[i] && slots[i].in)
       e = hipMemcpyAsync(d[i], slots[i].in, (size_t)count * slots[i].frame_bytes, hipMemcpyHostToDevice, ctx->stream);
@@ -426,7 +458,30 @@ int staged_records(mx_ctx *ctx, int64_t count, const StagedSlot (&slots)[K], con
   const hipError_t es = hipStreamSynchronize(ctx->stream);
   if (rc == MX_OK && e == hipSuccess) e = es;
   if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "%s download: %s", what, hipGetErrorString(e));
-  stage_trim(ctx);
+  stage_trim(stage);
+  return rc;
+}
+
+// The host form of a job-list call: records that are already on the device, a host list of `njobs` jobs, `res_per_job` results of Res
+// per job back at `out`.  `launch(d_jobs, d_res) -> status` queues the unit's device form on the context's stream; the jobs and the
+// results pass through the context's `jobs` set, held for the call.  out null: no result buffer, d_res is null.  No jobs: MX_OK and
+// nothing queued.  `what` names the call in an error.  Blocks, on every path: the upload reads the caller's memory.
+template <class Job, class Res, class F>
+int job_pass(mx_ctx *ctx, const char *what, const Job *jobs, int64_t njobs, size_t res_per_job, Res *out, F &&launch) {
+  if (njobs == 0) return MX_OK;
+  Hold work(ctx, ctx->jobs);
+  Job *d_jobs = nullptr;
+  Res *d_res = nullptr;
+  hipError_t e = hipSetDevice(ctx->device);  // (before the buffers are had: they belong on the context's device)
+  int rc = e == hipSuccess ? work.get(kJobsIn, (size_t)njobs, &d_jobs, what) : MX_OK;
+  if (rc == MX_OK && e == hipSuccess && out) rc = work.get(kJobsOut, (size_t)njobs * res_per_job, &d_res, what);
+  if (rc == MX_OK && e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs, (size_t)njobs * sizeof(Job), hipMemcpyHostToDevice, ctx->stream);
+  if (rc == MX_OK && e == hipSuccess) rc = launch(static_cast<const Job *>(d_jobs), d_res);
+  if (rc == MX_OK && e == hipSuccess && out)
+    e = hipMemcpyAsync(out, d_res, (size_t)njobs * res_per_job * sizeof(Res), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (a caller's upload of the records may be in flight too)
+  if (e == hipSuccess) e = es;
+  if (rc == MX_OK && e != hipSuccess) rc = fail(MX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
   return rc;
 }
 
@@ -438,11 +493,26 @@ struct TrackCall {
   int sampleRate, hop;
   int64_t first_frame, count;
 };
+// The small argument checks, each refusal worded once: the hop range (file_frames' too), a positive sample rate, a frame count the
+// kernels index with int32, and of a note list — `finite`: every note number; `ordered`: none reversed, empty or overlapping.
+inline int hop_check(int hop) { return hop >= 1 && hop <= 16384 ? MX_OK : fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop); }
+inline int rate_check(int sampleRate) { return sampleRate > 0 ? MX_OK : fail(MX_ERR_INVALID, "sample rate %d", sampleRate); }
+inline int frames_i32(int64_t count) {
+  return count >= 0 && count <= INT32_MAX ? MX_OK : fail(MX_ERR_INVALID, "%lld frames outside [0, INT32_MAX]", (long long)count);
+}
+inline int notes_check(const mx_note *notes, int64_t count, bool finite, bool ordered) {
+  for (int64_t i = 0; i < count; ++i) {
+    if (finite && !std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
+    if (ordered && (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample)))
+      return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
+  }
+  return MX_OK;
+}
 // the frame span (frame_span: `out`), then the sample rate
 inline int track_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, int64_t first_frame, int64_t count, const void *out,
                        TrackCall &q) {
   if (const int rc = frame_span(ctx, a, hop, first_frame, count, out)) return rc;
-  if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+  if (const int rc = rate_check(sampleRate)) return rc;
   q = TrackCall{ctx, a, sampleRate, hop, first_frame, count};
   return MX_OK;
 }

@@ -80,6 +80,21 @@ int jobs_inside(const mx_chroma_job *jobs, int64_t njobs, int64_t count) {
   return MX_OK;
 }
 
+// The sums of host `jobs` at `out` (job_pass) over `count` records that `records(d_rec) -> status` puts on the device, in memory of
+// the call as ever: kept in the staging buffer, an hour's 108 MB made a context's later calls 6 % slower (refactor_work_memory.log).
+template <class F>
+int sums_pass(mx_ctx *ctx, const char *what, int64_t count, const mx_chroma_job *jobs, int64_t njobs, double *out, F &&records) {
+  if (njobs == 0) return MX_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  DeviceArray<mx_chroma_rec> d_rec;  // (freed once the stream has drained, on every path)
+  if (const hipError_t e = d_rec.alloc(ctx->stream, (size_t)count)) return fail(MX_ERR_NOMEM, "%s: %s", what, hipGetErrorString(e));
+  if (const int rc = records(d_rec.p)) return rc;
+  return job_pass(ctx, what, jobs, njobs, chroma::kCols, out, [&](const mx_chroma_job *d_jobs, double *d_out) -> int {
+    HIP_TRY(launch_chroma_sum(d_rec.p, count, d_jobs, njobs, d_out, ctx->stream));
+    return MX_OK;
+  });
+}
+
 }  // namespace
 
 namespace mx {
@@ -139,21 +154,10 @@ int mx_chroma_sum(mx_ctx *ctx, const mx_chroma_rec *chroma, int64_t count, const
   return mx_guard([&]() -> int {
     if (const int rc = sum_args(ctx, chroma, count, jobs, njobs, out)) return rc;
     if (const int rc = jobs_inside(jobs, njobs, count)) return rc;
-    if (njobs == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeviceArray<mx_chroma_rec> d_rec;  // (freed once the stream has drained)
-    DeviceArray<mx_chroma_job> d_jobs;
-    DeviceArray<double> d_out;
-    hipError_t e = d_rec.alloc(ctx->stream, (size_t)count);
-    if (e == hipSuccess) e = d_jobs.alloc(ctx->stream, (size_t)njobs);
-    if (e == hipSuccess) e = d_out.alloc(ctx->stream, (size_t)njobs * chroma::kCols);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "chroma sums: %s", hipGetErrorString(e));
-    if (count) e = hipMemcpyAsync(d_rec.p, chroma, (size_t)count * sizeof(mx_chroma_rec), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs.p, jobs, (size_t)njobs * sizeof(mx_chroma_job), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = launch_chroma_sum(d_rec.p, count, d_jobs.p, njobs, d_out.p, ctx->stream);
-    if (e == hipSuccess) e = d_out.download(out);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "chroma sums: %s", hipGetErrorString(e));
+    return sums_pass(ctx, "chroma sums", count, jobs, njobs, out, [&](mx_chroma_rec *d_rec) -> int {
+      if (count) HIP_TRY(hipMemcpyAsync(d_rec, chroma, (size_t)count * sizeof(mx_chroma_rec), hipMemcpyHostToDevice, ctx->stream));
+      return MX_OK;
+    });
   });
 }
 
@@ -168,8 +172,7 @@ int mx_key_from_chroma(const double *sum40, mx_key *out) {
 int mx_key_from_notes(const mx_note *notes, int64_t count, mx_key *out) {
   return mx_guard([&]() -> int {
     if (!out || count < 0 || (count > 0 && !notes)) return fail(MX_ERR_INVALID, "null argument or negative count");
-    for (int64_t i = 0; i < count; ++i)
-      if (!std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
+    if (const int rc = notes_check(notes, count, /*finite=*/true, /*ordered=*/false)) return rc;
     *out = key_from_notes(notes, count);
     return MX_OK;
   });
@@ -183,7 +186,7 @@ int mx_key_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const
       return fail(MX_ERR_INVALID, "windows of %lld frames every %lld", (long long)window_frames, (long long)window_hop);
     int64_t count = 0;  // (the whole file)
     if (const int rc = file_frames(ctx, a, hop, count)) return rc;
-    if (count > INT32_MAX) return fail(MX_ERR_INVALID, "%lld frames beyond int32", (long long)count);
+    if (const int rc = frames_i32(count)) return rc;
     ChromaCall q;
     if (const int rc = chroma_parse(ctx, a, sampleRate, hop, 0, count, params, key, q)) return rc;
     std::vector<mx_chroma_job> jobs = key_windows(count, windows ? window_frames : 0, window_hop);
@@ -191,23 +194,9 @@ int mx_key_detect(mx_ctx *ctx, const mx_audio *a, int sampleRate, int hop, const
     jobs.push_back(mx_chroma_job{0, count});  // the take, behind its windows
     const size_t njobs = jobs.size();
     std::vector<double> sums(njobs * chroma::kCols);
-    HIP_TRY(hipSetDevice(ctx->device));
-    {
-      DeviceArray<mx_chroma_rec> d_rec;
-      DeviceArray<mx_chroma_job> d_jobs;
-      DeviceArray<double> d_out;
-      hipError_t e = d_rec.alloc(ctx->stream, (size_t)count);
-      if (e == hipSuccess) e = d_jobs.alloc(ctx->stream, njobs);
-      if (e == hipSuccess) e = d_out.alloc(ctx->stream, sums.size());
-      if (e != hipSuccess) return fail(MX_ERR_NOMEM, "key detection: %s", hipGetErrorString(e));
-      e = hipMemcpyAsync(d_jobs.p, jobs.data(), njobs * sizeof(mx_chroma_job), hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) return fail(MX_ERR_DEVICE, "job upload: %s", hipGetErrorString(e));
-      if (const int rc = chroma_launch(q, d_rec.p)) return rc;
-      e = launch_chroma_sum(d_rec.p, count, d_jobs.p, (int64_t)njobs, d_out.p, ctx->stream);
-      if (e == hipSuccess) e = d_out.download(sums.data());
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) return fail(MX_ERR_DEVICE, "key detection: %s", hipGetErrorString(e));
-    }
+    if (const int rc = sums_pass(ctx, "key detection", count, jobs.data(), (int64_t)njobs, sums.data(),
+                                 [&](mx_chroma_rec *d_rec) { return chroma_launch(q, d_rec); }))
+      return rc;
     if (windows) {
       std::vector<mx_key_window> w(njobs - 1);
       for (size_t j = 0; j + 1 < njobs; ++j)
@@ -226,11 +215,7 @@ int mx_correction_markers_tuned(const mx_note *notes, int64_t count, double stre
     if (!(strength >= 0.0 && strength <= 1.0)) return fail(MX_ERR_INVALID, "strength %g outside [0, 1]", strength);
     if (scale_mask < 0 || scale_mask > 0xFFF) return fail(MX_ERR_INVALID, "scale mask 0x%x beyond the twelve classes", scale_mask);
     if (!(tuning_cents >= -50.0 && tuning_cents <= 50.0)) return fail(MX_ERR_INVALID, "tuning of %g cents outside [-50, 50]", tuning_cents);
-    for (int64_t i = 0; i < count; ++i) {
-      if (!std::isfinite(notes[i].note)) return fail(MX_ERR_INVALID, "note %lld is not finite", (long long)i);
-      if (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample))
-        return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
-    }
+    if (const int rc = notes_check(notes, count, /*finite=*/true, /*ordered=*/true)) return rc;
     correction_markers_tuned(notes, count, strength, scale_mask, tuning_cents, out);
     return MX_OK;
   });

@@ -143,9 +143,7 @@ int mx_level_gain_points(const mx_note *notes, int64_t nnotes, const double *luf
     if (!(p.raise >= 0.0 && p.raise <= 1.0) || !(p.lower >= 0.0 && p.lower <= 1.0))
       return fail(MX_ERR_INVALID, "raise %g / lower %g: both in [0, 1]", p.raise, p.lower);
     if (!(p.max_db >= 0.0 && p.max_db <= 40.0)) return fail(MX_ERR_INVALID, "max_db %g outside [0, 40]", p.max_db);
-    for (int64_t i = 0; i < nnotes; ++i)
-      if (notes[i].end_sample <= notes[i].start_sample || (i > 0 && notes[i].start_sample <= notes[i - 1].end_sample))
-        return fail(MX_ERR_INVALID, "notes out of order or overlapping at %lld", (long long)i);
+    if (const int rc = notes_check(notes, nnotes, /*finite=*/false, /*ordered=*/true)) return rc;
     const double ref = level_gain_points(notes, nnotes, lufs, p, out);
     if (reference_out) *reference_out = ref;
     return MX_OK;

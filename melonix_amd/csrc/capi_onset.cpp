@@ -159,7 +159,7 @@ int mx_timing_markers(const int32_t *anchors, int64_t nanchors, int64_t n, int s
   return mx_guard([&]() -> int {
     if (!out || !nout || (nanchors > 0 && !anchors) || (nbase > 0 && !base)) return fail(MX_ERR_INVALID, "null argument");
     if (nanchors < 0 || nbase < 0) return fail(MX_ERR_INVALID, "negative count");
-    if (sampleRate <= 0) return fail(MX_ERR_INVALID, "sample rate %d", sampleRate);
+    if (const int rc = rate_check(sampleRate)) return rc;
     if (n < 1 || n > INT32_MAX) return fail(MX_ERR_INVALID, "%lld samples outside [1, INT32_MAX]", (long long)n);
     const mx_timing_params p = params_or(params, kTimingDefaults);
     if (!(p.bpm >= 30.0 && p.bpm <= 250.0)) return fail(MX_ERR_INVALID, "bpm %g outside [30, 250]", p.bpm);

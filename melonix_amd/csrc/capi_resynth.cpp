@@ -66,7 +66,7 @@ int mx_grain_table_dev(mx_ctx *ctx, const mx_audio *a, int32_t **starts, int32_t
     *count = 0;
     HIP_TRY(hipSetDevice(ctx->device));
     PhaseClock phases;
-    std::lock_guard<std::mutex> zlk(ctx->zc_mu);
+    Hold chain(ctx, ctx->chain);
     const int64_t n = a->n;
     const size_t words = (size_t)((n + 63) >> 6);
     uint32_t ngr = 0;
@@ -75,10 +75,10 @@ int mx_grain_table_dev(mx_ctx *ctx, const mx_audio *a, int32_t **starts, int32_t
     if (words && n >= 1501) {  // (the reference's size_t arithmetic wraps below 1501 samples, app.cpp:161: no grains)
       uint64_t *d7 = nullptr, *d3 = nullptr;
       void *rk = nullptr, *ch = nullptr;
-      hipError_t e = ctx->chain[kChainBitmap7].get(words * 8, &d7);
-      if (e == hipSuccess) e = ctx->chain[kChainBitmap3].get(words * 8, &d3);
-      if (e == hipSuccess) e = ctx->chain[kChainRanks].get(grain_rank_scratch_bytes(n), &rk);
-      if (e != hipSuccess) return fail(MX_ERR_NOMEM, "grain chain buffers: %s", hipGetErrorString(e));
+      const char *what = "grain chain buffers";
+      if (const int rc = chain.get(kChainBitmap7, words, &d7, what)) return rc;
+      if (const int rc = chain.get(kChainBitmap3, words, &d3, what)) return rc;
+      if (const int rc = chain.get(kChainRanks, grain_rank_scratch_bytes(n), &rk, what)) return rc;
       HIP_TRY(launch_zc_bitmaps(a->d_padded, n, d7, d3, ctx->stream));
       HIP_TRY(launch_grain_rank(a->d_padded, n, d7, d3, rk, ctx->stream));
       uint32_t hdr[4] = {0, 0, 0, 0};
@@ -89,8 +89,7 @@ int mx_grain_table_dev(mx_ctx *ctx, const mx_audio *a, int32_t **starts, int32_t
       uint32_t out_cap;
       size_t bytes;
       grain_chain_sizes(n, hdr[2], &levels, &out_cap, &bytes);
-      e = ctx->chain[kChainTables].get(bytes, &ch);
-      if (e != hipSuccess) return fail(MX_ERR_NOMEM, "grain chain tables (%zu bytes): %s", bytes, hipGetErrorString(e));
+      if (const int rc = chain.get(kChainTables, bytes, &ch, what)) return rc;
       HIP_TRY(launch_grain_chain(a->d_padded, n, d7, d3, rk, hdr[2], ch, &d_s, &d_l, &d_f, ctx->stream));
       HIP_TRY(hipMemcpyAsync(hdr, rk, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -13,7 +13,8 @@
 //   fault_sweep host-malloc / device-malloc   (built with -DSWEEP_MALLOC, no sanitizer) the same sweeps with the faults in the
 //                         library's own malloc() calls — the arrays it hands out for mx_free — instead of operator new
 //   fault_sweep device    ... and those that do (context, audio, STFT in all modes, kept rows, grain table, resynthesis,
-//                         export, phase vocoder incl. the three rank stages, pyramid): only allocations made FROM the
+//                         export, phase vocoder incl. the three rank stages, pyramid, f0 and its decode, tempo, chroma and key,
+//                         pitch contour, the mastering chain): only allocations made FROM the
 //                         library's own code are faulted there (the HIP runtime beneath it is not the subject)
 #include <dlfcn.h>
 #include <unistd.h>
@@ -375,6 +376,171 @@ void host_entries() {
     mx_free(pts);
     return {rc, h};
   });
+  // the host logic of the analysis units that hands arrays out: two notes in a synthetic track, three peaks in a synthetic curve
+  std::vector<mx_f0> track(200, mx_f0{0, 0.f, 1.f, 0.f});
+  for (int f = 10; f < 180; ++f)
+    if (f < 80 || f >= 100) track[(size_t)f] = mx_f0{f < 80 ? 218 : 145, f < 80 ? 218.18f : 145.45f, 0.05f, 0.1f};
+  mx_note_params np;
+  mx_note_params_default(&np);
+  sweep("mx_detect_notes", [&]() -> Result {
+    mx_note *out = nullptr;
+    int64_t nn = -5;
+    const int rc = mx_detect_notes(track.data(), (int64_t)track.size(), sr, 256, 0, &np, &out, &nn);
+    if (rc < 0) {
+      CHECK(out == nullptr && nn == -5, "mx_detect_notes: outputs set on failure");
+      return {rc, 0};
+    }
+    const uint64_t h = fnv(out, (size_t)nn * sizeof(mx_note), (uint64_t)nn);
+    mx_free(out);
+    return {rc, h};
+  });
+  std::vector<float> flux(400, 0.5f);
+  for (const int f : {50, 150, 300}) flux[(size_t)f] = 20.f;
+  sweep("mx_onset_pick", [&]() -> Result {
+    mx_onset *out = nullptr;
+    int64_t no = -5;
+    const int rc = mx_onset_pick(flux.data(), (int64_t)flux.size(), 256, 0, nullptr, &out, &no);
+    if (rc < 0) {
+      CHECK(out == nullptr && no == -5, "mx_onset_pick: outputs set on failure");
+      return {rc, 0};
+    }
+    const uint64_t h = fnv(out, (size_t)no * sizeof(mx_onset), (uint64_t)no);
+    mx_free(out);
+    return {rc, h};
+  });
+  sweep("mx_timing_markers", [&]() -> Result {
+    const int32_t anchors[3] = {50 * 256, 150 * 256, 300 * 256};
+    mx_marker *out = nullptr;
+    int64_t no = -5;
+    const int rc = mx_timing_markers(anchors, 3, n, sr, nullptr, nullptr, 0, &out, &no);
+    if (rc < 0) {
+      CHECK(out == nullptr && no == -5, "mx_timing_markers: outputs set on failure");
+      return {rc, 0};
+    }
+    uint64_t h = (uint64_t)no;
+    for (int64_t i = 0; i < no; ++i) h = fnv(&out[i].pitchBend, 8, fnv(&out[i].dTime, 8, fnv(&out[i].note, 8, fnv(&out[i].sample, 4, h))));
+    mx_free(out);
+    return {rc, h};
+  });
+}
+
+// The analysis units over the device take (tempo, chroma and key, pitch contour, f0 decode): their host forms pass through the
+// context's staging buffers, work memory and job buffers.  The inputs of each are made once, unfaulted.
+void analysis_entries(mx_ctx *ctx, mx_audio *a, int sr, int hop, int64_t F) {
+  std::vector<float> flux((size_t)F), curve((size_t)F);
+  CHECK(mx_onset_flux(ctx, a, sr, hop, 0, F, nullptr, flux.data()) == MX_OK, "flux: %s", mx_last_error());
+  sweep("mx_tempo_smooth", [&]() -> Result {
+    const int rc = mx_tempo_smooth(ctx, flux.data(), F, 4, curve.data());
+    return {rc, rc < 0 ? 0 : fnv(curve.data(), curve.size() * 4)};
+  });
+  std::vector<mx_comb_job> combs;
+  for (int k = 0; k < 12; ++k) combs.push_back(mx_comb_job{k, (int32_t)F - 2 * k, (uint32_t)(40 + 7 * k) << 16});
+  sweep("mx_tempo_comb", [&]() -> Result {
+    std::vector<mx_comb> rec(combs.size());
+    const int rc = mx_tempo_comb(ctx, curve.data(), F, combs.data(), (int64_t)combs.size(), rec.data());
+    return {rc, rc < 0 ? 0 : fnv(rec.data(), rec.size() * sizeof(mx_comb))};
+  });
+  auto tempo_result = [&](const char *name, int rc, const mx_tempo &t, mx_tempo_window *win, int64_t nwin) -> Result {
+    if (rc < 0) {
+      CHECK(t.levels == -7 && win == nullptr && nwin == -5, "%s: outputs set on failure", name);
+      return {rc, 0};
+    }
+    const double v[6] = {t.bpm, t.offset, (double)t.score, (double)t.clarity, (double)t.locked_frames, (double)t.levels};
+    const uint64_t h = fnv(win, (size_t)nwin * sizeof(mx_tempo_window), fnv(v, sizeof v));
+    mx_free(win);
+    return {rc, h};
+  };
+  sweep("mx_tempo_from_flux (windows)", [&]() -> Result {
+    mx_tempo t{};
+    t.levels = -7;
+    mx_tempo_window *win = nullptr;
+    int64_t nwin = -5;
+    const int rc = mx_tempo_from_flux(ctx, flux.data(), F, sr, hop, 0, nullptr, &t, &win, &nwin);
+    return tempo_result("mx_tempo_from_flux", rc, t, win, nwin);
+  });
+  sweep("mx_tempo_detect", [&]() -> Result {
+    mx_tempo t{};
+    t.levels = -7;
+    mx_tempo_window *win = nullptr;
+    int64_t nwin = -5;
+    const int rc = mx_tempo_detect(ctx, a, sr, hop, nullptr, nullptr, &t, &win, &nwin);
+    return tempo_result("mx_tempo_detect", rc, t, win, nwin);
+  });
+  std::vector<mx_chroma_rec> chroma((size_t)F);
+  sweep("mx_chroma", [&]() -> Result {
+    const int rc = mx_chroma(ctx, a, sr, hop, 0, F, nullptr, chroma.data());
+    return {rc, rc < 0 ? 0 : fnv(chroma.data(), chroma.size() * sizeof(mx_chroma_rec))};
+  });
+  sweep("mx_chroma_sum", [&]() -> Result {
+    const mx_chroma_job jobs[3] = {{0, F}, {10, 100}, {F, 0}};
+    double sums[3 * 40];
+    const int rc = mx_chroma_sum(ctx, chroma.data(), F, jobs, 3, sums);
+    return {rc, rc < 0 ? 0 : fnv(sums, sizeof sums)};
+  });
+  sweep("mx_key_detect (windows)", [&]() -> Result {
+    mx_key key{};
+    key.tonic = -7;
+    mx_key_window *win = nullptr;
+    int64_t nwin = -5;
+    const int rc = mx_key_detect(ctx, a, sr, hop, nullptr, 256, 128, &key, &win, &nwin);
+    if (rc < 0) {
+      CHECK(key.tonic == -7 && win == nullptr && nwin == -5, "mx_key_detect: outputs set on failure");
+      return {rc, 0};
+    }
+    const uint64_t h = fnv(win, (size_t)nwin * sizeof(mx_key_window), fnv(&key, sizeof key));
+    mx_free(win);
+    return {rc, h};
+  });
+  std::vector<mx_f0> track((size_t)F), decoded((size_t)F);
+  std::vector<mx_f0_cand> cands((size_t)F * MX_F0_CANDS);
+  CHECK(mx_f0_candidates(ctx, a, sr, hop, 0, F, 55.f, 1760.f, 0.15f, track.data(), cands.data()) == MX_OK, "ladder: %s", mx_last_error());
+  sweep("mx_f0_decode", [&]() -> Result {
+    std::vector<uint8_t> state((size_t)F);
+    const int rc = mx_f0_decode(ctx, track.data(), cands.data(), F, nullptr, decoded.data(), state.data());
+    return {rc, rc < 0 ? 0 : fnv(state.data(), state.size(), fnv(decoded.data(), decoded.size() * sizeof(mx_f0)))};
+  });
+  sweep("mx_f0_track_decoded", [&]() -> Result {
+    const int rc = mx_f0_track_decoded(ctx, a, sr, hop, 0, F, 55.f, 1760.f, 0.15f, nullptr, decoded.data());
+    return {rc, rc < 0 ? 0 : fnv(decoded.data(), decoded.size() * sizeof(mx_f0))};
+  });
+  std::vector<int32_t> cents((size_t)F);
+  sweep("mx_contour_cents", [&]() -> Result {
+    const int rc = mx_contour_cents(ctx, decoded.data(), F, sr, 0.15f, 1e-3f, cents.data());
+    return {rc, rc < 0 ? 0 : fnv(cents.data(), cents.size() * 4)};
+  });
+  // spans: the voiced runs of the take, cut into pieces of up to 100 frames (at least 4); the notes that give them
+  std::vector<mx_contour_span> spans;
+  std::vector<mx_note> notes;
+  for (int64_t f = 0, run = 0; f <= F; ++f) {
+    const bool voiced = f < F && cents[(size_t)f] != MX_CONTOUR_NONE;
+    if (voiced && run < 100) {
+      ++run;
+      continue;
+    }
+    if (run >= 4) {
+      spans.push_back(mx_contour_span{(int32_t)(f - run), (int32_t)run});
+      notes.push_back(mx_note{(int32_t)((f - run) * hop), (int32_t)((f - 1) * hop), (int32_t)(f - run), (int32_t)run, 60., 0.f, 0.f});
+    }
+    run = voiced ? 1 : 0;
+  }
+  const int64_t ns = (int64_t)spans.size();
+  CHECK(ns >= 2, "the take gives %lld spans", (long long)ns);
+  mx_contour_params cp{};
+  CHECK(mx_contour_params_default(sr, hop, &cp) == MX_OK, "contour parameters: %s", mx_last_error());
+  std::vector<mx_contour_rec> rec((size_t)F);
+  std::vector<mx_contour_stat> stat((size_t)ns);
+  sweep("mx_contour_split", [&]() -> Result {
+    const int rc = mx_contour_split(ctx, cents.data(), F, spans.data(), ns, &cp, rec.data(), stat.data());
+    return {rc, rc < 0 ? 0 : fnv(stat.data(), stat.size() * sizeof(mx_contour_stat), fnv(rec.data(), rec.size() * sizeof(mx_contour_rec)))};
+  });
+  sweep("mx_contour_split (statistics)", [&]() -> Result {
+    const int rc = mx_contour_split(ctx, cents.data(), F, spans.data(), ns, &cp, nullptr, stat.data());
+    return {rc, rc < 0 ? 0 : fnv(stat.data(), stat.size() * sizeof(mx_contour_stat))};
+  });
+  sweep("mx_pitch_contour", [&]() -> Result {
+    const int rc = mx_pitch_contour(ctx, decoded.data(), F, sr, hop, 0, notes.data(), ns, 0.15f, 1e-3f, nullptr, rec.data(), stat.data());
+    return {rc, rc < 0 ? 0 : fnv(stat.data(), stat.size() * sizeof(mx_contour_stat), fnv(rec.data(), rec.size() * sizeof(mx_contour_rec)))};
+  });
 }
 
 void device_entries() {
@@ -612,6 +778,7 @@ void device_entries() {
     const int rc = mx_f0_track(ctx, a, sr, hop, 0, F, 55.f, 1760.f, 0.15f, f0.data());
     return {rc, rc < 0 ? 0 : fnv(f0.data(), f0.size() * sizeof(mx_f0))};
   });
+  analysis_entries(ctx, a, sr, hop, F);
   // the mastering chain at the smallest sizes that take every branch: 2049 samples at 48 kHz (one limiter tile plus one sample, 5
   // steps, one group) and one sample
   for (const int64_t len : {(int64_t)2049, (int64_t)1}) {
