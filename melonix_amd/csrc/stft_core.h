@@ -957,6 +957,22 @@ MX_HD uint32_t band_mask(int t, int kmin, int kmax) {
   }
   return m;
 }
+// The pitch key of one bin: (magnitude bits << 32) | (0x7fffffff - bin); a bin outside [kmin, kmax] gives 0.
+MX_HD unsigned long long pick_key(float mag, int bin, int kmin, int kmax) {
+  const unsigned in = (bin >= kmin && bin <= kmax) ? 0xffffffffu : 0u;
+  return ((unsigned long long)(__builtin_bit_cast(unsigned, mag) & in) << 32) | ((0x7fffffffu - (unsigned)bin) & in);
+}
+// Row-side pick (stft_kernel ROWPICK): the best key of a lane that holds the four consecutive bins b0 .. b0 + 3 of a
+// finished row, taken in ascending bin order with a strict > — the keys and the order of the transform-side pick.
+MX_HD unsigned long long row_pick_key(int b0, float m0, float m1, float m2, float m3, int kmin, int kmax) {
+  unsigned long long best = pick_key(m0, b0, kmin, kmax);
+  const unsigned long long k1 = pick_key(m1, b0 + 1, kmin, kmax), k2 = pick_key(m2, b0 + 2, kmin, kmax),
+                           k3 = pick_key(m3, b0 + 3, kmin, kmax);
+  best = k1 > best ? k1 : best;
+  best = k2 > best ? k2 : best;
+  best = k3 > best ? k3 : best;
+  return best;
+}
 
 // Post-split twiddles of thread t: u[s] = i*exp(-2*pi*i*k_s/N) for the slot's bin k_s.
 // ubase[t] = i*exp(-2*pi*i*t/N) comes from the table; k_s = t + NS3*s adds exp(-2*pi*i*s/(2*R3)).

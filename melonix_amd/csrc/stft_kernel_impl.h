@@ -70,6 +70,11 @@ __device__ __forceinline__ void st_row_nt(const float *base, unsigned off, float
 //   CMAP         RGB8 texel output (the fused colormap of SpecCache::populateTex)
 //   DIRECT       (N = 32768) the row leaves straight from the registers, one dword per lane and slot
 //   CIRC         the circular sliding window (stft_core.h)
+//   ROWPICK      (DEFER, rows and pitch records both wanted, band below bin 256) the pitch record is picked where the row
+//                is flushed: wave 0's lanes hold bins 4t .. 4t+3 of the finished row there, so the band is one f32x4 of one
+//                wave; the transform-side pick (per-slot keys in both waves, red[], flush_pitch) is compiled out.  The keys,
+//                their order and the tie rule are the same, the values are the same floats after an LDS round trip: the
+//                record is bit for bit the transform-side one.  The host selects it (stft_kernels.hip: launch_plan).
 // Twiddle placement follows from the plan: the pass-2 table always lives in LDS (shared by the workgroup's waves); with
 // R3 = 8 (N = 4096) a thread's seven pass-3 twiddles and its post-split twiddles stay in registers for the whole
 // workgroup; with R3 = 16 (N = 16384 / 32768) six pass-3 base powers stay in registers, the other nine twiddles are one
@@ -79,7 +84,7 @@ __device__ __forceinline__ void st_row_nt(const float *base, unsigned off, float
 // and table values out of the frame loop and the kernel spills.  The thread index is therefore re-materialised per
 // frame — an empty asm — which keeps the invariants as a handful of cheap VALU ops inside the loop.)
 template <class P, int MODE, int HOP, int WPE, bool DEFER = false, bool PREFETCH = false, bool CMAP = false, bool DIRECT = false,
-          bool CIRC = false>
+          bool CIRC = false, bool ROWPICK = false>
 __global__ __launch_bounds__(P::T) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void stft_kernel(const StftArgs a0) {
   const StftArgs &a = a0;
@@ -94,6 +99,8 @@ void stft_kernel(const StftArgs a0) {
   constexpr int kTw2 = ((C::TW2 + 1) / 2) * 2;
   static_assert(P::R3 == 16 || P::R3 == 8, "twiddle placement per plan");
   static_assert(!DIRECT || (NW > 1 && !DEFER && !CMAP), "direct row stores: multi-wave, non-deferred plans");
+  static_assert(!ROWPICK || (DEFER && NW > 1 && !CMAP && !DIRECT && C::M / 4 / C::T >= 1 && C::T >= 128),
+                "row-side pitch pick: the deferred two-wave plan, rows without texels");
   static_assert(!CIRC || (MODE != kRanges && HOP == 0 && !PREFETCH && !CMAP), "circular window: bulk modes");
   constexpr int IMG = t1_size<C>();
   __shared__ __attribute__((aligned(16))) float2 lds[IMG + kRed + (DEFER ? C::M / 2 : 0) + kTw2];
@@ -113,12 +120,15 @@ void stft_kernel(const StftArgs a0) {
     post_twiddles<P>(t_, a.ubase, *reinterpret_cast<cpx(*)[P::R3]>(&u));
     fetch_tw3<P>(t_, a.tw3, *reinterpret_cast<cpx(*)[P::R3 - 1]>(&w3r));
   }
-  const uint32_t bmask_ = band_mask<P>(t_, a.kmin, a.kmax);
+  uint32_t bmask_ = 0;
   // output slots some lane of this wavefront needs for the pitch pick (wave-uniform)
   uint32_t umask = 0;
+  if constexpr (!ROWPICK) {
+    bmask_ = band_mask<P>(t_, a.kmin, a.kmax);
 #pragma unroll
-  for (int o = 0; o < P::E; ++o) umask |= (__ballot((bmask_ >> o) & 1u) != 0ull) ? (1u << o) : 0u;
-  umask = __builtin_amdgcn_readfirstlane(umask);
+    for (int o = 0; o < P::E; ++o) umask |= (__ballot((bmask_ >> o) & 1u) != 0ull) ? (1u << o) : 0u;
+    umask = __builtin_amdgcn_readfirstlane(umask);
+  }
   constexpr bool kSlide = (MODE == kBulkAligned) && (HOP > 0) && Slide<P, (HOP > 0 ? HOP : 2)>::ok;
   constexpr int SD = Slide<P, (HOP > 0 ? HOP : 2)>::D;
   constexpr float kSc = 0.5f / (float)N;
@@ -150,7 +160,7 @@ void stft_kernel(const StftArgs a0) {
   // output path.
   unsigned long long *const red = reinterpret_cast<unsigned long long *>(lds + IMG);
   auto flush_pitch = [&](int64_t fr, int tt) {  // after a barrier that follows red[] of frame fr
-    if (a.pitch && tt == 0) {
+    if (!ROWPICK && a.pitch && tt == 0) {
       unsigned long long b = red[0];
 #pragma unroll
       for (int i = 1; i < NW; ++i) b = red[i] > b ? red[i] : b;
@@ -175,6 +185,19 @@ void stft_kernel(const StftArgs a0) {
 #pragma unroll
         for (int i = 0; i < C::M / 4 / C::T; ++i) {
           __builtin_nontemporal_store(q[i], &row4[C::T * i]);
+        }
+      }
+      if constexpr (ROWPICK) {
+        // the band lies in bins 0 .. 255: q[0] of wave 0, four consecutive bins to a lane (tt is re-materialised per
+        // frame, so the in-band tests stay a few VALU ops inside the loop)
+        if (wave0) {
+          const unsigned long long b = wave_max_u64(row_pick_key(4 * tt, q[0].x, q[0].y, q[0].z, q[0].w, a.kmin, a.kmax));
+          if (tt == 0) {
+            mx_pitch p;
+            p.bin = 0x7fffffff - (int)(unsigned)(b & 0xffffffffull);
+            p.mag = __uint_as_float((unsigned)(b >> 32));
+            a.pitch[fr] = p;
+          }
         }
       }
       if constexpr (CMAP) {
@@ -334,7 +357,7 @@ void stft_kernel(const StftArgs a0) {
     // bit patterns, so max(key) = largest magnitude, lowest bin on ties; out-of-band -> 0.
     // bins: even o -> (s < R3/2 ? lo : hi) + NS3*s, odd o -> M - that (thread 0, s = R3/2: M/2)
     unsigned long long best = 0ull;
-    if (a.pitch) {
+    if (!ROWPICK && a.pitch) {
       const unsigned klo = 0x7fffffffu - (unsigned)out_lo, khi = 0x7fffffffu - (unsigned)out_hi;
       const unsigned nlo = 0x7fffffffu - (unsigned)(C::M - out_lo), nhi = 0x7fffffffu - (unsigned)(C::M - out_hi);
 #pragma unroll
