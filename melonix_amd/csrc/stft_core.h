@@ -796,8 +796,17 @@ MX_HD void pass3_bases(int t, cpx (&v)[P::E], const cpx (&wb)[6]) {
   }
   pass3_reg<P, MAY0>(t, v, w);
 }
-template <class P, bool MAY0 = true>
-MX_HD void pass3_reg(int t, cpx (&v)[P::E], const cpx (&w)[P::R3 - 1]) {
+// Thread 0's P butterfly takes 1 for every twiddle: wp[r] = csel(t == 0, 1, w[r - 1]).  The select does not depend on the
+// frame, so a caller with registers to spare makes the first KH of them once (pass3_wp0) and hands them in as wph.
+template <class P, int KH>
+MX_HD void pass3_wp0(int t, const cpx (&w)[P::R3 - 1], cpx (&wph)[KH > 0 ? KH : 1]) {
+  static_assert(KH >= 0 && KH <= P::R3 - 1, "at most every twiddle");
+  wph[0] = mk(1.0f, 0.0f);
+#pragma unroll
+  for (int r = 1; r <= KH; ++r) wph[r - 1] = csel(t == 0, mk(1.0f, 0.0f), w[r - 1]);
+}
+template <class P, bool MAY0 = true, int KH = 0>
+MX_HD void pass3_reg(int t, cpx (&v)[P::E], const cpx (&w)[P::R3 - 1], const cpx (&wph)[KH > 0 ? KH : 1]) {
   constexpr int R = P::R3;
   const bool t0 = MAY0 && (t == 0);
   cpx inp[R], inq[R], wp[R], wq[R], out[R];
@@ -809,7 +818,7 @@ MX_HD void pass3_reg(int t, cpx (&v)[P::E], const cpx (&w)[P::R3 - 1]) {
   }
 #pragma unroll
   for (int r = 1; r < R; ++r) {
-    wp[r] = csel(t0, mk(1.0f, 0.0f), w[r - 1]);
+    wp[r] = (MAY0 && r <= KH) ? wph[r <= KH ? r - 1 : 0] : csel(t0, mk(1.0f, 0.0f), w[r - 1]);
     wq[r] = w[r - 1];
   }
   DftTw<R, 1, 0, false>::run(inp, wp, out);
@@ -818,6 +827,11 @@ MX_HD void pass3_reg(int t, cpx (&v)[P::E], const cpx (&w)[P::R3 - 1]) {
   DftTw<R, 1, 0, true>::run(inq, wq, out);
 #pragma unroll
   for (int r = 0; r < R; ++r) v[R + r] = out[r];
+}
+template <class P, bool MAY0>
+MX_HD void pass3_reg(int t, cpx (&v)[P::E], const cpx (&w)[P::R3 - 1]) {  // every select per call
+  const cpx none[1] = {mk(1.0f, 0.0f)};
+  pass3_reg<P, MAY0, 0>(t, v, w, none);
 }
 
 // ---- real-FFT split + magnitude ---------------------------------------------
@@ -958,9 +972,12 @@ MX_HD uint32_t band_mask(int t, int kmin, int kmax) {
   return m;
 }
 // The pitch key of one bin: (magnitude bits << 32) | (0x7fffffff - bin); a bin outside [kmin, kmax] gives 0.
-MX_HD unsigned long long pick_key(float mag, int bin, int kmin, int kmax) {
-  const unsigned in = (bin >= kmin && bin <= kmax) ? 0xffffffffu : 0u;
+MX_HD unsigned long long pick_key(float mag, int bin, bool in_band) {
+  const unsigned in = in_band ? 0xffffffffu : 0u;
   return ((unsigned long long)(__builtin_bit_cast(unsigned, mag) & in) << 32) | ((0x7fffffffu - (unsigned)bin) & in);
+}
+MX_HD unsigned long long pick_key(float mag, int bin, int kmin, int kmax) {
+  return pick_key(mag, bin, bin >= kmin && bin <= kmax);
 }
 // Row-side pick (stft_kernel ROWPICK): the best key of a lane that holds the four consecutive bins b0 .. b0 + 3 of a
 // finished row, taken in ascending bin order with a strict > — the keys and the order of the transform-side pick.
@@ -972,6 +989,27 @@ MX_HD unsigned long long row_pick_key(int b0, float m0, float m1, float m2, floa
   best = k2 > best ? k2 : best;
   best = k3 > best ? k3 : best;
   return best;
+}
+// The same with the four in-band tests taken once, by the caller: in_j says whether bin b0 + j lies in [kmin, kmax].  The
+// band and a lane's bins do not change from frame to frame, so the kernel keeps the tests (as lane masks) and builds the
+// same keys in the same ascending order with the same strict >.
+MX_HD unsigned long long row_pick_key(int b0, float m0, float m1, float m2, float m3, bool in0, bool in1, bool in2, bool in3) {
+  unsigned long long best = pick_key(m0, b0, in0);
+  const unsigned long long k1 = pick_key(m1, b0 + 1, in1), k2 = pick_key(m2, b0 + 2, in2), k3 = pick_key(m3, b0 + 3, in3);
+  best = k1 > best ? k1 : best;
+  best = k2 > best ? k2 : best;
+  best = k3 > best ? k3 : best;
+  return best;
+}
+// ... as one 4-bit mask per lane: bit j of row_band_mask(b0, kmin, kmax) is set iff bin b0 + j lies in [kmin, kmax]
+MX_HD unsigned row_band_mask(int b0, int kmin, int kmax) {
+  unsigned m = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m |= (b0 + j >= kmin && b0 + j <= kmax) ? (1u << j) : 0u;
+  return m;
+}
+MX_HD unsigned long long row_pick_key(int b0, float m0, float m1, float m2, float m3, unsigned mask) {
+  return row_pick_key(b0, m0, m1, m2, m3, (mask & 1u) != 0, (mask & 2u) != 0, (mask & 4u) != 0, (mask & 8u) != 0);
 }
 
 // Post-split twiddles of thread t: u[s] = i*exp(-2*pi*i*k_s/N) for the slot's bin k_s.

@@ -91,9 +91,9 @@ void stft_kernel(const StftArgs a0) {
   using C = P;
   constexpr int N = P::N;
   constexpr int NW = C::T / 64;  // wavefronts per frame
-  // one LDS object: the image (with the first transposition's padding), NW 8-byte reduction slots (padded to 16 B),
-  // — DEFER — a separate M-float region for the magnitude transposition, so that the image can be refilled by the next
-  // frame without an extra barrier, and the pass-2 twiddle table
+  // one LDS object: the image (with the first transposition's padding), — DEFER — a separate M-float region for the
+  // magnitude transposition, so that the image can be refilled by the next frame without an extra barrier, NW 8-byte
+  // reduction slots (padded to 16 B; they follow the image where nothing is deferred), and the pass-2 twiddle table
   constexpr int kRed = (NW > 1) ? ((NW + 1) / 2) * 2 : 0;
   constexpr bool kTw3Bases = (P::R3 == 16);
   constexpr int kTw2 = ((C::TW2 + 1) / 2) * 2;
@@ -104,10 +104,14 @@ void stft_kernel(const StftArgs a0) {
   static_assert(!CIRC || (MODE != kRanges && HOP == 0 && !PREFETCH && !CMAP), "circular window: bulk modes");
   constexpr int IMG = t1_size<C>();
   __shared__ __attribute__((aligned(16))) float2 lds[IMG + kRed + (DEFER ? C::M / 2 : 0) + kTw2];
-  float *const lout = reinterpret_cast<float *>(DEFER ? lds + IMG + kRed : lds);
+  // (DEFER: the row region follows the image directly, so that it starts on a multiple of 256 bytes: the scatter's slots,
+  // 4*NS3 = 1024 bytes apart, then pair into ds_write2st64_b32 off one base register; the reduction slots come after it)
+  float *const lout = reinterpret_cast<float *>(DEFER ? lds + IMG : lds);
   float2 *const ltw2 = lds + IMG + kRed + (DEFER ? C::M / 2 : 0);
 
   const int t_ = threadIdx.x;
+  constexpr bool kSlide = (MODE == kBulkAligned) && (HOP > 0) && Slide<P, (HOP > 0 ? HOP : 2)>::ok;
+  constexpr int SD = Slide<P, (HOP > 0 ? HOP : 2)>::D;
   const bool wave0 = __builtin_amdgcn_readfirstlane(t_) < 64;  // wave-uniform
   cpx u[kTw3Bases ? 1 : P::R3];  // post-split twiddles (R3 = 8: registers that replace R3 complex multiplies per frame)
   cpx ulo;  // (thread 0's second base, (-1, 0), is re-selected per frame in the one wavefront that holds thread 0)
@@ -120,6 +124,14 @@ void stft_kernel(const StftArgs a0) {
     post_twiddles<P>(t_, a.ubase, *reinterpret_cast<cpx(*)[P::R3]>(&u));
     fetch_tw3<P>(t_, a.tw3, *reinterpret_cast<cpx(*)[P::R3 - 1]>(&w3r));
   }
+  // Thread 0's selected pass-3 twiddles (stft_core.h: pass3_wp0), as many as the instantiation's register budget leaves
+  // room for next to the frame image: two registers each under the 168 of three waves per SIMD, no scratch.  The row-side
+  // pick's direct-load kernels (162 registers) and its one-slot slide (hop 256: 168) take all seven, a two-slot slide
+  // (hop 512: four more edge and prefetch registers) three (168); every other instantiation keeps the per-frame selects
+  // (tests/test_stft_resources.py holds every N = 4096 instantiation to 168 registers and no scratch).
+  constexpr int kTw3Hoist = (!kTw3Bases && ROWPICK) ? ((kSlide && SD > 1) ? 3 : P::R3 - 1) : 0;
+  cpx w3p[kTw3Hoist > 0 ? kTw3Hoist : 1];
+  if constexpr (!kTw3Bases) pass3_wp0<P, kTw3Hoist>(t_, *reinterpret_cast<cpx(*)[P::R3 - 1]>(&w3r), w3p);
   uint32_t bmask_ = 0;
   // output slots some lane of this wavefront needs for the pitch pick (wave-uniform)
   uint32_t umask = 0;
@@ -129,8 +141,14 @@ void stft_kernel(const StftArgs a0) {
     for (int o = 0; o < P::E; ++o) umask |= (__ballot((bmask_ >> o) & 1u) != 0ull) ? (1u << o) : 0u;
     umask = __builtin_amdgcn_readfirstlane(umask);
   }
-  constexpr bool kSlide = (MODE == kBulkAligned) && (HOP > 0) && Slide<P, (HOP > 0 ? HOP : 2)>::ok;
-  constexpr int SD = Slide<P, (HOP > 0 ? HOP : 2)>::D;
+  // the row-side pick's in-band tests, once: wave 0's lane tt holds bins 4 tt .. 4 tt + 3 of a finished row (flush_row), and
+  // neither they nor the band change from frame to frame — one lane mask per bin (four SGPR pairs, no vector register)
+  unsigned long long rin[4] = {0ull, 0ull, 0ull, 0ull};
+  if constexpr (ROWPICK) {
+    const unsigned rm = row_band_mask(4 * t_, a.kmin, a.kmax);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rin[j] = __ballot((rm >> j) & 1u);
+  }
   constexpr float kSc = 0.5f / (float)N;
   for (int i = t_; i < C::TW2; i += C::T) ltw2[i] = a.tw2[i];
   MX_BARRIER();
@@ -158,7 +176,7 @@ void stft_kernel(const StftArgs a0) {
   // DEFER: the magnitude row and the pitch record of frame f leave the workgroup during frame f+1 — scatter at the
   // end of f, LDS read + global stores after f+1's T1 barrier — so no barrier and no LDS round trip sits in the
   // output path.
-  unsigned long long *const red = reinterpret_cast<unsigned long long *>(lds + IMG);
+  unsigned long long *const red = reinterpret_cast<unsigned long long *>(lds + IMG + (DEFER ? C::M / 2 : 0));
   auto flush_pitch = [&](int64_t fr, int tt) {  // after a barrier that follows red[] of frame fr
     if (!ROWPICK && a.pitch && tt == 0) {
       unsigned long long b = red[0];
@@ -173,6 +191,7 @@ void stft_kernel(const StftArgs a0) {
   // CMAP (ranges mode): the row can also leave as RGB8 texels — SpecCache::populateTex's colormap
   // (spec-cache.cpp:77-96) applied to the four consecutive bins a lane holds, 12 bytes per lane.
   const bool want_rows = a.mags != nullptr || (CMAP && a.rgb != nullptr);
+  constexpr bool kRowSaddr = (C::M / 4 / C::T == 4) && (C::T * 16 == 2048);  // N = 4096: four stores, 2 KiB apart
   auto flush_row = [&](int64_t fr, int tt) {  // after a barrier that follows the scatter of frame fr
     if (want_rows) {
       using f32x4 = float __attribute__((ext_vector_type(4)));
@@ -182,16 +201,39 @@ void stft_kernel(const StftArgs a0) {
 #pragma unroll
       for (int i = 0; i < C::M / 4 / C::T; ++i) q[i] = l4[C::T * i];
       if (!CMAP || a.mags) {
+        if constexpr (kRowSaddr) {
+          // wave-uniform row base (an SGPR pair, biased by half the row so that the four immediates -4096 .. +2048 fit the
+          // store's 13 bits) + one 32-bit lane offset: global_store_dwordx4 v_off, v_data, s[base] offset:imm nt
+          // (the biased base passes through an empty asm as a scalar: left to itself the compiler folds the bias back into the
+          // offsets and builds a 64-bit per-lane address for the two stores past +4095)
+          uintptr_t mid = reinterpret_cast<uintptr_t>(a.mags + (size_t)fr * (size_t)(N / 2)) + 4096;
+#if defined(__HIP_DEVICE_COMPILE__)
+          asm volatile("" : "+s"(mid));
+          using gchar = __attribute__((address_space(1))) char;
+          using gf32x4 = __attribute__((address_space(1))) f32x4;
+#else
+          using gchar = char;
+          using gf32x4 = f32x4;
+#endif
+          const unsigned off = 16u * (unsigned)tt;
 #pragma unroll
-        for (int i = 0; i < C::M / 4 / C::T; ++i) {
-          __builtin_nontemporal_store(q[i], &row4[C::T * i]);
+          for (int i = 0; i < 4; ++i)
+            __builtin_nontemporal_store(q[i], reinterpret_cast<gf32x4 *>(reinterpret_cast<gchar *>(mid) + off + (2048 * i - 4096)));
+        } else {
+#pragma unroll
+          for (int i = 0; i < C::M / 4 / C::T; ++i) {
+            __builtin_nontemporal_store(q[i], &row4[C::T * i]);
+          }
         }
       }
       if constexpr (ROWPICK) {
-        // the band lies in bins 0 .. 255: q[0] of wave 0, four consecutive bins to a lane (tt is re-materialised per
-        // frame, so the in-band tests stay a few VALU ops inside the loop)
+        // the band lies in bins 0 .. 255: q[0] of wave 0, four consecutive bins to a lane, whose in-band tests are the
+        // lane masks rin[] (taken once per workgroup)
         if (wave0) {
-          const unsigned long long b = wave_max_u64(row_pick_key(4 * tt, q[0].x, q[0].y, q[0].z, q[0].w, a.kmin, a.kmax));
+          const unsigned long long b = wave_max_u64(row_pick_key(
+              4 * tt, q[0].x, q[0].y, q[0].z, q[0].w, __builtin_amdgcn_inverse_ballot_w64(rin[0]),
+              __builtin_amdgcn_inverse_ballot_w64(rin[1]), __builtin_amdgcn_inverse_ballot_w64(rin[2]),
+              __builtin_amdgcn_inverse_ballot_w64(rin[3])));
           if (tt == 0) {
             mx_pitch p;
             p.bin = 0x7fffffff - (int)(unsigned)(b & 0xffffffffull);
@@ -328,7 +370,7 @@ void stft_kernel(const StftArgs a0) {
         pass3_bases<P, true>(t, v, w3base);
         post_fly<P, true>(t, v, ulo, csel(t == 0, mk(-1.0f, 0.0f), ulo), mg);
       } else {
-        pass3_reg<P, true>(t, v, *reinterpret_cast<cpx(*)[P::R3 - 1]>(&w3r));
+        pass3_reg<P, true, kTw3Hoist>(t, v, *reinterpret_cast<cpx(*)[P::R3 - 1]>(&w3r), w3p);
         post<P, true>(t, v, *reinterpret_cast<cpx(*)[P::R3]>(&u), mg);
       }
     } else {
@@ -416,13 +458,15 @@ void stft_kernel(const StftArgs a0) {
     } else if (want_rows) {
       float *plo = lout + out_lo, *phi = lout + out_hi;
       float *mlo = lout + (C::M - out_lo), *mhi = lout + (C::M - out_hi);
+      constexpr int H = C::R3 / 2;
+      // slots that share a base one after the other (the direct half going up, the mirrored half going down), so that two
+      // neighbours leave as one ds_write2st64_b32; thread 0's bin-M/2 slot keeps a write of its own
 #pragma unroll
-      for (int s = 0; s < C::R3; ++s) {
-        constexpr int H = C::R3 / 2;
-        (s < H ? plo : phi)[C::NS3 * s] = mg[2 * s];
-        if (s == H) (t == 0 ? lout + C::M / 2 : mhi - C::NS3 * H)[0] = mg[2 * s + 1];
-        else (s < H ? mlo : mhi)[-C::NS3 * s] = mg[2 * s + 1];
-      }
+      for (int s = 0; s < C::R3; ++s) (s < H ? plo : phi)[C::NS3 * s] = mg[2 * s];
+#pragma unroll
+      for (int s = 0; s < C::R3; ++s)
+        if (s != H) (s < H ? mlo : mhi)[-C::NS3 * s] = mg[2 * s + 1];
+      (t == 0 ? lout + C::M / 2 : mhi - C::NS3 * H)[0] = mg[2 * H + 1];
     }
     if constexpr (!DEFER && !DIRECT) {
       if (want_rows) {
