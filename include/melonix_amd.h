@@ -1422,6 +1422,62 @@ int mx_loudness_range(const mx_loud_step *steps, int64_t nsteps, int sampleRate,
  * MX_ERR_INVALID (amp untouched) when integrated is not finite, true_peak is 0 or not finite, or an argument is not finite. */
 int mx_normalize_gain_tp(const mx_loudness *m, float true_peak, double target_lufs, double ceiling_dbtp, float *amp);
 
+/* ---- Sample-rate conversion (BUILD-DEFINED; restated by tests/resample_ref.py) ----
+ * A take at another sample rate: a polyphase windowed-sinc filter with one table, one summation order and the same bytes on the
+ * device, in the CPU emulation and in numpy, whatever the launch split.  The reference has none of it (its SwrContext keeps the
+ * rate).  In the export chain it sits BEFORE the limiter: a true peak is a property of the samples at the delivered rate.
+ *
+ * Plan, for rates in [8000, 384000]:  g = gcd(in, out), L = out / g, M = in / g, s = min(1, L / M);  Z = 32 zero crossings a
+ * side, H = ceil(Z / s) = ceil(Z max(L, M) / L) in integers, T = 2 H taps.  Refused (MX_ERR_INVALID): a rate out of range,
+ * L > 1024, T > 512.  Equal rates are not refused: the plan is {L = 1, M = 1, T = 0, H = 0} and every form below copies the
+ * input's bytes; there is no table.  48000 -> 44100 is 147 / 160 with T = 70, 44100 -> 48000 is 160 / 147 with T = 64,
+ * 96000 -> 48000 is 1 / 2 with T = 128, 192000 -> 44100 is 147 / 640 with T = 280; 384000 -> 44100 (T = 558) and
+ * 44100 -> 48001 (L = 48001) are refused.
+ *
+ * Length: m = ceil(n L / M) outputs; output j sits at input time j M / L: the conversion is centred and adds no delay.
+ *
+ * Table: h[phi][k], phase phi < L, tap k < T, belongs to the input sample at offset d = k - (H - 1) from i_j, at distance
+ * u = d - phi / L from the output.  In binary64:  h = s sinc(s u) w(u / H),  sinc(v) = sin(pi v) / (pi v) (1 at 0),
+ * w(t) = I0(12 sqrt(1 - t^2)) / I0(12), the Kaiser window with beta = 12;  I0(x) is the power series sum of ((x / 2)^k / k!)^2
+ * summed in ascending k until a term falls below 2^-60 of the sum.  Each row is divided by its binary64 sum (k ascending), so DC
+ * passes at 1; then each tap is rounded to binary32.  One exception, exact by definition: where s = 1 and phi = 0 the row is the
+ * unit row, 1 at d = 0 and +0 elsewhere (sin(pi k) is not 0 in floating point, and an output that falls on an input sample shall
+ * be that sample).  mx_resample_taps hands the table out: the device, the emulation and numpy all read that one table.
+ *
+ * An output:  i_j = floor(j M / L), phi_j = (j M) mod L, in 64-bit integers;
+ *   y_j = sum over k ascending of x[i_j - (H - 1) + k] * h[phi_j][k], from +0.f, each product rounded, then added, in binary32
+ * without contraction (the true peak's rule).  Samples outside [0, n) are zeros whatever the pads hold.  A NaN or +-Inf is plain
+ * arithmetic.
+ *
+ * Consequences (tests pin all six, on the emulation and on the device):
+ *   1. unit rows: where L > M, out[j] for (j M) mod L = 0 has the bytes of x[j M / L] for every finite window;
+ *   2. scale: resample(2^k x) = 2^k resample(x) bit for bit where nothing leaves the normal range;
+ *   3. silence, of -0.0f samples too, gives +0.f everywhere;
+ *   4. locality: sample s changes no output outside those j with s - H <= i_j <= s + H - 1; a NaN at s makes exactly those NaN;
+ *   5. shift: x delayed by M samples is the output delayed by L samples, byte for byte, away from the file's ends;
+ *   6. split: any split of [0, m) into ranges gives the same bytes. */
+typedef struct mx_resample_plan {
+  int32_t L;    /* phases: out / gcd */
+  int32_t M;    /* in / gcd */
+  int32_t taps; /* T = 2 H; 0 for equal rates */
+  int32_t half; /* H */
+} mx_resample_plan;
+/* The plan of inRate -> outRate.  MX_ERR_INVALID (out untouched) for what the plan refuses, or NULL. */
+int mx_resample_plan_for(int inRate, int outRate, mx_resample_plan *out);
+/* m for n samples; negative (MX_ERR_INVALID) for n < 0 or a refused rate pair. */
+int64_t mx_resample_length(int64_t n, int inRate, int outRate);
+/* out = h[0][0 .. T), h[1][0 .. T), ...: L * T floats (none for equal rates).  MX_ERR_INVALID for a refused rate pair or NULL. */
+int mx_resample_taps(int inRate, int outRate, float *out);
+/* Outputs [first_out, first_out + count) of the converted take -> d_out[0 .. count) (in HBM, at any 4-byte-aligned address).
+ * Asynchronous on the context's stream.  An empty range is legal.  MX_ERR_INVALID, before any launch and with nothing written,
+ * for a refused rate pair, a range outside [0, m), NULLs (d_out may be NULL where count is 0) or a misaligned d_out. */
+int mx_resample_dev(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, float *d_out);
+/* Same, host output staged through device memory of the call's own.  Blocks. */
+int mx_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, float *out);
+/* The converted take as a new audio object of m samples (zeroed pads, as mx_audio_gain_dev; release it with mx_audio_free).
+ * Asynchronous on the context's stream.  MX_ERR_INVALID, with *out untouched, for a refused rate pair or NULLs. */
+int mx_audio_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, mx_audio **out);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

@@ -39,7 +39,8 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "bend_params_default", "contour_spans", "contour_vibrato", "contour_bend", "psola_plan_bend", "psola_plan_formant_bend",
            "LOUD_STEP_DTYPE", "LOUD_GROUP_STEPS", "level_params_default", "loudness_step_count", "loudness_coeffs", "loudness_curve",
            "loudness_integrated", "note_loudness", "level_gain_points", "normalize_gain",
-           "TP_STEP_DTYPE", "true_peak_oversampling", "true_peak_taps", "limit_params_default", "loudness_range", "normalize_gain_tp"]
+           "TP_STEP_DTYPE", "true_peak_oversampling", "true_peak_taps", "limit_params_default", "loudness_range", "normalize_gain_tp",
+           "resample_plan", "resample_length", "resample_taps"]
 
 
 # The two pointer forms of an optional argument.  New wrappers use these: _opt for a host array, _dev for a device address.
@@ -59,11 +60,11 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
-_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget")  # they return a count, or a negative status
+_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget", "mx_resample_length")  # they return a count, or a negative status
 
 
 def _call(name: str, *args):
-    """The entry point `name` with args, its status checked (MxError); the count of the two entry points that return one."""
+    """The entry point `name` with args, its status checked (MxError); the count of the entry points that return one."""
     rc = getattr(_capi.lib(), name)(*args)
     if name in _COUNT_CALLS:
         if rc < 0:
@@ -641,6 +642,24 @@ class Context:
 
     def normalize_gain_tp(self, measured: dict, true_peak: float, target_lufs: float = -23.0, ceiling_dbtp: float = -1.0) -> float:
         return normalize_gain_tp(measured, true_peak, target_lufs, ceiling_dbtp)
+
+    # ---- sample-rate conversion (build-defined; include/melonix_amd.h) ----
+    def resample(self, audio: Audio, in_rate: int, out_rate: int) -> Audio:
+        """A new Audio: `audio` converted from in_rate to out_rate, resample_length(audio.n, ...) samples (equal rates: a copy).
+        Asynchronous on the context's stream."""
+        return self._audio(resample_length(audio.n, in_rate, out_rate), "mx_audio_resample", audio.handle, in_rate, out_rate)
+
+    def resample_dev(self, audio: Audio, in_rate: int, out_rate: int, first_out: int, count: int, d_out: int):
+        """Outputs [first_out, first_out + count) of the converted take stay in HBM at d_out (4-byte aligned); asynchronous on the
+        context's stream."""
+        _call("mx_resample_dev", self.handle, audio.handle, in_rate, out_rate, first_out, count, _dev(d_out))
+
+    def resample_range(self, audio: Audio, in_rate: int, out_rate: int, first_out: int = 0, count: int | None = None):
+        """-> float32 outputs [first_out, first_out + count) of the converted take (count None: to its end).  Blocks."""
+        count = resample_length(audio.n, in_rate, out_rate) - first_out if count is None else count
+        out = np.empty(max(count, 0), dtype=np.float32)
+        _call("mx_resample", self.handle, audio.handle, in_rate, out_rate, first_out, count, _ptr(out))
+        return out
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
     def tempo_smooth(self, flux, width: int = 4):
@@ -1259,3 +1278,24 @@ def normalize_gain_tp(measured: dict, true_peak: float, target_lufs: float = -23
     _call("mx_normalize_gain_tp", C.byref(_capi.Loudness(**measured)), float(true_peak), float(target_lufs), float(ceiling_dbtp),
           C.byref(amp))
     return amp.value
+
+
+# ---- sample-rate conversion: the plan, the length and the tap table of a rate pair (host; build-defined) ----
+def resample_plan(in_rate: int, out_rate: int) -> dict:
+    """The plan of in_rate -> out_rate -> {L, M, taps, half}; equal rates: {1, 1, 0, 0}.  MxError for a refused pair."""
+    p = _capi.ResamplePlan()
+    _call("mx_resample_plan_for", int(in_rate), int(out_rate), C.byref(p))
+    return _fields(p)
+
+
+def resample_length(n: int, in_rate: int, out_rate: int) -> int:
+    """m = ceil(n L / M): the samples of a take of n converted from in_rate to out_rate."""
+    return _call("mx_resample_length", int(n), int(in_rate), int(out_rate))
+
+
+def resample_taps(in_rate: int, out_rate: int):
+    """The tap table -> float32[L, taps], a row per phase ([1, 0] for equal rates)."""
+    p = resample_plan(in_rate, out_rate)
+    out = np.empty((p["L"], p["taps"]), dtype=np.float32)
+    _call("mx_resample_taps", int(in_rate), int(out_rate), _ptr(out))
+    return out

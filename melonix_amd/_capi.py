@@ -212,6 +212,10 @@ class LoudnessRange(C.Structure):
                 ("gated", C.c_int64), ("bad", C.c_int64)]
 
 
+class ResamplePlan(C.Structure):
+    _fields_ = [("L", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("half", C.c_int32)]
+
+
 # the C type of every record class, in the order of include/melonix_amd.h.  A record is declared here once, as its class: the
 # field names are the header's, the numpy dtypes below are derived from the classes, and tests/test_abi.py compares every
 # class's size, field offsets and field sizes with what a C compiler makes of the header.  (mx_chroma_rec has no class: a
@@ -228,7 +232,7 @@ RECORDS = {
     "mx_contour_span": ContourSpan, "mx_contour_params": ContourParams, "mx_contour_rec": ContourRec,
     "mx_contour_stat": ContourStat, "mx_vibrato": Vibrato, "mx_bend_params": BendParams, "mx_loud_step": LoudStep,
     "mx_loudness": Loudness, "mx_level_params": LevelParams, "mx_tp_step": TpStep, "mx_limit_params": LimitParams,
-    "mx_loudness_range_result": LoudnessRange,
+    "mx_loudness_range_result": LoudnessRange, "mx_resample_plan": ResamplePlan,
 }
 
 PITCH_DTYPE, STEP_DTYPE, MARKER_DTYPE = np.dtype(Pitch), np.dtype(Step), np.dtype(Marker)
@@ -426,6 +430,12 @@ SIGNATURES = {
     "mx_audio_limit": (_i, [_vp, _vp, _i, C.POINTER(LimitParams), C.POINTER(_vp), _vp]),
     "mx_loudness_range": (_i, [_vp, _i64, _i, C.POINTER(LoudnessRange)]),
     "mx_normalize_gain_tp": (_i, [C.POINTER(Loudness), _f, _d, _d, C.POINTER(_f)]),
+    "mx_resample_plan_for": (_i, [_i, _i, C.POINTER(ResamplePlan)]),
+    "mx_resample_length": (_i64, [_i64, _i, _i]),
+    "mx_resample_taps": (_i, [_i, _i, _vp]),
+    "mx_resample_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp]),
+    "mx_resample": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp]),
+    "mx_audio_resample": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

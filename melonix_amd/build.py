@@ -62,6 +62,9 @@ UNITS = [
     # build-defined true-peak records and look-ahead limiter: binary32 taps with every product rounded before its sum, integers
     # from the peak to the gain (truepeak_core.h), bit for bit numpy's
     ("truepeak_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined sample-rate conversion: binary32 taps with every product rounded before its sum, in ascending tap order
+    # (resample_core.h), bit for bit numpy's
+    ("resample_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -80,6 +83,7 @@ UNITS = [
     ("capi_loudness.cpp", "hip", []),
     ("capi_truepeak.cpp", "hip", []),
     ("capi_audio.cpp", "hip", []),
+    ("capi_resample.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
@@ -90,6 +94,7 @@ UNITS = [
     ("key_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("contour_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("loudness_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("resample_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

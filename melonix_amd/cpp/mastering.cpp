@@ -35,28 +35,42 @@ double Mastering::truePeakDb() const {
 }
 
 std::vector<int16_t> Mastering::finish(double targetLufs, double ceilingDbtp, double lookaheadMs) const {
+  return finishAt(sampleRate, targetLufs, ceilingDbtp, lookaheadMs);
+}
+
+std::vector<int16_t> Mastering::finishAt(int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
   float amp = 1.f;
   // (a ceiling far above any take: the loudness term alone)
   if (!good || mx_normalize_gain_tp(&loudness_, truePeak_, targetLufs, 200.0, &amp) != MX_OK) return {};
-  mx_limit_params p;
-  if (mx_limit_params_default(sampleRate, &p) != MX_OK || !std::isfinite(ceilingDbtp) || !std::isfinite(lookaheadMs)) return {};
+  const int64_t m = mx_resample_length((int64_t)wav_.size(), sampleRate, outRate);
+  mx_limit_params p;  // the limiter works at the rate it delivers
+  if (m < 0 || mx_limit_params_default(outRate, &p) != MX_OK || !std::isfinite(ceilingDbtp) || !std::isfinite(lookaheadMs)) return {};
   p.ceiling_amp = (float)std::pow(10.0, ceilingDbtp / 20.0);
   if (lookaheadMs > 0.0) {
-    const double a = std::floor(lookaheadMs * (double)sampleRate / 1000.0 + 0.5);
+    const double a = std::floor(lookaheadMs * (double)outRate / 1000.0 + 0.5);
     p.lookahead = a < 1.0 ? 1 : a > 1024.0 ? 1024 : (int32_t)a;
   }
-  std::vector<int16_t> out(wav_.size());
+  std::vector<int16_t> out((size_t)m);
   glue::Session s(device_, wav_);
   const mx_gain_point point{0, amp};
-  const bool done = s.ok && mx_audio_gain(s.ctx, s.audio, &point, 1, &s.made[0]) == MX_OK &&
-                    mx_audio_limit(s.ctx, s.made[0], sampleRate, &p, &s.made[1], out.data()) == MX_OK;
+  bool done = s.ok && mx_audio_gain(s.ctx, s.audio, &point, 1, &s.made[0]) == MX_OK;
+  const mx_audio *levelled = s.made[0];
+  if (done && outRate != sampleRate) {  // conversion before the limiter: a true peak belongs to the delivered samples
+    done = mx_audio_resample(s.ctx, levelled, sampleRate, outRate, &s.made[1]) == MX_OK;
+    levelled = s.made[1];
+  }
+  done = done && mx_audio_limit(s.ctx, levelled, outRate, &p, &s.made[2], out.data()) == MX_OK;
   if (!done) out.clear();
   return out;
 }
 
 bool Mastering::exportWav(const std::string &path, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
-  const std::vector<int16_t> pcm = finish(targetLufs, ceilingDbtp, lookaheadMs);
-  return !pcm.empty() && mx_save_wav(path.c_str(), pcm.data(), (int64_t)pcm.size(), sampleRate, 0) == MX_OK;
+  return exportWavAt(path, sampleRate, targetLufs, ceilingDbtp, lookaheadMs);
+}
+
+bool Mastering::exportWavAt(const std::string &path, int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
+  const std::vector<int16_t> pcm = finishAt(outRate, targetLufs, ceilingDbtp, lookaheadMs);
+  return !pcm.empty() && mx_save_wav(path.c_str(), pcm.data(), (int64_t)pcm.size(), outRate, 0) == MX_OK;
 }
 
 }  // namespace melonix

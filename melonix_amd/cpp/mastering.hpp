@@ -1,11 +1,13 @@
 // mastering.hpp — NOT in the reference (it has no meter and no limiter): the end of the export chain over the build-defined
 // entry points — the take's BS.1770 loudness, its true peak (mx_true_peak_steps) and its loudness range (mx_loudness_range), and
 // the finished int16: the gain that brings the take to a target loudness (mx_normalize_gain_tp, mx_audio_gain), then the
-// look-ahead limiter under a true-peak ceiling (mx_audio_limit) — as a class the App can own next to its melonix::LoudnessTrack.
+// look-ahead limiter under a true-peak ceiling (mx_audio_limit), with the sample-rate conversion between the two where the take is
+// delivered at another rate (mx_audio_resample) — as a class the App can own next to its melonix::LoudnessTrack.
 //
 //   melonix::Mastering master(rendered, sampleRate);         // uploads once; loudness, true peak and range on the GPU
 //   meter->show(master.loudness().integrated, master.truePeakDb(), master.range().lra);
 //   master.exportWav("take.wav", -16.0, -1.0);               // -16 LUFS under -1 dBTP, a correct RIFF header
+//   master.exportWavAt("take-cd.wav", 44100, -16.0, -1.0);   // the same delivered at 44.1 kHz: converted, then limited
 //
 // A render that is already on the device needs no round trip: render f32 into a padded device buffer, mx_audio_wrap_device it
 // and call mx_audio_gain / mx_audio_limit_dev directly.
@@ -42,6 +44,13 @@ public:
   std::vector<int16_t> finish(double targetLufs, double ceilingDbtp, double lookaheadMs = 0.0) const;
   // finish() into a WAV file with a correct RIFF header (mx_save_wav); false after a failed call
   bool exportWav(const std::string &path, double targetLufs, double ceilingDbtp, double lookaheadMs = 0.0) const;
+  // The same delivered at outRate: the gain finish() takes (from the measurement at the take's own rate), then the sample-rate
+  // conversion (mx_audio_resample), then the limiter at outRate — after the conversion, since a true peak is a property of the
+  // delivered samples —, mx_resample_length(n, sampleRate, outRate) samples of int16; lookaheadMs is taken at outRate.  At the
+  // take's own rate: finish().  Empty for a rate pair the conversion refuses.
+  std::vector<int16_t> finishAt(int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs = 0.0) const;
+  // finishAt() into a WAV file whose header carries outRate
+  bool exportWavAt(const std::string &path, int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs = 0.0) const;
 
 private:
   int sampleRate, device_;

@@ -1,8 +1,10 @@
-// capi_audio.cpp — the audio objects made from another one on the device: the source gain (gain_kernels.hip) and the look-ahead
-// limiter (truepeak_kernels.hip), and the download of an audio object's samples: BUILD-DEFINED, the reference has none of it.  One
+// capi_audio.cpp — the audio objects made from another one on the device: the source gain (gain_kernels.hip), the look-ahead
+// limiter (truepeak_kernels.hip) and the sample-rate conversion (resample_kernels.hip; its range forms: capi_resample.cpp), and
+// the download of an audio object's samples: BUILD-DEFINED, the reference has none of it.  One
 // unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).  (mx_audio_upload, _wrap_device, _free:
 // capi_ctx.cpp.)
 #include "capi_internal.h"
+#include "resample_core.h"
 #include "sibilant_logic.h"
 #include "truepeak_core.h"
 
@@ -10,14 +12,14 @@ using namespace mx;
 
 namespace {
 
-// A new audio object of a's length at *out: zeroed pads, and the samples that `fill(dst) -> hipError_t` queues behind the two
+// A new audio object of n samples at *out: zeroed pads, and the samples that `fill(dst) -> hipError_t` queues behind the two
 // clears (not called for an empty take).  Queued on the context's stream; nothing is left allocated where it fails.  `what` names
 // the call in a device error.
 template <class F>
-int derived_audio(mx_ctx *ctx, const mx_audio *a, const char *what, F &&fill, mx_audio **out) {
+int derived_audio(mx_ctx *ctx, int64_t length, const char *what, F &&fill, mx_audio **out) {
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mx_audio> b(new mx_audio());
-  const size_t n = (size_t)a->n, pad = (size_t)MX_AUDIO_PAD;
+  const size_t n = (size_t)length, pad = (size_t)MX_AUDIO_PAD;
   hipError_t e = hipMalloc(&b->d_padded, (n + 2 * pad) * sizeof(float));
   if (e != hipSuccess) return fail(MX_ERR_NOMEM, "audio buffer: %s", hipGetErrorString(e));
   e = hipMemsetAsync(b->d_padded, 0, pad * sizeof(float), ctx->stream);
@@ -28,7 +30,7 @@ int derived_audio(mx_ctx *ctx, const mx_audio *a, const char *what, F &&fill, mx
     hipFree(b->d_padded);
     return fail(MX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
   }
-  b->n = a->n;
+  b->n = length;
   b->owned = true;
   *out = b.release();
   return MX_OK;
@@ -38,9 +40,9 @@ int derived_audio(mx_ctx *ctx, const mx_audio *a, const char *what, F &&fill, mx
 // reach `host` (may be null: nothing) behind the fill; one synchronise; where that fails the new object goes the way
 // mx_audio_free releases one and *out is left alone.
 template <class T, class F>
-int derived_audio_host(mx_ctx *ctx, const mx_audio *a, const char *what, const DeviceArray<T> &d, T *host, F &&fill, mx_audio **out) {
+int derived_audio_host(mx_ctx *ctx, int64_t length, const char *what, const DeviceArray<T> &d, T *host, F &&fill, mx_audio **out) {
   mx_audio *b = nullptr;
-  if (const int rc = derived_audio(ctx, a, what, fill, &b)) return rc;
+  if (const int rc = derived_audio(ctx, length, what, fill, &b)) return rc;
   hipError_t e = d.download(host);
   const hipError_t es = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = es;
@@ -99,7 +101,7 @@ extern "C" {
 int mx_audio_gain_dev(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_points, int64_t npts, mx_audio **out) {
   return mx_guard([&]() -> int {
     if (!ctx || !a || !out || npts < 0 || (npts > 0 && !d_points)) return fail(MX_ERR_INVALID, "bad argument");
-    return derived_audio(ctx, a, "audio gain", gain_fill(ctx, a, d_points, npts), out);
+    return derived_audio(ctx, a->n, "audio gain", gain_fill(ctx, a, d_points, npts), out);
   });
 }
 
@@ -113,7 +115,7 @@ int mx_audio_gain(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *points, i
     if (e != hipSuccess) return fail(MX_ERR_NOMEM, "gain points: %s", hipGetErrorString(e));
     if (npts) e = hipMemcpyAsync(d.p, points, (size_t)npts * sizeof(mx_gain_point), hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) return fail(MX_ERR_DEVICE, "gain points upload: %s", hipGetErrorString(e));
-    return derived_audio_host(ctx, a, "audio gain", d, (mx_gain_point *)nullptr, gain_fill(ctx, a, d.p, npts), out);
+    return derived_audio_host(ctx, a->n, "audio gain", d, (mx_gain_point *)nullptr, gain_fill(ctx, a, d.p, npts), out);
   });
 }
 
@@ -146,7 +148,7 @@ int mx_audio_limit_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_
   return mx_guard([&]() -> int {
     mx_limit_params p;
     if (const int rc = limit_parse(ctx, a, sampleRate, params, out, p)) return rc;
-    return derived_audio(ctx, a, "audio limit", limit_fill(ctx, a, sampleRate, p, d_pcm16), out);
+    return derived_audio(ctx, a->n, "audio limit", limit_fill(ctx, a, sampleRate, p, d_pcm16), out);
   });
 }
 
@@ -158,7 +160,20 @@ int mx_audio_limit(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limi
     DeviceArray<int16_t> d;
     const hipError_t e = d.alloc(ctx->stream, pcm16_out ? (size_t)a->n : 0);
     if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device PCM buffer: %s", hipGetErrorString(e));
-    return derived_audio_host(ctx, a, "audio limit", d, pcm16_out, limit_fill(ctx, a, sampleRate, p, d.p), out);
+    return derived_audio_host(ctx, a->n, "audio limit", d, pcm16_out, limit_fill(ctx, a, sampleRate, p, d.p), out);
+  });
+}
+
+int mx_audio_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, mx_audio **out) {
+  return mx_guard([&]() -> int {
+    if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+    mx_resample_plan p;
+    if (const int rc = resample_plan_check(inRate, outRate, p)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const float *d_table = nullptr;
+    if (const int rc = resample_table_dev(ctx, p, &d_table)) return rc;
+    const int64_t m = rs::out_length(a->n, p);
+    return derived_audio(ctx, m, "audio resample", [=](float *dst) { return resample_enqueue(ctx, a, p, d_table, 0, m, dst); }, out);
   });
 }
 

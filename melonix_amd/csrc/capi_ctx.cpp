@@ -213,6 +213,7 @@ void mx_ctx_destroy(mx_ctx *ctx) {
     hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->tables) free_tables(kv.second);
     for (auto &kv : ctx->wtabs) hipFree(kv.second);
+    for (auto &kv : ctx->rtabs) hipFree(kv.second);
     hipFree(ctx->onset_tw);
     hipFree(ctx->chroma_hann);
     for_each_work(ctx, [](auto &set) { set.drop(); });  // (no locks: the context is the caller's alone)

@@ -251,6 +251,7 @@ struct mx_ctx {
   int frames_per_block = 0;  // 0 = per-N default
   float2 *onset_tw = nullptr;  // the 1024-point transform's twiddles (onset_table), built on first use under mu
   float *chroma_hann = nullptr;  // the chroma frame's window (chroma_window), built on first use under mu
+  std::map<std::pair<int, int>, float *> rtabs;  // (L, M) -> the resampler's taps, a row per tap index (resample_table_dev)
   std::mutex mu;
   // Device memory kept between calls, one WorkMem each (for_each_work names them all; mx_ctx_release_scratch gives them back).
   // stage: staging of the host-pointer entry points (mx_stft_ranges, mx_stft_hop, mx_stft_ranges_rgb*, mx_rows_colormap, mx_f0_track,
@@ -306,6 +307,14 @@ int onset_table(mx_ctx *ctx, const float2 **out);
 // The chroma frame's window (capi_key.cpp): periodic Hann over 4096 samples, pre-scaled by 1/2048, in HBM, built on the context's
 // first use and kept until it goes.
 int chroma_window(mx_ctx *ctx, const float **out);
+// The sample-rate conversion's pieces that its entry points (capi_resample.cpp) and mx_audio_resample (capi_audio.cpp) share:
+// the plan of a rate pair or its refusal, worded once; the plan's tap table in HBM (a row per tap index), built on the context's
+// first use of (L, M) and kept until it goes, null for equal rates; and outputs [first, first + count) queued on the context's
+// stream — the kernel, or for equal rates a copy of the input's bytes.
+int resample_plan_check(int inRate, int outRate, mx_resample_plan &p);
+int resample_table_dev(mx_ctx *ctx, const mx_resample_plan &p, const float **out);
+hipError_t resample_enqueue(mx_ctx *ctx, const mx_audio *a, const mx_resample_plan &p, const float *d_table, int64_t first,
+                            int64_t count, float *d_out);
 int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_t first_frame, const int32_t *d_ranges,
                 int64_t count, int kmin, int kmax, float *d_mags, mx_pitch *d_pitch, uint8_t *d_rgb, float cmap_k,
                 int run_length = 0);

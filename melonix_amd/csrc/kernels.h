@@ -280,6 +280,19 @@ struct LimitArgs {
   int16_t *pcm16;
 };
 hipError_t launch_audio_limit(const LimitArgs &a, hipStream_t s);
+// Build-defined sample-rate conversion (resample_kernels.hip; definition: include/melonix_amd.h, arithmetic: resample_core.h).
+// Outputs [first_out, first_out + count) of the converted take, all inside [0, m), plan a plan of rs::plan_for with taps > 0:
+// checked by the caller.  table: the plan's taps with a row per tap index (resample_table_by_tap), in HBM.  out: 4-byte aligned;
+// no store outside out[0 .. count).
+struct ResampleArgs {
+  const float *image;  // padded image (the samples outside the file are taken as zeros whatever the pads hold)
+  int64_t n;
+  mx_resample_plan plan;
+  const float *table;
+  int64_t first_out, count;
+  float *out;
+};
+hipError_t launch_resample(const ResampleArgs &a, hipStream_t s);
 // Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
 // count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
 // range (the caller's check) gives a wrong record and nothing worse.

@@ -22,6 +22,7 @@
 // [0, n) of the outputs only.
 #include <hip/hip_runtime.h>
 
+#include "image_quads.h"
 #include "kernels.h"
 #include "pcm16.h"
 #include "truepeak_core.h"
@@ -31,21 +32,7 @@ namespace {
 
 constexpr int kThreads = 256, kWave = 64, kWaves = kThreads / kWave;
 constexpr int kHalo = 2;  // quads either side of a lane's quad: 8 samples, at least the 5 before and the 6 after a sample
-static_assert(MX_AUDIO_PAD % 4 == 0, "an aligned quad of the image is an aligned quad of the samples");
 static_assert(4 * kHalo >= tp::kAfter && 4 * kHalo >= tp::kBefore, "the halo holds every window of the quad");
-
-// the aligned quad `quad` of the padded image, its samples outside [0, n) as zeros
-__device__ __forceinline__ float4 load_quad(const float4 *img, int64_t quad, int64_t n) {
-  float4 v = img[quad];
-  const int64_t i = 4 * quad - MX_AUDIO_PAD;
-  if (i < 0 || i + 3 >= n) {
-    if (i + 0 < 0 || i + 0 >= n) v.x = 0.f;
-    if (i + 1 < 0 || i + 1 >= n) v.y = 0.f;
-    if (i + 2 < 0 || i + 2 >= n) v.z = 0.f;
-    if (i + 3 < 0 || i + 3 >= n) v.w = 0.f;
-  }
-  return v;
-}
 
 // quads k - 2 .. k + 2 of an LDS image as 20 floats: w[8 + e] is sample e of quad k
 __device__ __forceinline__ void read_window(const float4 *lds, int k, float (&w)[4 * (2 * kHalo + 1)]) {
