@@ -671,6 +671,90 @@ MX_HD void load_t1_tw2(int t, cpx (&v)[P::E], const cpx *lds, const cpx *ltw2, c
 #endif
 }
 
+// ---- the q-major T1 image (stft_kernel T1Q: the N = 4096 plan's row-side-pick kernels) -------------------------
+// The XOR layout above pays one v_xor per scattered point and two alternate read bases, per frame, for its freedom from
+// bank conflicts.  Stored q-major — pass-1 output q of butterfly j at point q*PITCH + j — the image needs neither:
+//   store  thread t (butterfly j = t) writes its 16 outputs at (lds + t)[q*PITCH]: one base, sixteen immediates; a
+//          16-lane write group covers 128 consecutive bytes (32 banks, each once);
+//   read   thread t is pass-2 butterfly (q = t & 15, a = t >> 4) and wants j = a + 8 r, r = 0..15:
+//          (lds + PITCH*(t & 15) + (t >> 4))[8 r]: one base, sixteen immediates.  A ds_read_b64 is served in 32-lane
+//          groups over 64 dword banks: the 8-byte slot index mod 32 of a group's lanes, (PITCH*q + a + 8 r) mod 32 with
+//          q = 0..15 and a in {2g, 2g + 1}, must be 32 different values: PITCH = 130 gives 2 q + a (+ 8 r) = 0..31 (+ 8 r);
+//          129 gives q + a, two lanes to a slot.  130 is the smallest pitch without conflicts.
+// The image is 16*130 = 2080 points, 32 more than the XOR image; T2 keeps using its first M points.  A kernel that takes
+// it keeps its LDS by holding the last two rows (r = 14, 15) of the pass-2 twiddle table in registers: kT1qTwRows rows of
+// R1 entries stay in LDS, 2080 + 13*16 = 2048 + 15*16.
+constexpr int kT1qPitch = 130;
+constexpr int kT1qTwRows = 13;
+template <class P>
+MX_HD constexpr int t1q_size() { return P::R1 * kT1qPitch; }
+MX_HD constexpr int t1q_index(int j, int q) { return q * kT1qPitch + j; }
+template <class P>
+MX_HD void store_t1q(int t, const cpx (&v)[P::E], cpx *lds) {
+  static_assert(P::NB1 == 1 && P::R1 == 16 && P::T <= kT1qPitch, "the q-major image is written for the N = 4096 plan");
+  cpx *const p = lds + t;
+#ifdef MX_LDS_ASM
+  // (volatile: sixteen ds_write_b64 off the one base.  Left to merge them, the compiler pairs neighbours into ds_write2_b64,
+  // whose 8-bit offsets do not reach past the second row: seven more base registers, and the wider store is no faster)
+  volatile __attribute__((address_space(3))) mx_f2v *const lp = (volatile __attribute__((address_space(3))) mx_f2v *)p;
+#pragma unroll
+  for (int q = 0; q < P::R1; ++q) lp[q * kT1qPitch] = mx_f2v{v[q].x, v[q].y};
+#else
+#pragma unroll
+  for (int q = 0; q < P::R1; ++q) p[q * kT1qPitch] = v[q];
+#endif
+}
+// pass-2 twiddle rows kT1qTwRows + 1 .. R2 - 1 of thread t, from the table in global memory (once per workgroup)
+template <class P>
+MX_HD void fetch_tw2_tail(int t, const cpx *tw2, cpx (&wt)[P::R2 - 1 - kT1qTwRows]) {
+#pragma unroll
+  for (int r = kT1qTwRows + 1; r < P::R2; ++r) wt[r - 1 - kT1qTwRows] = tw2[(r - 1) * P::R1 + (t & (P::R1 - 1))];
+}
+#ifdef MX_LDS_ASM
+__device__ __forceinline__ void lds_wait29(mx_f2v (&q)[29]) {  // 16 points + 13 twiddles behind one wait
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 24; i += 8)
+    asm volatile("" : "+v"(q[i]), "+v"(q[i + 1]), "+v"(q[i + 2]), "+v"(q[i + 3]), "+v"(q[i + 4]),
+                 "+v"(q[i + 5]), "+v"(q[i + 6]), "+v"(q[i + 7]));
+  asm volatile("" : "+v"(q[24]), "+v"(q[25]), "+v"(q[26]), "+v"(q[27]), "+v"(q[28]));
+}
+#endif
+// The T1 read of the q-major image plus the pass-2 twiddles: rows 1 .. kT1qTwRows from the LDS table, the rest (wt) from
+// the caller's registers — the same floats load_t1_tw2 brings, in the same order.
+template <class P>
+MX_HD void load_t1q_tw2(int t, cpx (&v)[P::E], const cpx *lds, const cpx *ltw2, const cpx (&wt)[P::R2 - 1 - kT1qTwRows],
+                        cpx (&w)[P::R2 - 1]) {
+  static_assert(P::NB2 == 1 && P::E == P::R2 && P::R2 == 16 && P::M / P::R2 == 8 * P::R1, "one pass-2 butterfly per thread, j = a + 8 r");
+  const int b1 = kT1qPitch * (t & (P::R1 - 1)) + (t >> P::L1);
+#ifdef MX_LDS_ASM
+  const uint32_t ab = lds_addr(lds + b1);
+  const uint32_t aw = lds_addr(ltw2 + (t & (P::R1 - 1)));
+  mx_f2v q[P::E + kT1qTwRows];
+  static_for<0, P::R2>([&](auto rr) {
+    constexpr int r = decltype(rr)::value;
+    q[r] = lds_rd64<r * 8 * 8>(ab);
+  });
+  static_for<1, kT1qTwRows + 1>([&](auto rr) {
+    constexpr int r = decltype(rr)::value;
+    q[P::E + r - 1] = lds_rd64<(r - 1) * P::R1 * 8>(aw);
+  });
+  lds_wait29(q);
+#pragma unroll
+  for (int i = 0; i < P::E; ++i) v[i] = mk(q[i].x, q[i].y);
+#pragma unroll
+  for (int r = 1; r <= kT1qTwRows; ++r) w[r - 1] = mk(q[P::E + r - 1].x, q[P::E + r - 1].y);
+#else
+  const cpx *pb = lds + b1, *pw = ltw2 + (t & (P::R1 - 1));
+#pragma unroll
+  for (int r = 0; r < P::R2; ++r) v[r] = pb[8 * r];
+#pragma unroll
+  for (int r = 1; r <= kT1qTwRows; ++r) w[r - 1] = pw[(r - 1) * P::R1];
+#endif
+#pragma unroll
+  for (int r = kT1qTwRows + 1; r < P::R2; ++r) w[r - 1] = wt[r - 1 - kT1qTwRows];
+}
+
 // ---- pass 2 ----------------------------------------------------------------
 // tw2[(r-1)*R1 + k] = exp(-2*pi*i*r*k/(R1*R2)), r = 1..R2-1, k = 0..R1-1
 template <class P>
@@ -1010,6 +1094,24 @@ MX_HD unsigned row_band_mask(int b0, int kmin, int kmax) {
 }
 MX_HD unsigned long long row_pick_key(int b0, float m0, float m1, float m2, float m3, unsigned mask) {
   return row_pick_key(b0, m0, m1, m2, m3, (mask & 1u) != 0, (mask & 2u) != 0, (mask & 4u) != 0, (mask & 8u) != 0);
+}
+
+// The row-side pick with ONE reduction.  Lane order is bin order (lane tt holds bins 4 tt .. 4 tt + 3), so the low word
+// of the key need not be reduced: the wavefront's maximum of the lanes' largest in-band magnitude bits (row_pick_lane_max,
+// out-of-band bins count as 0) is the high word of max(row_pick_key); the winner is the LOWEST lane that reaches it and
+// holds an in-band bin, and in that lane the first in-band bin whose bits equal it (row_pick_first).  That is the maximum
+// of the same keys: bits compared as unsigned (NaN and Inf patterns above every finite one), ties to the lowest in-band
+// bin, a silent band to its first bin.
+MX_HD unsigned row_pick_lane_max(float m0, float m1, float m2, float m3, bool in0, bool in1, bool in2, bool in3) {
+  const unsigned a = in0 ? __builtin_bit_cast(unsigned, m0) : 0u, b = in1 ? __builtin_bit_cast(unsigned, m1) : 0u;
+  const unsigned c = in2 ? __builtin_bit_cast(unsigned, m2) : 0u, d = in3 ? __builtin_bit_cast(unsigned, m3) : 0u;
+  const unsigned ab = a > b ? a : b, abc = ab > c ? ab : c;
+  return abc > d ? abc : d;
+}
+// j of the winner lane's bin: b0 .. b3 the lane's four magnitude bits, in0 .. in3 its in-band tests, mhi the wavefront's
+// maximum.  (The caller's lane reaches mhi with an in-band bin, or mhi is 0 and the lane has an in-band bin: some j fits.)
+MX_HD int row_pick_first(unsigned mhi, unsigned b0, unsigned b1, unsigned b2, unsigned b3, bool in0, bool in1, bool in2, bool in3) {
+  return (in0 && b0 == mhi) ? 0 : (in1 && b1 == mhi) ? 1 : (in2 && b2 == mhi) ? 2 : 3;
 }
 
 // Post-split twiddles of thread t: u[s] = i*exp(-2*pi*i*k_s/N) for the slot's bin k_s.

@@ -72,9 +72,14 @@ __device__ __forceinline__ void st_row_nt(const float *base, unsigned off, float
 //   CIRC         the circular sliding window (stft_core.h)
 //   ROWPICK      (DEFER, rows and pitch records both wanted, band below bin 256) the pitch record is picked where the row
 //                is flushed: wave 0's lanes hold bins 4t .. 4t+3 of the finished row there, so the band is one f32x4 of one
-//                wave; the transform-side pick (per-slot keys in both waves, red[], flush_pitch) is compiled out.  The keys,
-//                their order and the tie rule are the same, the values are the same floats after an LDS round trip: the
-//                record is bit for bit the transform-side one.  The host selects it (stft_kernels.hip: launch_plan).
+//                wave; the transform-side pick (per-slot keys in both waves, red[], flush_pitch) is compiled out.  Lane order
+//                is bin order there, so ONE reduction — of the lanes' largest in-band magnitude bits — and the lowest lane
+//                that reaches it give the maximum of the transform side's keys (stft_core.h: row_pick_lane_max), on the same
+//                floats after an LDS round trip: the record is bit for bit the transform-side one.  The host selects it
+//                (stft_kernels.hip: launch_plan).
+//   T1Q          (ROWPICK, N = 4096) the first transposition goes through the q-major image (stft_core.h: store_t1q): one
+//                store base and one read base with immediate offsets instead of a swizzle per point; the image's 32 extra
+//                points are paid for with the last two rows of the LDS pass-2 table, which this thread holds in registers
 // Twiddle placement follows from the plan: the pass-2 table always lives in LDS (shared by the workgroup's waves); with
 // R3 = 8 (N = 4096) a thread's seven pass-3 twiddles and its post-split twiddles stay in registers for the whole
 // workgroup; with R3 = 16 (N = 16384 / 32768) six pass-3 base powers stay in registers, the other nine twiddles are one
@@ -84,7 +89,7 @@ __device__ __forceinline__ void st_row_nt(const float *base, unsigned off, float
 // and table values out of the frame loop and the kernel spills.  The thread index is therefore re-materialised per
 // frame — an empty asm — which keeps the invariants as a handful of cheap VALU ops inside the loop.)
 template <class P, int MODE, int HOP, int WPE, bool DEFER = false, bool PREFETCH = false, bool CMAP = false, bool DIRECT = false,
-          bool CIRC = false, bool ROWPICK = false>
+          bool CIRC = false, bool ROWPICK = false, bool T1Q = false>
 __global__ __launch_bounds__(P::T) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void stft_kernel(const StftArgs a0) {
   const StftArgs &a = a0;
@@ -96,13 +101,16 @@ void stft_kernel(const StftArgs a0) {
   // reduction slots (padded to 16 B; they follow the image where nothing is deferred), and the pass-2 twiddle table
   constexpr int kRed = (NW > 1) ? ((NW + 1) / 2) * 2 : 0;
   constexpr bool kTw3Bases = (P::R3 == 16);
-  constexpr int kTw2 = ((C::TW2 + 1) / 2) * 2;
+  constexpr int kTw2N = T1Q ? kT1qTwRows * P::R1 : C::TW2;  // entries of the pass-2 table kept in LDS
+  constexpr int kTw2 = ((kTw2N + 1) / 2) * 2;
   static_assert(P::R3 == 16 || P::R3 == 8, "twiddle placement per plan");
   static_assert(!DIRECT || (NW > 1 && !DEFER && !CMAP), "direct row stores: multi-wave, non-deferred plans");
   static_assert(!ROWPICK || (DEFER && NW > 1 && !CMAP && !DIRECT && C::M / 4 / C::T >= 1 && C::T >= 128),
                 "row-side pitch pick: the deferred two-wave plan, rows without texels");
+  static_assert(!T1Q || (ROWPICK && P::NB2 == 1 && P::R1 == 16), "q-major T1 image: the N = 4096 row-side-pick kernels");
   static_assert(!CIRC || (MODE != kRanges && HOP == 0 && !PREFETCH && !CMAP), "circular window: bulk modes");
-  constexpr int IMG = t1_size<C>();
+  constexpr int IMG = T1Q ? t1q_size<C>() : t1_size<C>();
+  static_assert(!DEFER || (IMG * 8) % 256 == 0, "the row region starts on a multiple of 256 bytes");
   __shared__ __attribute__((aligned(16))) float2 lds[IMG + kRed + (DEFER ? C::M / 2 : 0) + kTw2];
   // (DEFER: the row region follows the image directly, so that it starts on a multiple of 256 bytes: the scatter's slots,
   // 4*NS3 = 1024 bytes apart, then pair into ds_write2st64_b32 off one base register; the reduction slots come after it)
@@ -126,8 +134,9 @@ void stft_kernel(const StftArgs a0) {
   }
   // Thread 0's selected pass-3 twiddles (stft_core.h: pass3_wp0), as many as the instantiation's register budget leaves
   // room for next to the frame image: two registers each under the 168 of three waves per SIMD, no scratch.  The row-side
-  // pick's direct-load kernels (162 registers) and its one-slot slide (hop 256: 168) take all seven, a two-slot slide
-  // (hop 512: four more edge and prefetch registers) three (168); every other instantiation keeps the per-frame selects
+  // pick's direct-load kernels (164 registers, with the q-major image's four twiddle registers) and its one-slot slide
+  // (hop 256: 167) take all seven, a two-slot slide (hop 512: four more edge and prefetch registers) three (165); every other
+  // instantiation keeps the per-frame selects
   // (tests/test_stft_resources.py holds every N = 4096 instantiation to 168 registers and no scratch).
   constexpr int kTw3Hoist = (!kTw3Bases && ROWPICK) ? ((kSlide && SD > 1) ? 3 : P::R3 - 1) : 0;
   cpx w3p[kTw3Hoist > 0 ? kTw3Hoist : 1];
@@ -149,8 +158,11 @@ void stft_kernel(const StftArgs a0) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) rin[j] = __ballot((rm >> j) & 1u);
   }
+  [[maybe_unused]] const unsigned long long rany = rin[0] | rin[1] | rin[2] | rin[3];  // wave 0's lanes that hold an in-band bin
   constexpr float kSc = 0.5f / (float)N;
-  for (int i = t_; i < C::TW2; i += C::T) ltw2[i] = a.tw2[i];
+  for (int i = t_; i < kTw2N; i += C::T) ltw2[i] = a.tw2[i];
+  cpx w2t[T1Q ? P::R2 - 1 - kT1qTwRows : 1];  // T1Q: the table rows that left the LDS
+  if constexpr (T1Q) fetch_tw2_tail<P>(t_, a.tw2, *reinterpret_cast<cpx(*)[P::R2 - 1 - kT1qTwRows]>(&w2t));
   MX_BARRIER();
 
   // XCD-aware block -> frame-range map: the dispatcher places block b on XCD b % 8 and each
@@ -229,15 +241,25 @@ void stft_kernel(const StftArgs a0) {
       if constexpr (ROWPICK) {
         // the band lies in bins 0 .. 255: q[0] of wave 0, four consecutive bins to a lane, whose in-band tests are the
         // lane masks rin[] (taken once per workgroup)
+        // lane order is bin order: one reduction of the lanes' largest in-band magnitude bits, then the lowest lane that
+        // reaches it (stft_core.h: row_pick_lane_max / row_pick_first) — everything after the reduction is scalar
         if (wave0) {
-          const unsigned long long b = wave_max_u64(row_pick_key(
-              4 * tt, q[0].x, q[0].y, q[0].z, q[0].w, __builtin_amdgcn_inverse_ballot_w64(rin[0]),
-              __builtin_amdgcn_inverse_ballot_w64(rin[1]), __builtin_amdgcn_inverse_ballot_w64(rin[2]),
-              __builtin_amdgcn_inverse_ballot_w64(rin[3])));
+          const unsigned m = row_pick_lane_max(q[0].x, q[0].y, q[0].z, q[0].w, __builtin_amdgcn_inverse_ballot_w64(rin[0]),
+                                               __builtin_amdgcn_inverse_ballot_w64(rin[1]), __builtin_amdgcn_inverse_ballot_w64(rin[2]),
+                                               __builtin_amdgcn_inverse_ballot_w64(rin[3]));
+          const unsigned mhi = wave_reduce_u32<true>(m);
+          const unsigned long long cand = __ballot(m == mhi) & rany;
+          const int L = __builtin_ctzll(cand);
+          const unsigned b0 = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(q[0].x), L);
+          const unsigned b1 = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(q[0].y), L);
+          const unsigned b2 = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(q[0].z), L);
+          const unsigned b3 = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(q[0].w), L);
+          const int j = row_pick_first(mhi, b0, b1, b2, b3, (rin[0] >> L) & 1ull, (rin[1] >> L) & 1ull, (rin[2] >> L) & 1ull,
+                                       (rin[3] >> L) & 1ull);
           if (tt == 0) {
             mx_pitch p;
-            p.bin = 0x7fffffff - (int)(unsigned)(b & 0xffffffffull);
-            p.mag = __uint_as_float((unsigned)(b >> 32));
+            p.bin = 4 * L + j;
+            p.mag = __uint_as_float(mhi);
             a.pitch[fr] = p;
           }
         }
@@ -339,14 +361,16 @@ void stft_kernel(const StftArgs a0) {
     pass1<P>(Y, v);
     // one pass-2 butterfly per thread (N = 4096, N = 32768): its twiddles ride with the T1 read, one batch, one wait
     constexpr bool kTw2Batch = (P::NB2 == 1);
-    store_t1<P>(t, v, lds);
+    if constexpr (T1Q) store_t1q<P>(t, v, lds);
+    else store_t1<P>(t, v, lds);
     MX_BARRIER();
     if constexpr (DEFER || DIRECT) {
       if (f > f0) flush_pitch(f - 1, t);
     }
     if constexpr (kTw2Batch) {
       cpx w2[P::R2 - 1];
-      load_t1_tw2<P>(t, v, lds, ltw2, w2);
+      if constexpr (T1Q) load_t1q_tw2<P>(t, v, lds, ltw2, *reinterpret_cast<cpx(*)[P::R2 - 1 - kT1qTwRows]>(&w2t), w2);
+      else load_t1_tw2<P>(t, v, lds, ltw2, w2);
       if constexpr (DEFER) {
         if (f > f0) flush_row(f - 1, t);  // previous frame's row: LDS -> HBM in the shadow of T1
       }

@@ -58,11 +58,11 @@ struct Tune {
 };
 
 // Launches the sliding-window kernel for HOP if the plan can slide by it (Slide<P,HOP>::ok) and the call asks for it.
-template <class P, int HOP, bool ROWPICK = false>
+template <class P, int HOP, bool ROWPICK = false, bool T1Q = false>
 bool try_slide(const StftArgs &b, dim3 grid, dim3 block, hipStream_t s) {
   if constexpr (Slide<P, HOP>::ok && Tune<P>::slides(HOP)) {
     if (b.hop != HOP) return false;
-    hipLaunchKernelGGL((stft_kernel<P, kBulkAligned, HOP, Tune<P>::WPE, Tune<P>::DEFER, false, false, Tune<P>::DIRECT, false, ROWPICK>),
+    hipLaunchKernelGGL((stft_kernel<P, kBulkAligned, HOP, Tune<P>::WPE, Tune<P>::DEFER, false, false, Tune<P>::DIRECT, false, ROWPICK, T1Q>),
                        grid, block, 0, s, b);
     return true;
   } else {
@@ -97,15 +97,16 @@ hipError_t launch_plan(int mode, const StftArgs &a, hipStream_t s) {
   constexpr bool DF = Tune<P>::DEFER, PF = Tune<P>::PREFETCH, DR = Tune<P>::DIRECT;
   // Row-side pitch pick (stft_kernel_impl.h: ROWPICK): the deferred plan's bulk calls that want rows and records with the
   // whole band below bin 4 * 64, which the first f32x4 of wave 0's lanes holds in the row flush.  Pitch-only calls, higher
-  // bands, ranges mode and the texel path keep the transform-side pick; the records are the same bits either way.
+  // bands, ranges mode and the texel path keep the transform-side pick; the records are the same bits either way.  The same
+  // calls take the q-major T1 image (T1Q); every other instantiation keeps the XOR image.
   if constexpr (DF) {
     if (mode != kRanges && !a.rgb && a.mags && a.pitch && 0 <= a.kmin && a.kmin <= a.kmax && a.kmax < 4 * 64) {
       if (mode == kBulkAny)
-        hipLaunchKernelGGL((stft_kernel<P, kBulkAny, 0, W, DF, PF, false, DR, false, true>), grid, block, 0, s, b);
+        hipLaunchKernelGGL((stft_kernel<P, kBulkAny, 0, W, DF, PF, false, DR, false, true, true>), grid, block, 0, s, b);
       else if (mode != kBulkAligned)
         return hipErrorInvalidValue;
-      else if (!(try_slide<P, 256, true>(b, grid, block, s) || try_slide<P, 512, true>(b, grid, block, s)))
-        hipLaunchKernelGGL((stft_kernel<P, kBulkAligned, 0, W, DF, PF, false, DR, false, true>), grid, block, 0, s, b);
+      else if (!(try_slide<P, 256, true, true>(b, grid, block, s) || try_slide<P, 512, true, true>(b, grid, block, s)))
+        hipLaunchKernelGGL((stft_kernel<P, kBulkAligned, 0, W, DF, PF, false, DR, false, true, true>), grid, block, 0, s, b);
       return hipGetLastError();
     }
   }
