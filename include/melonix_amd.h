@@ -108,10 +108,13 @@ const char *mx_version(void);
 
 /* ---- audio ---------------------------------------------------------------
  * Replaces Spec::Spec(std::span<float> wav) borrowing App::wavData
- * (spec.cpp:10-16, app.cpp:251): the samples are copied to HBM once. */
+ * (spec.cpp:10-16, app.cpp:251): the samples are copied to HBM once.
+ * MX_ERR_INVALID for n > 0x7fffffff - 2 * MX_AUDIO_PAD (2 147 418 111): the padded image's last element is then the last
+ * int32 index, and every kernel indexes the image in int32. */
 int mx_audio_upload(mx_ctx *ctx, const float *host_wav, int64_t n, mx_audio **out);
 /* Zero-copy: wrap a device buffer already laid out [PAD zeros][n][PAD zeros]
- * (d_padded points at the first pad sample, 16-byte aligned).  The caller keeps ownership. */
+ * (d_padded points at the first pad sample, 16-byte aligned).  The caller keeps ownership.
+ * MX_ERR_INVALID, with *out untouched, for n > 0x7fffffff - 2 * MX_AUDIO_PAD: mx_audio_upload's bound and message. */
 int mx_audio_wrap_device(mx_ctx *ctx, const float *d_padded, int64_t n, mx_audio **out);
 int64_t mx_audio_length(const mx_audio *a);
 int mx_audio_free(mx_ctx *ctx, mx_audio *a);
@@ -1475,7 +1478,9 @@ int mx_resample_dev(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int
 /* Same, host output staged through device memory of the call's own.  Blocks. */
 int mx_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, float *out);
 /* The converted take as a new audio object of m samples (zeroed pads, as mx_audio_gain_dev; release it with mx_audio_free).
- * Asynchronous on the context's stream.  MX_ERR_INVALID, with *out untouched, for a refused rate pair or NULLs. */
+ * Asynchronous on the context's stream.  MX_ERR_INVALID, with *out untouched, for a refused rate pair or NULLs, and, before
+ * anything is allocated, for m > 0x7fffffff - 2 * MX_AUDIO_PAD (mx_audio_upload's bound: no kernel could walk the object; a
+ * maximal 44.1 kHz take to 48 kHz asks for 2 337 325 836).  The range forms above keep serving outputs above 2^31. */
 int mx_audio_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, mx_audio **out);
 
 /* ---- WAV writer -------------------------------------------------------------

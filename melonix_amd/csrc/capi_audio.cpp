@@ -17,6 +17,8 @@ namespace {
 // the call in a device error.
 template <class F>
 int derived_audio(mx_ctx *ctx, int64_t length, const char *what, F &&fill, mx_audio **out) {
+  if (length > 0x7fffffffLL - 2 * MX_AUDIO_PAD)  // (mx_audio_upload's bound, before anything is allocated)
+    return fail(MX_ERR_INVALID, "%s: audio longer than the reference's int sample indices allow", what);
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mx_audio> b(new mx_audio());
   const size_t n = (size_t)length, pad = (size_t)MX_AUDIO_PAD;
