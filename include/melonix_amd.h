@@ -1483,6 +1483,78 @@ int mx_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t
  * maximal 44.1 kHz take to 48 kHz asks for 2 337 325 836).  The range forms above keep serving outputs above 2^31. */
 int mx_audio_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, mx_audio **out);
 
+/* ---- Noise reduction (BUILD-DEFINED; restated in f64 by tests/denoise_ref.py) ----
+ * Spectral noise reduction of a take from a noise print: the step before every analyser and renderer.  The reference has none
+ * of it (app.cpp decodes to mono and edits what it got).  One transform size, one wavefront per frame on the onset detector's
+ * transform, a gain rule without discontinuities.
+ *
+ * Framing: N = 1024, hop H = 256, any sample rate.  w[j] = 0.5 - 0.5 cos(2 pi j / 1024) (periodic Hann).  Frame f starts at
+ * sample (f - 3) H, f = 0 .. F - 1, F = ceil(n / H) + 3 (mx_denoise_frames): every sample of [0, n) lies in exactly four
+ * frames.  Samples outside [0, n) are zeros whatever the pads hold.  X_f[k], k = 0 .. 512, is the real transform of w x.
+ *
+ * Noise print: P[k], 513 binary32 values.  Learned from samples [begin, end) of a take (0 <= begin <= end <= n): over the frames
+ * that lie wholly inside, begin <= (f - 3) H and (f - 3) H + N <= end — at least 1 and at most 8192 of them, anything else is
+ * refused before any launch —, P[k] = the binary64 sum, in ascending frame order, of the binary32 powers
+ * a_f[k] = (|X_f[k]| / 512)^2 (the sibilant features' scale), divided by the frame count in binary64 and rounded to binary32.
+ * A print may equally be the caller's own (a saved one, a synthetic one); a negative or non-finite value is refused.
+ *
+ * Parameters: reduction_db in [0, 60], sensitivity_db in [-12, 24], NaN refused.  The host turns them into two binary32
+ * factors, once, in binary64: floor = 10^(-reduction_db / 20), sens = 10^(sensitivity_db / 10); mx_denoise_factors hands them
+ * out: the device, the emulation and numpy all read those two floats.
+ *
+ * Raw gain per frame and bin, binary32, written as comparisons:  theta = sens P[k];  g = a > theta ? 1 - theta / a : 0;
+ * g = g < floor ? floor : g.  Continuous in a; a NaN power gives `floor`; no square root, no threshold at which a bin flips.
+ * Smoothed gain: first over time, ((g_{f-1} + (g_f + g_f)) + g_{f+1}) * 0.25 with f - 1, f + 1 clamped to [0, F - 1]; then over
+ * frequency, the same expression of the time-smoothed values at k - 1, k, k + 1 with k - 1, k + 1 clamped to [0, 512].
+ *
+ * Output: y_f = the inverse real transform of G_f X_f, times w, times the binary32 constant 2/3 (the squared windows of the four
+ * frames sum to exactly 3/2).  out[t] = the sum of its four frames in ascending f from +0.f, each product rounded, then added,
+ * without contraction.  int16: the clamped conversion of "PCM conversions".
+ *
+ * Consequences (tests/denoise_ref.py check_laws pins them on the emulation and on the device):
+ *   split         any split of the output range gives the same bytes, and so does any run length;
+ *   scale         x 2^k with P 4^k gives out 2^k bit for bit where nothing leaves the normal range (k = -7, -20);
+ *   zero print    P = 0 gives out = x within 2e-5 max|x| + 1e-9: the transform pair's own error;
+ *   full          a print of 1e6 times the take's largest power gives out = floor x within the same bound;
+ *   silence       silence, of -0.0f samples too, gives zeros;
+ *   locality      a NaN at sample s makes exactly the outputs of [(floor(s / H) - 3) H, (floor(s / H) + 4) H) in [0, n) NaN:
+ *                 its four frames' gains are `floor` and their spectra NaN; the frames either side see those gains through the
+ *                 time smoothing, so no output outside [(floor(s / H) - 4) H, (floor(s / H) + 5) H) changes a bit, and where
+ *                 every gain is `floor` anyway (the full-reduction print) none outside the NaN stretch does. */
+typedef struct mx_denoise_params {
+  float reduction_db;   /* the most a bin is turned down, dB: [0, 60] */
+  float sensitivity_db; /* how far above the print a bin counts as noise, dB of power: [-12, 24] */
+} mx_denoise_params;
+#define MX_DENOISE_BINS 513
+/* F for a take of n samples; negative (MX_ERR_INVALID) for n < 0. */
+int64_t mx_denoise_frames(int64_t n);
+/* out[0] = floor, out[1] = sens.  MX_ERR_INVALID (out untouched) for parameters out of range, NaN or NULLs. */
+int mx_denoise_factors(const mx_denoise_params *params, float *out);
+/* The power rows of frames [first_frame, first_frame + count) -> d_rows[513 f + k] (HBM, 4-byte aligned).  Asynchronous on the
+ * context's stream.  MX_ERR_INVALID, before any launch, for frames outside [0, F) or NULLs (d_rows may be NULL where count is 0). */
+int mx_noise_rows_dev(mx_ctx *ctx, const mx_audio *a, int64_t first_frame, int64_t count, float *d_rows);
+/* The print of `count` rows on the host (the definition's sum, what the device's second kernel computes): count in [1, 8192]. */
+int mx_noise_print_rows(const float *rows, int64_t count, float *print);
+/* The print of samples [begin, end) -> d_print[0 .. 513) (HBM, 4-byte aligned): the rows pass through work memory of the
+ * context.  Asynchronous on the context's stream.  MX_ERR_INVALID, before any launch and with nothing written, for a region
+ * outside the take, with no frame or with more than 8192, or NULLs. */
+int mx_noise_print_dev(mx_ctx *ctx, const mx_audio *a, int64_t begin, int64_t end, float *d_print);
+/* Same, host output.  Blocks. */
+int mx_noise_print(mx_ctx *ctx, const mx_audio *a, int64_t begin, int64_t end, float *print);
+/* Outputs [first, first + count) of the cleaned take -> d_f32[0 .. count) and / or d_i16[0 .. count) (HBM, at any 4-byte / 2-byte
+ * aligned address; each may be NULL, not both where count > 0).  print: 513 values in HOST memory, checked and copied before the
+ * call returns.  Asynchronous on the context's stream.  An empty range is legal.  MX_ERR_INVALID, before any launch and with
+ * nothing written, for refused parameters, a refused print, a range outside [0, n), NULLs or a misaligned output. */
+int mx_denoise_dev(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, int64_t first,
+                   int64_t count, float *d_f32, int16_t *d_i16);
+/* Same, host outputs staged through device memory of the call's own.  Blocks. */
+int mx_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, int64_t first, int64_t count,
+               float *f32_out, int16_t *i16_out);
+/* The cleaned take as a new audio object of n samples (zeroed pads, as mx_audio_gain_dev; release it with mx_audio_free): the
+ * source of every analyser and renderer without a round trip.  Asynchronous on the context's stream.  MX_ERR_INVALID, with *out
+ * untouched, for refused parameters, a refused print or NULLs. */
+int mx_audio_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, mx_audio **out);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

@@ -40,7 +40,8 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "LOUD_STEP_DTYPE", "LOUD_GROUP_STEPS", "level_params_default", "loudness_step_count", "loudness_coeffs", "loudness_curve",
            "loudness_integrated", "note_loudness", "level_gain_points", "normalize_gain",
            "TP_STEP_DTYPE", "true_peak_oversampling", "true_peak_taps", "limit_params_default", "loudness_range", "normalize_gain_tp",
-           "resample_plan", "resample_length", "resample_taps"]
+           "resample_plan", "resample_length", "resample_taps",
+           "DENOISE_BINS", "denoise_frames", "denoise_factors", "noise_print_rows"]
 
 
 # The two pointer forms of an optional argument.  New wrappers use these: _opt for a host array, _dev for a device address.
@@ -60,7 +61,7 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
-_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget", "mx_resample_length")  # they return a count, or a negative status
+_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget", "mx_resample_length", "mx_denoise_frames")  # they return a count, or a negative status
 
 
 def _call(name: str, *args):
@@ -660,6 +661,45 @@ class Context:
         out = np.empty(max(count, 0), dtype=np.float32)
         _call("mx_resample", self.handle, audio.handle, in_rate, out_rate, first_out, count, _ptr(out))
         return out
+
+    # ---- noise reduction from a noise print (build-defined; include/melonix_amd.h) ----
+    def noise_rows_dev(self, audio: Audio, first_frame: int, count: int, d_rows: int):
+        """The power rows of frames [first_frame, first_frame + count) stay in HBM at d_rows (513 floats a frame); asynchronous
+        on the context's stream."""
+        _call("mx_noise_rows_dev", self.handle, audio.handle, first_frame, count, _dev(d_rows))
+
+    def noise_print(self, audio: Audio, begin: int, end: int):
+        """-> the noise print (513 float32) learned from samples [begin, end) of `audio`.  Blocks."""
+        out = np.empty(DENOISE_BINS, dtype=np.float32)
+        _call("mx_noise_print", self.handle, audio.handle, begin, end, _ptr(out))
+        return out
+
+    def noise_print_dev(self, audio: Audio, begin: int, end: int, d_print: int):
+        """The same print stays in HBM at d_print; asynchronous on the context's stream."""
+        _call("mx_noise_print_dev", self.handle, audio.handle, begin, end, _dev(d_print))
+
+    def denoise(self, audio: Audio, noise_print, reduction_db: float = 12.0, sensitivity_db: float = 6.0) -> Audio:
+        """A new Audio: `audio` cleaned with `noise_print` (513 float32, host).  Asynchronous on the context's stream."""
+        pr = _noise_print_arg(noise_print)
+        return self._audio(audio.n, "mx_audio_denoise", audio.handle, _ptr(pr), _denoise_params(reduction_db, sensitivity_db))
+
+    def denoise_dev(self, audio: Audio, noise_print, reduction_db: float, sensitivity_db: float, first: int, count: int,
+                    d_f32: int | None = None, d_i16: int | None = None):
+        """Outputs [first, first + count) of the cleaned take stay in HBM: float32 at d_f32 and / or int16 at d_i16 (None: not
+        wanted); asynchronous on the context's stream."""
+        pr = _noise_print_arg(noise_print)
+        _call("mx_denoise_dev", self.handle, audio.handle, _ptr(pr), _denoise_params(reduction_db, sensitivity_db), first, count,
+              _dev(d_f32), _dev(d_i16))
+
+    def denoise_range(self, audio: Audio, noise_print, reduction_db: float = 12.0, sensitivity_db: float = 6.0, first: int = 0,
+                      count: int | None = None, want_f32: bool = True, want_i16: bool = False):
+        """-> (float32 | None, int16 | None) outputs [first, first + count) of the cleaned take (count None: to its end).  Blocks."""
+        count = audio.n - first if count is None else count
+        pr = _noise_print_arg(noise_print)
+        f, i = _pcm_pair(max(count, 0), want_f32, want_i16)
+        _call("mx_denoise", self.handle, audio.handle, _ptr(pr), _denoise_params(reduction_db, sensitivity_db), first, count,
+              _ptr(f), _ptr(i))
+        return f, i
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
     def tempo_smooth(self, flux, width: int = 4):
@@ -1281,6 +1321,40 @@ def normalize_gain_tp(measured: dict, true_peak: float, target_lufs: float = -23
 
 
 # ---- sample-rate conversion: the plan, the length and the tap table of a rate pair (host; build-defined) ----
+DENOISE_BINS = _capi.DENOISE_BINS
+
+
+def _noise_print_arg(noise_print):
+    pr = np.ascontiguousarray(noise_print, dtype=np.float32)
+    if pr.shape != (DENOISE_BINS,):
+        raise ValueError(f"a noise print has {DENOISE_BINS} values")
+    return pr
+
+
+def _denoise_params(reduction_db: float, sensitivity_db: float):
+    return C.byref(_capi.DenoiseParams(float(reduction_db), float(sensitivity_db)))
+
+
+def denoise_frames(n: int) -> int:
+    """F = ceil(n / 256) + 3: the frames of the noise reduction over a take of n samples."""
+    return _call("mx_denoise_frames", int(n))
+
+
+def denoise_factors(reduction_db: float, sensitivity_db: float):
+    """-> (floor, sens) as float32: the two factors the device, the emulation and numpy read."""
+    out = np.empty(2, dtype=np.float32)
+    _call("mx_denoise_factors", _denoise_params(reduction_db, sensitivity_db), _ptr(out))
+    return out[0], out[1]
+
+
+def noise_print_rows(rows):
+    """The print of power rows (count x 513 float32) by the library's host form."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, DENOISE_BINS)
+    out = np.empty(DENOISE_BINS, dtype=np.float32)
+    _call("mx_noise_print_rows", _ptr(rows), len(rows), _ptr(out))
+    return out
+
+
 def resample_plan(in_rate: int, out_rate: int) -> dict:
     """The plan of in_rate -> out_rate -> {L, M, taps, half}; equal rates: {1, 1, 0, 0}.  MxError for a refused pair."""
     p = _capi.ResamplePlan()

@@ -216,6 +216,10 @@ class ResamplePlan(C.Structure):
     _fields_ = [("L", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("half", C.c_int32)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("reduction_db", C.c_float), ("sensitivity_db", C.c_float)]
+
+
 # the C type of every record class, in the order of include/melonix_amd.h.  A record is declared here once, as its class: the
 # field names are the header's, the numpy dtypes below are derived from the classes, and tests/test_abi.py compares every
 # class's size, field offsets and field sizes with what a C compiler makes of the header.  (mx_chroma_rec has no class: a
@@ -233,6 +237,7 @@ RECORDS = {
     "mx_contour_stat": ContourStat, "mx_vibrato": Vibrato, "mx_bend_params": BendParams, "mx_loud_step": LoudStep,
     "mx_loudness": Loudness, "mx_level_params": LevelParams, "mx_tp_step": TpStep, "mx_limit_params": LimitParams,
     "mx_loudness_range_result": LoudnessRange, "mx_resample_plan": ResamplePlan,
+    "mx_denoise_params": DenoiseParams,
 }
 
 PITCH_DTYPE, STEP_DTYPE, MARKER_DTYPE = np.dtype(Pitch), np.dtype(Step), np.dtype(Marker)
@@ -249,6 +254,7 @@ CONTOUR_SPAN_DTYPE, CONTOUR_REC_DTYPE, CONTOUR_STAT_DTYPE = np.dtype(ContourSpan
 LOUD_STEP_DTYPE = np.dtype(LoudStep)
 LOUD_GROUP_STEPS = 10  # G: steps per group, the unit mx_loudness_steps is asked in
 TP_STEP_DTYPE = np.dtype(TpStep)
+DENOISE_BINS = 513  # MX_DENOISE_BINS: the values of a noise print, the floats of a power row
 
 # name -> (restype, argtypes); kept in the order of include/melonix_amd.h
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -436,6 +442,15 @@ SIGNATURES = {
     "mx_resample_dev": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp]),
     "mx_resample": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp]),
     "mx_audio_resample": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "mx_denoise_frames": (_i64, [_i64]),
+    "mx_denoise_factors": (_i, [C.POINTER(DenoiseParams), _vp]),
+    "mx_noise_rows_dev": (_i, [_vp, _vp, _i64, _i64, _vp]),
+    "mx_noise_print_rows": (_i, [_vp, _i64, _vp]),
+    "mx_noise_print_dev": (_i, [_vp, _vp, _i64, _i64, _vp]),
+    "mx_noise_print": (_i, [_vp, _vp, _i64, _i64, _vp]),
+    "mx_denoise_dev": (_i, [_vp, _vp, _vp, C.POINTER(DenoiseParams), _i64, _i64, _vp, _vp]),
+    "mx_denoise": (_i, [_vp, _vp, _vp, C.POINTER(DenoiseParams), _i64, _i64, _vp, _vp]),
+    "mx_audio_denoise": (_i, [_vp, _vp, _vp, C.POINTER(DenoiseParams), C.POINTER(_vp)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

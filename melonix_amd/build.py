@@ -65,6 +65,9 @@ UNITS = [
     # build-defined sample-rate conversion: binary32 taps with every product rounded before its sum, in ascending tap order
     # (resample_core.h), bit for bit numpy's
     ("resample_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined noise reduction: the onset transform forwards and, around conjugation, backwards (denoise_core.h), every
+    # rounding as written, one correctly rounded division per bin
+    ("denoise_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -84,6 +87,7 @@ UNITS = [
     ("capi_truepeak.cpp", "hip", []),
     ("capi_audio.cpp", "hip", []),
     ("capi_resample.cpp", "hip", []),
+    ("capi_denoise.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
@@ -95,6 +99,7 @@ UNITS = [
     ("contour_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("loudness_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("resample_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("denoise_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

@@ -66,14 +66,24 @@ bool fileTrack(std::span<const float> wav, int hop, int device, std::vector<T> &
 // rate the library refuses: no frames)
 inline int stepSamples(int sampleRate) { return mx_loudness_step_count(1, sampleRate) == 1 ? (sampleRate + 50) / 100 : 0; }
 
-// `wav` through mx_audio_gain with `points`, on a session of its own; empty where a call fails
-inline std::vector<float> gained(std::span<const float> wav, int device, const std::vector<mx_gain_point> &points) {
-  std::vector<float> out(wav.size());
-  Session s(device, wav);
-  const bool done = s.ok && mx_audio_gain(s.ctx, s.audio, points.data(), (int64_t)points.size(), &s.made[0]) == MX_OK &&
-                    mx_audio_download(s.ctx, s.made[0], 0, (int64_t)out.size(), out.data()) == MX_OK;
+// The samples of an audio object made of the session's take: `make(ctx, audio, &object) -> status` (mx_audio_gain,
+// mx_audio_denoise, ...) fills slot `slot` of `made`, which must be free; the object's n samples come back, empty where a call
+// fails.  The object stays with the session.
+template <class Make>
+std::vector<float> derivedSamples(Session &s, int slot, int64_t n, Make make) {
+  std::vector<float> out((size_t)n);
+  const bool done = s.ok && !s.made[slot] && make(s.ctx, s.audio, &s.made[slot]) == MX_OK &&
+                    mx_audio_download(s.ctx, s.made[slot], 0, n, out.data()) == MX_OK;
   if (!done) out.clear();
   return out;
+}
+
+// `wav` through mx_audio_gain with `points`, on a session of its own; empty where a call fails
+inline std::vector<float> gained(std::span<const float> wav, int device, const std::vector<mx_gain_point> &points) {
+  Session s(device, wav);
+  return derivedSamples(s, 0, (int64_t)wav.size(), [&](mx_ctx *ctx, mx_audio *a, mx_audio **out) {
+    return mx_audio_gain(ctx, a, points.data(), (int64_t)points.size(), out);
+  });
 }
 
 }  // namespace melonix::glue

@@ -1,5 +1,6 @@
 // capi_audio.cpp — the audio objects made from another one on the device: the source gain (gain_kernels.hip), the look-ahead
-// limiter (truepeak_kernels.hip) and the sample-rate conversion (resample_kernels.hip; its range forms: capi_resample.cpp), and
+// limiter (truepeak_kernels.hip), the sample-rate conversion (resample_kernels.hip; its range forms: capi_resample.cpp) and the
+// noise reduction (denoise_kernels.hip; its range forms and prints: capi_denoise.cpp), and
 // the download of an audio object's samples: BUILD-DEFINED, the reference has none of it.  One
 // unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).  (mx_audio_upload, _wrap_device, _free:
 // capi_ctx.cpp.)
@@ -176,6 +177,23 @@ int mx_audio_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, m
     if (const int rc = resample_table_dev(ctx, p, &d_table)) return rc;
     const int64_t m = rs::out_length(a->n, p);
     return derived_audio(ctx, m, "audio resample", [=](float *dst) { return resample_enqueue(ctx, a, p, d_table, 0, m, dst); }, out);
+  });
+}
+
+int mx_audio_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, mx_audio **out) {
+  return mx_guard([&]() -> int {
+    if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+    float floor = 0.f, sens = 0.f;
+    if (const int rc = denoise_check(print, params, &floor, &sens)) return rc;
+    int status = MX_OK;  // (denoise_enqueue records its own message; derived_audio words the device error it is told of)
+    mx_audio *made = nullptr;
+    const int rc = derived_audio(ctx, a->n, "audio denoise", [&](float *dst) {
+      status = denoise_enqueue(ctx, a, print, floor, sens, 0, a->n, dst, nullptr);
+      return status == MX_OK ? hipSuccess : hipErrorUnknown;
+    }, &made);
+    if (rc) return status ? status : rc;
+    *out = made;
+    return MX_OK;
   });
 }
 

@@ -293,6 +293,34 @@ struct ResampleArgs {
   float *out;
 };
 hipError_t launch_resample(const ResampleArgs &a, hipStream_t s);
+// Build-defined noise reduction (denoise_kernels.hip; definition: include/melonix_amd.h, arithmetic: denoise_core.h on
+// onset_core.h's transform).  Outputs [first, first + count) of the cleaned take, all inside [0, n): checked by the caller.
+// print: the 513 values, in HBM; sens, floor: mx_denoise_factors'.  f32 (4-byte aligned) and i16 (2-byte aligned), each or null:
+// no store outside [0 .. count) of either.
+struct DenoiseArgs {
+  const float *image;  // padded image (the samples outside the file are taken as zeros whatever the pads hold)
+  int64_t n;
+  const float2 *tw;  // the onset transform's table
+  const float *print;
+  float sens, floor;
+  int64_t first, count;
+  float *f32;
+  int16_t *i16;
+  int run;  // output blocks of 256 samples per wavefront; 0: the default.  The output does not depend on it
+};
+hipError_t launch_denoise(const DenoiseArgs &a, hipStream_t s);
+// The power rows of frames [first_frame, first_frame + count) of the same framing: rows[513 f + k] = (|X_k| / 512)^2; and the
+// print of `count` rows (1 .. 8192: checked by the caller): their binary64 sum in ascending frame order / count, to binary32.
+struct NoiseRowsArgs {
+  const float *image;
+  int64_t n;
+  const float2 *tw;
+  int64_t first_frame, count;
+  float *rows;
+  int run;  // consecutive frames per wavefront; 0: onset_default_run's
+};
+hipError_t launch_noise_rows(const NoiseRowsArgs &a, hipStream_t s);
+hipError_t launch_noise_print(const float *rows, int64_t count, float *print, hipStream_t s);
 // Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
 // count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
 // range (the caller's check) gives a wrong record and nothing worse.
