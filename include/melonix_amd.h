@@ -1555,6 +1555,107 @@ int mx_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_deno
  * untouched, for refused parameters, a refused print or NULLs. */
 int mx_audio_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, mx_audio **out);
 
+/* ---- Dynamics compressor (BUILD-DEFINED; restated in binary64 and Python integers by tests/compress_ref.py) ----
+ * A feed-forward peak compressor with a threshold, a ratio, a soft knee, attack and release times, a look-ahead and a make-up
+ * gain: the step between note levelling (one gain per note) and the limiter (nothing over the ceiling), and its gain-reduction
+ * curve, the meter an editor draws.  The reference has none of it (app.cpp exports what process() wrote).  Integers from one
+ * table look-up on: the device, the CPU emulation and numpy give the same bytes whatever the launch split.
+ *
+ * Geometry: sr in [8000, 384000].  A control step is D = (sr + 500) / 1000 samples (integer division: 48 at 48 kHz, 44 at
+ * 44.1 kHz), B = ceil(n / D) steps (mx_compress_steps); step b covers samples [b D, (b + 1) D) of [0, n).  Samples outside the
+ * file do not exist, whatever the pads hold.
+ *
+ * Parameters (mx_compress_params; NaN and anything out of range refused before any launch): threshold_db [-60, 0], ratio
+ * [1, 100], knee_db [0, 24], attack_ms [0, 500], release_ms [0, 2000], lookahead_ms [0, 20], makeup_amp a normal number in
+ * [1/16, 16] (an amplitude: the facade converts dB).  Defaults: -18 dB, 4, 6 dB, 5 ms, 100 ms, 0 ms, 1.
+ *
+ * Plan (mx_compress_plan_for; binary64 on the host, once): K = floor(lookahead_ms sr / (1000 D) + 0.5) steps;
+ * c = round((1 - exp(-D / (sr tau))) 2^24) clamped to [1, 2^24] for tau = attack, release in seconds, 2^24 for tau = 0; the group
+ * length Gc = 4096 steps; the warm-up W = min(32768, 16 ceil(2^24 / min(c_att, c_rel))) steps.
+ *
+ * Curve (mx_compress_curve): T[j], j = 0 .. 2048, the Q30 gain target of the level p whose binary32 bit pattern is
+ * ((127 - 24) << 23) + (j << 17): 64 entries an octave from 2^-24 to 2^8.  In binary64: L = 20 log10 p, o = L - threshold,
+ * s = 1 / ratio - 1; g_dB = 0 where 2 o <= -knee, s (o + knee / 2)^2 / (2 knee) where |2 o| < knee, s o otherwise;
+ * T[j] = min(2^30, floor(10^(g_dB / 20) 2^30)), then a running minimum over j: non-increasing, and at least 1 inside the ranges.
+ *
+ * Peak: p_b = the largest |x_i| of step b that is not a NaN (+-Inf counts); 0 for a step without one and for b outside [0, B).
+ * Target: p clamped to [2^-24, 2^8], u = bits(p) - ((127 - 24) << 23), j = u >> 17, r = u & 0x1ffff:
+ * q_b = T[j] + (((int64)(T[j + 1] - T[j]) r) >> 17) (arithmetic shift), T[2048] at the top.  (T[0] = 2^30: a step outside the
+ * file asks for unity.)
+ * Smoothed gain, int64: q_b < s ? s -= ((s - q_b) c_att + 2^24 - 1) >> 24 : s += ((q_b - s) c_rel + 2^24 - 1) >> 24: rounded
+ * towards the target, so it arrives.  Group g owns steps [g Gc, (g + 1) Gc): it starts from s = 2^30 at step g Gc - W and its s_b
+ * count from g Gc on; s_b = 2^30 for b < 0; for b >= B the recurrence goes on with q = 2^30 as far as K asks.  The truncated
+ * warm-up is part of the definition: s_b depends on the peaks of [floor(b / Gc) Gc - W, b] alone.
+ * Output, sample i of step b at offset o = i - b D: G_i = s_{b+K-1} (D - o) + s_{b+K} o (int64);
+ * out_i = (float)(((double)x_i (double)makeup_amp) (double)G_i / (double)(D 2^30)) in binary64 without contraction; where
+ * G_i = D 2^30 and makeup_amp = 1 the quotient is left out: out_i = x_i, the same value.  int16: the clamped conversion of "PCM
+ * conversions".
+ *
+ * Laws (tests/compress_ref.py check_laws pins them on the emulation and on the device):
+ *   split        any [first, count) and any launch geometry give the whole call's bytes;
+ *   ratio 1      ratio 1 with makeup 1 gives the input's bytes;
+ *   below        a take whose every |x| lies a table interval below the knee's lower edge — at most edge / (1 + 1/64): the entry
+ *                above the edge pulls the interpolation under it below unity — gives the input's bytes (makeup 1); silence, of
+ *                -0.0f too, gives its own bytes;
+ *   steady       a constant |x| = a gives s = q(a) exactly after finitely many steps (at a seam, where the attack is no slower than
+ *                the release), then out = the quotient with G = D q(a): a m q(a) / 2^30 to the last binary32 place;
+ *   recovery     after the last step over that level s returns to exactly 2^30; from there out = x (makeup 1);
+ *   monotone     raising any |x_i| raises no s_b;
+ *   NaN          a NaN in place of a sample that is not its step's largest changes out_t alone (the peak passes over it);
+ *   Inf          an +-Inf at sample t changes no output before sample (floor(t / D) - K - 1) D, and none from sample
+ *                ((floor((floor(t / D) + W) / Gc) + 1) Gc - K + 1) D on: the steps after it in its own group, and the groups
+ *                whose warm-up still reads it, are all that see its step. */
+typedef struct mx_compress_params {
+  float threshold_db; /* [-60, 0] */
+  float ratio;        /* [1, 100] */
+  float knee_db;      /* full width of the soft knee, dB: [0, 24] */
+  float attack_ms;    /* [0, 500] */
+  float release_ms;   /* [0, 2000] */
+  float lookahead_ms; /* [0, 20] */
+  float makeup_amp;   /* a normal number in [1/16, 16] */
+} mx_compress_params;
+typedef struct mx_compress_plan {
+  int32_t D;     /* samples per control step */
+  int32_t K;     /* look-ahead, steps */
+  int32_t c_att; /* Q24 */
+  int32_t c_rel; /* Q24 */
+  int32_t W;     /* warm-up, steps */
+  int32_t Gc;    /* steps per group */
+} mx_compress_plan;
+#define MX_COMPRESS_CURVE 2049
+/* The defaults at sampleRate.  MX_ERR_INVALID for a rate out of range or a NULL. */
+int mx_compress_params_default(int sampleRate, mx_compress_params *p);
+/* The plan of `params` (NULL: the defaults) at sampleRate.  MX_ERR_INVALID (plan untouched) for refused parameters or rate, NULL. */
+int mx_compress_plan_for(int sampleRate, const mx_compress_params *params, mx_compress_plan *plan);
+/* T[0 .. 2049) of `params` (NULL: the defaults; the curve does not depend on the rate).  MX_ERR_INVALID (out untouched) likewise. */
+int mx_compress_curve(const mx_compress_params *params, int32_t *out);
+/* B for a take of n samples; negative (MX_ERR_INVALID) for n < 0 or a rate out of range. */
+int64_t mx_compress_steps(int64_t n, int sampleRate);
+/* p_b of steps [first_step, first_step + nsteps) of [0, B) -> d_peaks[0 .. nsteps) (HBM, 4-byte aligned).  Asynchronous on the
+ * context's stream.  MX_ERR_INVALID, before any launch, for steps outside [0, B), a refused rate, NULLs or a misaligned output. */
+int mx_compress_peaks_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_step, int64_t nsteps, float *d_peaks);
+/* s_b of steps [first_step, first_step + nsteps) of [0, B), Q30 -> d_gain[0 .. nsteps) (HBM, 4-byte aligned): the meter
+ * (20 log10(s / 2^30) dB).  The peaks pass through work memory of the context.  Asynchronous on the context's stream. */
+int mx_compress_gain_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first_step,
+                         int64_t nsteps, int32_t *d_gain);
+/* Same, host output.  Blocks. */
+int mx_compress_gain(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first_step,
+                     int64_t nsteps, int32_t *gain);
+/* Outputs [first, first + count) of the compressed take -> d_f32[0 .. count) and / or d_i16[0 .. count) (HBM, at any 4-byte /
+ * 2-byte aligned address; each may be NULL, not both where count > 0).  Only the groups the range and its look-ahead touch are
+ * computed, in work memory of the context.  Asynchronous on the context's stream.  An empty range is legal.  MX_ERR_INVALID,
+ * before any launch and with nothing written, for refused parameters or rate, a range outside [0, n), NULLs or a misaligned
+ * output. */
+int mx_compress_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first, int64_t count,
+                    float *d_f32, int16_t *d_i16);
+/* Same, host outputs staged through device memory of the call's own.  Blocks. */
+int mx_compress(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first, int64_t count,
+                float *f32_out, int16_t *i16_out);
+/* The compressed take as a new audio object of n samples (zeroed pads, as mx_audio_gain_dev; release it with mx_audio_free): the
+ * source of the loudness measure, the gain, the converter and the limiter without a round trip.  Asynchronous on the context's
+ * stream.  MX_ERR_INVALID, with *out untouched, for refused parameters or rate or NULLs. */
+int mx_audio_compress(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, mx_audio **out);
+
 /* ---- WAV writer -------------------------------------------------------------
  * Replaces saveWav (save-wav.cpp:17-48).  strict_reference_header != 0
  * reproduces the size-field quirk of save-wav.cpp:43 byte for byte (data size

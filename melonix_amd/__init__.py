@@ -41,7 +41,8 @@ __all__ = ["Context", "Audio", "MxError", "pitch_band", "frame_count", "grains_h
            "loudness_integrated", "note_loudness", "level_gain_points", "normalize_gain",
            "TP_STEP_DTYPE", "true_peak_oversampling", "true_peak_taps", "limit_params_default", "loudness_range", "normalize_gain_tp",
            "resample_plan", "resample_length", "resample_taps",
-           "DENOISE_BINS", "denoise_frames", "denoise_factors", "noise_print_rows"]
+           "DENOISE_BINS", "denoise_frames", "denoise_factors", "noise_print_rows",
+           "COMPRESS_CURVE", "compress_params_default", "compress_plan", "compress_curve", "compress_steps"]
 
 
 # The two pointer forms of an optional argument.  New wrappers use these: _opt for a host array, _dev for a device address.
@@ -61,7 +62,8 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
-_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget", "mx_resample_length", "mx_denoise_frames")  # they return a count, or a negative status
+_COUNT_CALLS = ("mx_pv_render_length", "mx_pv_arena_budget", "mx_resample_length", "mx_denoise_frames",
+                "mx_compress_steps")  # they return a count, or a negative status
 
 
 def _call(name: str, *args):
@@ -700,6 +702,42 @@ class Context:
         _call("mx_denoise", self.handle, audio.handle, _ptr(pr), _denoise_params(reduction_db, sensitivity_db), first, count,
               _ptr(f), _ptr(i))
         return f, i
+
+    # ---- dynamics compressor and its gain-reduction curve (build-defined; include/melonix_amd.h).  params: fields of
+    # compress_params_default() ----
+    def compress(self, audio: Audio, sr: int, **params) -> Audio:
+        """A new Audio: `audio` through the compressor at sr.  Asynchronous on the context's stream."""
+        return self._audio(audio.n, "mx_audio_compress", audio.handle, int(sr), _compress_params(params))
+
+    def compress_dev(self, audio: Audio, sr: int, first: int, count: int, d_f32: int | None = None, d_i16: int | None = None, **params):
+        """Outputs [first, first + count) of the compressed take stay in HBM: float32 at d_f32 and / or int16 at d_i16 (None: not
+        wanted); asynchronous on the context's stream."""
+        _call("mx_compress_dev", self.handle, audio.handle, int(sr), _compress_params(params), first, count, _dev(d_f32), _dev(d_i16))
+
+    def compress_range(self, audio: Audio, sr: int, first: int = 0, count: int | None = None, want_f32: bool = True,
+                       want_i16: bool = False, **params):
+        """-> (float32 | None, int16 | None) outputs [first, first + count) of the compressed take (count None: to its end).  Blocks."""
+        count = audio.n - first if count is None else count
+        f, i = _pcm_pair(max(count, 0), want_f32, want_i16)
+        _call("mx_compress", self.handle, audio.handle, int(sr), _compress_params(params), first, count, _ptr(f), _ptr(i))
+        return f, i
+
+    def compress_gain(self, audio: Audio, sr: int, first_step: int = 0, nsteps: int | None = None, **params):
+        """-> the smoothed gain s_b of steps [first_step, first_step + nsteps) as int32 Q30 (nsteps None: to the last): the
+        gain-reduction meter, 20 log10(s / 2^30) dB.  Blocks."""
+        nsteps = compress_steps(audio.n, sr) - first_step if nsteps is None else nsteps
+        out = np.empty(max(nsteps, 0), dtype=np.int32)
+        _call("mx_compress_gain", self.handle, audio.handle, int(sr), _compress_params(params), first_step, nsteps, _ptr(out))
+        return out
+
+    def compress_gain_dev(self, audio: Audio, sr: int, first_step: int, nsteps: int, d_gain: int, **params):
+        """The same curve stays in HBM at d_gain (int32); asynchronous on the context's stream."""
+        _call("mx_compress_gain_dev", self.handle, audio.handle, int(sr), _compress_params(params), first_step, nsteps, _dev(d_gain))
+
+    def compress_peaks_dev(self, audio: Audio, sr: int, first_step: int, nsteps: int, d_peaks: int):
+        """The peaks p_b of steps [first_step, first_step + nsteps) stay in HBM at d_peaks (float32); asynchronous on the
+        context's stream."""
+        _call("mx_compress_peaks_dev", self.handle, audio.handle, int(sr), first_step, nsteps, _dev(d_peaks))
 
     # ---- tempo and grid offset from the onset-strength curve (build-defined; include/melonix_amd.h) ----
     def tempo_smooth(self, flux, width: int = 4):
@@ -1353,6 +1391,49 @@ def noise_print_rows(rows):
     out = np.empty(DENOISE_BINS, dtype=np.float32)
     _call("mx_noise_print_rows", _ptr(rows), len(rows), _ptr(out))
     return out
+
+
+# ---- dynamics compressor: the defaults, the plan, the curve and the step count (host; build-defined) ----
+COMPRESS_CURVE = _capi.COMPRESS_CURVE
+
+
+def compress_params_default(sr: int = 48000) -> dict:
+    """The compressor's defaults: -18 dB, 4 : 1, a 6 dB knee, 5 ms / 100 ms, no look-ahead, make-up 1."""
+    p = _capi.CompressParams()
+    _call("mx_compress_params_default", int(sr), C.byref(p))
+    return _fields(p)
+
+
+def _compress_struct(params: dict):
+    d = compress_params_default()
+    unknown = set(params) - set(d)
+    if unknown:
+        raise TypeError(f"unknown compress parameters {sorted(unknown)}")
+    d.update(params)
+    return _capi.CompressParams(*(float(d[k]) for k, _ in _capi.CompressParams._fields_))
+
+
+def _compress_params(params: dict):
+    return C.byref(_compress_struct(params))
+
+
+def compress_plan(sr: int, **params) -> dict:
+    """The plan of `params` at sr -> {D, K, c_att, c_rel, W, Gc}.  MxError for a refused rate or parameter."""
+    q = _capi.CompressPlan()
+    _call("mx_compress_plan_for", int(sr), _compress_params(params), C.byref(q))
+    return _fields(q)
+
+
+def compress_curve(**params):
+    """-> the 2049 Q30 gain targets (int32) of `params`: what the device, the emulation and numpy look up."""
+    out = np.empty(COMPRESS_CURVE, dtype=np.int32)
+    _call("mx_compress_curve", _compress_params(params), _ptr(out))
+    return out
+
+
+def compress_steps(n: int, sr: int) -> int:
+    """B = ceil(n / D), D = (sr + 500) // 1000: the control steps of the compressor over a take of n samples."""
+    return _call("mx_compress_steps", int(n), int(sr))
 
 
 def resample_plan(in_rate: int, out_rate: int) -> dict:

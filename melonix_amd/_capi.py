@@ -220,6 +220,15 @@ class DenoiseParams(C.Structure):
     _fields_ = [("reduction_db", C.c_float), ("sensitivity_db", C.c_float)]
 
 
+class CompressParams(C.Structure):
+    _fields_ = [("threshold_db", C.c_float), ("ratio", C.c_float), ("knee_db", C.c_float), ("attack_ms", C.c_float),
+                ("release_ms", C.c_float), ("lookahead_ms", C.c_float), ("makeup_amp", C.c_float)]
+
+
+class CompressPlan(C.Structure):
+    _fields_ = [("D", C.c_int32), ("K", C.c_int32), ("c_att", C.c_int32), ("c_rel", C.c_int32), ("W", C.c_int32), ("Gc", C.c_int32)]
+
+
 # the C type of every record class, in the order of include/melonix_amd.h.  A record is declared here once, as its class: the
 # field names are the header's, the numpy dtypes below are derived from the classes, and tests/test_abi.py compares every
 # class's size, field offsets and field sizes with what a C compiler makes of the header.  (mx_chroma_rec has no class: a
@@ -237,7 +246,7 @@ RECORDS = {
     "mx_contour_stat": ContourStat, "mx_vibrato": Vibrato, "mx_bend_params": BendParams, "mx_loud_step": LoudStep,
     "mx_loudness": Loudness, "mx_level_params": LevelParams, "mx_tp_step": TpStep, "mx_limit_params": LimitParams,
     "mx_loudness_range_result": LoudnessRange, "mx_resample_plan": ResamplePlan,
-    "mx_denoise_params": DenoiseParams,
+    "mx_denoise_params": DenoiseParams, "mx_compress_params": CompressParams, "mx_compress_plan": CompressPlan,
 }
 
 PITCH_DTYPE, STEP_DTYPE, MARKER_DTYPE = np.dtype(Pitch), np.dtype(Step), np.dtype(Marker)
@@ -255,6 +264,7 @@ LOUD_STEP_DTYPE = np.dtype(LoudStep)
 LOUD_GROUP_STEPS = 10  # G: steps per group, the unit mx_loudness_steps is asked in
 TP_STEP_DTYPE = np.dtype(TpStep)
 DENOISE_BINS = 513  # MX_DENOISE_BINS: the values of a noise print, the floats of a power row
+COMPRESS_CURVE = 2049  # MX_COMPRESS_CURVE: the Q30 targets of a compressor's curve
 
 # name -> (restype, argtypes); kept in the order of include/melonix_amd.h
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -451,6 +461,16 @@ SIGNATURES = {
     "mx_denoise_dev": (_i, [_vp, _vp, _vp, C.POINTER(DenoiseParams), _i64, _i64, _vp, _vp]),
     "mx_denoise": (_i, [_vp, _vp, _vp, C.POINTER(DenoiseParams), _i64, _i64, _vp, _vp]),
     "mx_audio_denoise": (_i, [_vp, _vp, _vp, C.POINTER(DenoiseParams), C.POINTER(_vp)]),
+    "mx_compress_params_default": (_i, [_i, C.POINTER(CompressParams)]),
+    "mx_compress_plan_for": (_i, [_i, C.POINTER(CompressParams), C.POINTER(CompressPlan)]),
+    "mx_compress_curve": (_i, [C.POINTER(CompressParams), _vp]),
+    "mx_compress_steps": (_i64, [_i64, _i]),
+    "mx_compress_peaks_dev": (_i, [_vp, _vp, _i, _i64, _i64, _vp]),
+    "mx_compress_gain_dev": (_i, [_vp, _vp, _i, C.POINTER(CompressParams), _i64, _i64, _vp]),
+    "mx_compress_gain": (_i, [_vp, _vp, _i, C.POINTER(CompressParams), _i64, _i64, _vp]),
+    "mx_compress_dev": (_i, [_vp, _vp, _i, C.POINTER(CompressParams), _i64, _i64, _vp, _vp]),
+    "mx_compress": (_i, [_vp, _vp, _i, C.POINTER(CompressParams), _i64, _i64, _vp, _vp]),
+    "mx_audio_compress": (_i, [_vp, _vp, _i, C.POINTER(CompressParams), C.POINTER(_vp)]),
     "mx_save_wav": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 

@@ -68,6 +68,9 @@ UNITS = [
     # build-defined noise reduction: the onset transform forwards and, around conjugation, backwards (denoise_core.h), every
     # rounding as written, one correctly rounded division per bin
     ("denoise_kernels.hip", "hip", ["-ffp-contract=off"]),
+    # build-defined dynamics compressor: integers from the table look-up to the gain, one binary64 product and quotient as
+    # written (compress_core.h), bit for bit numpy's
+    ("compress_kernels.hip", "hip", ["-ffp-contract=off"]),
     ("capi_ctx.cpp", "hip", []),
     ("capi_stft.cpp", "hip", []),
     ("capi_rows.cpp", "hip", []),
@@ -88,6 +91,7 @@ UNITS = [
     ("capi_audio.cpp", "hip", []),
     ("capi_resample.cpp", "hip", []),
     ("capi_denoise.cpp", "hip", []),
+    ("capi_compress.cpp", "hip", []),
     # pure host logic: plain g++, no contraction, no -march (SURVEY §7 "Bit-exact schedule")
     ("host_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("f0_notes.cpp", "cxx", ["-ffp-contract=off"]),
@@ -100,6 +104,7 @@ UNITS = [
     ("loudness_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("resample_logic.cpp", "cxx", ["-ffp-contract=off"]),
     ("denoise_logic.cpp", "cxx", ["-ffp-contract=off"]),
+    ("compress_logic.cpp", "cxx", ["-ffp-contract=off"]),
 ]
 IDENTITY_UNIT = "capi_ctx.cpp"
 PV_UNITS = [src for src, kind, _ in UNITS if kind == "hip" and src.startswith("pv_")]  # the phase vocoder's kernel units

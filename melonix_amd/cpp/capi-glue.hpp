@@ -29,10 +29,10 @@ std::vector<Out> taken(T *v, int64_t n) {
 
 // What a call of the facade holds for its own length: a context on `device`, the upload of a take (the second constructor, or
 // upload()), and the audio objects the call makes of it (`made`, filled by the caller).  `ok`: everything asked for so far is
-// there.  The destructor frees what is there: made[2], made[1], made[0], the upload, then the context.
+// there.  The destructor frees what is there: made[3] .. made[0], the upload, then the context.
 struct Session {
   mx_ctx *ctx = nullptr;
-  mx_audio *audio = nullptr, *made[3] = {};
+  mx_audio *audio = nullptr, *made[4] = {};
   bool ok;
   explicit Session(int device) : ok(mx_ctx_create(device, &ctx) == MX_OK) {}
   Session(int device, std::span<const float> wav) : Session(device) { upload(wav); }
@@ -42,7 +42,7 @@ struct Session {
     return ok = ok && mx_audio_upload(ctx, wav.data(), (int64_t)wav.size(), &audio) == MX_OK;
   }
   ~Session() {
-    for (mx_audio *a : {made[2], made[1], made[0], audio})
+    for (mx_audio *a : {made[3], made[2], made[1], made[0], audio})
       if (a) mx_audio_free(ctx, a);
     if (ctx) mx_ctx_destroy(ctx);
   }

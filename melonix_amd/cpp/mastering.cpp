@@ -38,30 +38,61 @@ std::vector<int16_t> Mastering::finish(double targetLufs, double ceilingDbtp, do
   return finishAt(sampleRate, targetLufs, ceilingDbtp, lookaheadMs);
 }
 
+// the limiter's parameters at the rate it delivers: the ceiling as an amplitude, any look-ahead brought into [1, 1024] samples
+static bool limitParams(int outRate, double ceilingDbtp, double lookaheadMs, mx_limit_params &p) {
+  if (mx_limit_params_default(outRate, &p) != MX_OK || !std::isfinite(ceilingDbtp) || !std::isfinite(lookaheadMs)) return false;
+  p.ceiling_amp = (float)std::pow(10.0, ceilingDbtp / 20.0);
+  if (lookaheadMs > 0.0) {
+    const double a = std::floor(lookaheadMs * (double)outRate / 1000.0 + 0.5);
+    p.lookahead = a < 1.0 ? 1 : a > 1024.0 ? 1024 : (int32_t)a;
+  }
+  return true;
+}
+
+// The end of the chain from `src`, an object of the session at the take's rate: the gain `amp` (made[slot]), the conversion where
+// outRate differs (made[slot + 1]), the limiter (made[slot + 2]) -> int16; empty after a failed call.
+std::vector<int16_t> Mastering::deliver(glue::Session &s, const mx_audio *src, int slot, float amp, int outRate, const mx_limit_params &p,
+                                        int64_t m) const {
+  std::vector<int16_t> out((size_t)m);
+  const mx_gain_point point{0, amp};
+  bool done = s.ok && mx_audio_gain(s.ctx, src, &point, 1, &s.made[slot]) == MX_OK;
+  const mx_audio *levelled = s.made[slot];
+  if (done && outRate != sampleRate) {  // conversion before the limiter: a true peak belongs to the delivered samples
+    done = mx_audio_resample(s.ctx, levelled, sampleRate, outRate, &s.made[slot + 1]) == MX_OK;
+    levelled = s.made[slot + 1];
+  }
+  done = done && mx_audio_limit(s.ctx, levelled, outRate, &p, &s.made[slot + 2], out.data()) == MX_OK;
+  if (!done) out.clear();
+  return out;
+}
+
 std::vector<int16_t> Mastering::finishAt(int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
   float amp = 1.f;
   // (a ceiling far above any take: the loudness term alone)
   if (!good || mx_normalize_gain_tp(&loudness_, truePeak_, targetLufs, 200.0, &amp) != MX_OK) return {};
   const int64_t m = mx_resample_length((int64_t)wav_.size(), sampleRate, outRate);
   mx_limit_params p;  // the limiter works at the rate it delivers
-  if (m < 0 || mx_limit_params_default(outRate, &p) != MX_OK || !std::isfinite(ceilingDbtp) || !std::isfinite(lookaheadMs)) return {};
-  p.ceiling_amp = (float)std::pow(10.0, ceilingDbtp / 20.0);
-  if (lookaheadMs > 0.0) {
-    const double a = std::floor(lookaheadMs * (double)outRate / 1000.0 + 0.5);
-    p.lookahead = a < 1.0 ? 1 : a > 1024.0 ? 1024 : (int32_t)a;
-  }
-  std::vector<int16_t> out((size_t)m);
+  if (m < 0 || !limitParams(outRate, ceilingDbtp, lookaheadMs, p)) return {};
   glue::Session s(device_, wav_);
-  const mx_gain_point point{0, amp};
-  bool done = s.ok && mx_audio_gain(s.ctx, s.audio, &point, 1, &s.made[0]) == MX_OK;
-  const mx_audio *levelled = s.made[0];
-  if (done && outRate != sampleRate) {  // conversion before the limiter: a true peak belongs to the delivered samples
-    done = mx_audio_resample(s.ctx, levelled, sampleRate, outRate, &s.made[1]) == MX_OK;
-    levelled = s.made[1];
-  }
-  done = done && mx_audio_limit(s.ctx, levelled, outRate, &p, &s.made[2], out.data()) == MX_OK;
-  if (!done) out.clear();
-  return out;
+  return deliver(s, s.audio, 0, amp, outRate, p, m);
+}
+
+std::vector<int16_t> Mastering::finishCompressedAt(int outRate, const CompressorSettings &compressor, double targetLufs,
+                                                   double ceilingDbtp, double lookaheadMs) const {
+  mx_compress_params cp;
+  const int64_t m = mx_resample_length((int64_t)wav_.size(), sampleRate, outRate);
+  mx_limit_params p;
+  if (!good || !compressParams(compressor, cp) || m < 0 || !limitParams(outRate, ceilingDbtp, lookaheadMs, p)) return {};
+  glue::Session s(device_, wav_);
+  mx_loudness loud{};
+  float truePeak = 0.f, amp = 1.f;
+  // the loudness the gain is taken from is the compressed take's: the compressor changed it
+  const bool levelled = s.ok && mx_audio_compress(s.ctx, s.audio, sampleRate, &cp, &s.made[0]) == MX_OK &&
+                        mx_loudness_measure(s.ctx, s.made[0], sampleRate, &loud) == MX_OK &&
+                        mx_true_peak_measure(s.ctx, s.made[0], sampleRate, &truePeak, nullptr) == MX_OK &&
+                        mx_normalize_gain_tp(&loud, truePeak, targetLufs, 200.0, &amp) == MX_OK;
+  if (!levelled) return {};
+  return deliver(s, s.made[0], 1, amp, outRate, p, m);
 }
 
 bool Mastering::exportWav(const std::string &path, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
@@ -70,6 +101,12 @@ bool Mastering::exportWav(const std::string &path, double targetLufs, double cei
 
 bool Mastering::exportWavAt(const std::string &path, int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs) const {
   const std::vector<int16_t> pcm = finishAt(outRate, targetLufs, ceilingDbtp, lookaheadMs);
+  return !pcm.empty() && mx_save_wav(path.c_str(), pcm.data(), (int64_t)pcm.size(), outRate, 0) == MX_OK;
+}
+
+bool Mastering::exportWavCompressedAt(const std::string &path, int outRate, const CompressorSettings &compressor, double targetLufs,
+                                      double ceilingDbtp, double lookaheadMs) const {
+  const std::vector<int16_t> pcm = finishCompressedAt(outRate, compressor, targetLufs, ceilingDbtp, lookaheadMs);
   return !pcm.empty() && mx_save_wav(path.c_str(), pcm.data(), (int64_t)pcm.size(), outRate, 0) == MX_OK;
 }
 

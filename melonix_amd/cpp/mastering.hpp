@@ -8,6 +8,7 @@
 //   meter->show(master.loudness().integrated, master.truePeakDb(), master.range().lra);
 //   master.exportWav("take.wav", -16.0, -1.0);               // -16 LUFS under -1 dBTP, a correct RIFF header
 //   master.exportWavAt("take-cd.wav", 44100, -16.0, -1.0);   // the same delivered at 44.1 kHz: converted, then limited
+//   master.exportWavCompressedAt("loud.wav", 48000, {}, -12.0, -1.0);  // compressed first, measured again, then the same chain
 //
 // A render that is already on the device needs no round trip: render f32 into a padded device buffer, mx_audio_wrap_device it
 // and call mx_audio_gain / mx_audio_limit_dev directly.
@@ -17,9 +18,14 @@
 #include <string>
 #include <vector>
 
+#include "compressor.hpp"
 #include "melonix_amd.h"
 
 namespace melonix {
+
+namespace glue {
+struct Session;
+}
 
 class Mastering {
 public:
@@ -51,8 +57,18 @@ public:
   std::vector<int16_t> finishAt(int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs = 0.0) const;
   // finishAt() into a WAV file whose header carries outRate
   bool exportWavAt(const std::string &path, int outRate, double targetLufs, double ceilingDbtp, double lookaheadMs = 0.0) const;
+  // The chain with dynamics: the take through the compressor (mx_audio_compress), the loudness and the true peak measured again
+  // on the compressed object — the compressor changed both —, the gain to targetLufs from that measurement, the conversion, the
+  // limiter, int16.  Empty after a failed call: settings the compressor refuses, or whatever finishAt() refuses.
+  std::vector<int16_t> finishCompressedAt(int outRate, const CompressorSettings &compressor, double targetLufs, double ceilingDbtp,
+                                          double lookaheadMs = 0.0) const;
+  bool exportWavCompressedAt(const std::string &path, int outRate, const CompressorSettings &compressor, double targetLufs,
+                             double ceilingDbtp, double lookaheadMs = 0.0) const;
 
 private:
+  // gain, conversion and limiter from an object of a session (mastering.cpp): what finishAt() and finishCompressedAt() share
+  std::vector<int16_t> deliver(glue::Session &s, const mx_audio *src, int slot, float amp, int outRate, const mx_limit_params &p,
+                               int64_t m) const;
   int sampleRate, device_;
   bool good = false;
   std::vector<float> wav_;

@@ -1,6 +1,7 @@
 // capi_audio.cpp — the audio objects made from another one on the device: the source gain (gain_kernels.hip), the look-ahead
 // limiter (truepeak_kernels.hip), the sample-rate conversion (resample_kernels.hip; its range forms: capi_resample.cpp) and the
-// noise reduction (denoise_kernels.hip; its range forms and prints: capi_denoise.cpp), and
+// noise reduction (denoise_kernels.hip; its range forms and prints: capi_denoise.cpp), the dynamics compressor
+// (compress_kernels.hip; its range forms and its curve: capi_compress.cpp), and
 // the download of an audio object's samples: BUILD-DEFINED, the reference has none of it.  One
 // unit of the C-ABI implementation behind include/melonix_amd.h (see capi_internal.h).  (mx_audio_upload, _wrap_device, _free:
 // capi_ctx.cpp.)
@@ -189,6 +190,24 @@ int mx_audio_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const m
     mx_audio *made = nullptr;
     const int rc = derived_audio(ctx, a->n, "audio denoise", [&](float *dst) {
       status = denoise_enqueue(ctx, a, print, floor, sens, 0, a->n, dst, nullptr);
+      return status == MX_OK ? hipSuccess : hipErrorUnknown;
+    }, &made);
+    if (rc) return status ? status : rc;
+    *out = made;
+    return MX_OK;
+  });
+}
+
+int mx_audio_compress(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, mx_audio **out) {
+  return mx_guard([&]() -> int {
+    if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+    mx_compress_params p;
+    mx_compress_plan plan;
+    if (const int rc = compress_check(sampleRate, params, p, plan)) return rc;
+    int status = MX_OK;  // (compress_enqueue records its own message; derived_audio words the device error it is told of)
+    mx_audio *made = nullptr;
+    const int rc = derived_audio(ctx, a->n, "audio compress", [&](float *dst) {
+      status = compress_enqueue(ctx, a, p, plan, 0, a->n, dst, nullptr);
       return status == MX_OK ? hipSuccess : hipErrorUnknown;
     }, &made);
     if (rc) return status ? status : rc;

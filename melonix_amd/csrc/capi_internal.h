@@ -156,6 +156,7 @@ enum TempoSlot { kTempoFlux, kTempoCurve, kTempoSlots };
 enum ContourSlot { kContourPart, kContourRec, kContourSlots };  // (the records: where the caller wants the statistics alone)
 enum JobSlot { kJobsIn, kJobsOut, kJobSlots };
 enum DenoiseSlot { kDenoiseRows, kDenoisePrint, kDenoiseSlots };  // (the power rows of a learned print; the print a launch reads)
+enum CompressSlot { kCompressPeaks, kCompressCurve, kCompressTable, kCompressSlots };  // (step peaks, the s_b curve, the 2049 targets)
 
 // Arrays handed to the caller, who frees them with mx_free.  add(): a fresh malloc block of n elements (at least one, so an
 // empty result is not a null pointer), copied from src or, src null, left for a download.  give(): every block is there and
@@ -274,6 +275,8 @@ struct mx_ctx {
   mx::WorkMem<mx::kJobSlots> jobs;
   // denoise: the power rows of mx_noise_print* and the print mx_denoise* and mx_audio_denoise hand their launch (capi_denoise.cpp)
   mx::WorkMem<mx::kDenoiseSlots> denoise;
+  // compress: the step peaks and the gain curve of the groups a call touches, and the curve's table (capi_compress.cpp)
+  mx::WorkMem<mx::kCompressSlots> compress;
   // the phase vocoder's bounded work arena, second stream and events (capi_pv_arena.cpp): built on first use, kept for the next
   // call, released by mx_ctx_release_scratch / mx_ctx_destroy; pv_chunk_frames = 0: the default chunk length
   std::mutex pv_mu;
@@ -324,6 +327,13 @@ hipError_t resample_enqueue(mx_ctx *ctx, const mx_audio *a, const mx_resample_pl
 int denoise_check(const float *print, const mx_denoise_params *params, float *floor, float *sens);
 int denoise_enqueue(mx_ctx *ctx, const mx_audio *a, const float *print, float floor, float sens, int64_t first, int64_t count,
                     float *d_f32, int16_t *d_i16);
+// The compressor's pieces that its entry points (capi_compress.cpp) and mx_audio_compress (capi_audio.cpp) share: the check of the
+// rate and the parameters (null: the defaults), worded once, -> the parameters in force and their plan; and outputs [first, first +
+// count) queued on the context's stream: the peaks and the curve of the groups the range touches, in the context's work memory,
+// then the product.
+int compress_check(int sampleRate, const mx_compress_params *params, mx_compress_params &p, mx_compress_plan &plan);
+int compress_enqueue(mx_ctx *ctx, const mx_audio *a, const mx_compress_params &p, const mx_compress_plan &plan, int64_t first,
+                     int64_t count, float *d_f32, int16_t *d_i16);
 int stft_launch(mx_ctx *ctx, const mx_audio *a, int N, int mode, int hop, int64_t first_frame, const int32_t *d_ranges,
                 int64_t count, int kmin, int kmax, float *d_mags, mx_pitch *d_pitch, uint8_t *d_rgb, float cmap_k,
                 int run_length = 0);
@@ -368,6 +378,7 @@ void for_each_work(mx_ctx *ctx, F &&f) {
   f(ctx->contour);
   f(ctx->jobs);
   f(ctx->denoise);
+  f(ctx->compress);
 }
 // gives the phase vocoder's arena, stream and events back (capi_pv_arena.cpp); the caller holds ctx->pv_mu or owns the context
 // outright (mx_ctx_destroy)

@@ -321,6 +321,43 @@ struct NoiseRowsArgs {
 };
 hipError_t launch_noise_rows(const NoiseRowsArgs &a, hipStream_t s);
 hipError_t launch_noise_print(const float *rows, int64_t count, float *print, hipStream_t s);
+// Build-defined dynamics compressor (compress_kernels.hip; definition: include/melonix_amd.h, arithmetic: compress_core.h).
+// Peaks: p_b of steps [first_step, first_step + nsteps), any steps (0 outside the file's) -> out[0 .. nsteps).
+struct CompressPeaksArgs {
+  const float *image;  // padded image (the samples outside the file do not exist whatever the pads hold)
+  int64_t n;
+  int D;
+  int64_t first_step, nsteps;
+  float *out;
+};
+hipError_t launch_compress_peaks(const CompressPeaksArgs &a, hipStream_t s);
+// Curve: groups [g0, g0 + groups) walk their steps [g Gc - W, min((g + 1) Gc, total)) over peaks[b - peaks_first] — every such step
+// is there: the caller's sizing — and store s_b to out[b - out_first] for their own steps inside [out_first, out_end).
+struct CompressCurveArgs {
+  const float *peaks;
+  int64_t peaks_first;
+  const int32_t *table;  // T[0 .. 2049), in HBM
+  int32_t c_att, c_rel, W;
+  int64_t g0, groups, total;
+  int32_t *out;
+  int64_t out_first, out_end;
+};
+hipError_t launch_compress_curve(const CompressCurveArgs &a, hipStream_t s);
+// Apply: outputs [first, first + count), all inside [0, n): checked by the caller.  curve[u - curve_first] = s_u for every
+// u >= 0 the range reads (cp::gain_lo .. cp::gain_hi).  f32 (4-byte aligned) and i16 (2-byte aligned), each or null: no store
+// outside [0 .. count) of either.
+struct CompressApplyArgs {
+  const float *image;
+  int64_t n;
+  int D, K;
+  float makeup;
+  const int32_t *curve;
+  int64_t curve_first;
+  int64_t first, count;
+  float *f32;
+  int16_t *i16;
+};
+hipError_t launch_compress_apply(const CompressApplyArgs &a, hipStream_t s);
 // Build-defined tempo estimation (tempo_kernels.hip; definition: include/melonix_amd.h, arithmetic: tempo_core.h).  Smoothing:
 // count <= INT32_MAX, width in [0, 32], d_out not overlapping d_flux.  Comb: one record per job, count >= 1; a job outside its
 // range (the caller's check) gives a wrong record and nothing worse.
