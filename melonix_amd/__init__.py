@@ -108,26 +108,30 @@ _PARAMS = {"decode": (_capi.F0DecodeParams, "mx_f0_decode_params_default"), "not
            "sibilant": (_capi.SibilantParams, "mx_sibilant_params_default"),
            "chroma": (_capi.ChromaParams, "mx_chroma_params_default"), "bend": (_capi.BendParams, "mx_bend_params_default"),
            "level": (_capi.LevelParams, "mx_level_params_default")}
+# the same for the kinds whose entry point takes arguments in front of the block and returns a status: compress, the sample rate
+_PARAMS_OF = {"compress": (_capi.CompressParams, "mx_compress_params_default")}
 
 
-def _params_default(kind: str) -> dict:
-    struct, fn = _PARAMS[kind]
+def _params_default(kind: str, *args) -> dict:
+    struct, fn = _PARAMS_OF[kind] if args else _PARAMS[kind]
     p = struct()
-    getattr(_capi.lib(), fn)(C.byref(p))
+    rc = getattr(_capi.lib(), fn)(*args, C.byref(p))
+    if rc:
+        _capi.check(rc)
     return _fields(p)
 
 
-def _params_arg(kind: str, params: dict, never_null: bool = False):
-    """The defaults with `params` over them, each value as its field's type (int or float), for the C-ABI; nothing given:
-    NULL, the library's defaults (never_null: the defaults as a struct, for an entry point that refuses NULL)."""
+def _params_arg(kind: str, params: dict, never_null: bool = False, args=()):
+    """The defaults (of `args`, where the kind's entry point takes any) with `params` over them, each value as its field's type
+    (int or float), for the C-ABI; nothing given: NULL, the library's defaults (never_null: the defaults as a struct, for an
+    entry point that refuses NULL)."""
     if not params and not never_null:
         return None
-    d = _params_default(kind)
-    unknown = set(params) - set(d)
+    struct = (_PARAMS_OF if args else _PARAMS)[kind][0]
+    unknown = set(params) - {k for k, _ in struct._fields_}
     if unknown:
         raise TypeError(f"unknown {kind} parameters {sorted(unknown)}")
-    d.update(params)
-    struct = _PARAMS[kind][0]
+    d = {**_params_default(kind, *args), **params}
     return C.byref(struct(**{k: (float if t in (C.c_float, C.c_double) else int)(d[k]) for k, t in struct._fields_}))
 
 
@@ -693,46 +697,52 @@ class Context:
         _call("mx_denoise_dev", self.handle, audio.handle, _ptr(pr), _denoise_params(reduction_db, sensitivity_db), first, count,
               _dev(d_f32), _dev(d_i16))
 
+    def _pcm_range(self, name: str, audio: Audio, head: tuple, first: int, count: int | None, want_f32: bool, want_i16: bool):
+        """name(ctx, audio, *head, first, count, f32, i16): samples [first, first + count) of a processed take (count None: to the
+        take's end) -> (float32 | None, int16 | None)."""
+        count = audio.n - first if count is None else count
+        f, i = _pcm_pair(max(count, 0), want_f32, want_i16)
+        _call(name, self.handle, audio.handle, *head, first, count, _ptr(f), _ptr(i))
+        return f, i
+
     def denoise_range(self, audio: Audio, noise_print, reduction_db: float = 12.0, sensitivity_db: float = 6.0, first: int = 0,
                       count: int | None = None, want_f32: bool = True, want_i16: bool = False):
         """-> (float32 | None, int16 | None) outputs [first, first + count) of the cleaned take (count None: to its end).  Blocks."""
-        count = audio.n - first if count is None else count
         pr = _noise_print_arg(noise_print)
-        f, i = _pcm_pair(max(count, 0), want_f32, want_i16)
-        _call("mx_denoise", self.handle, audio.handle, _ptr(pr), _denoise_params(reduction_db, sensitivity_db), first, count,
-              _ptr(f), _ptr(i))
-        return f, i
+        return self._pcm_range("mx_denoise", audio, (_ptr(pr), _denoise_params(reduction_db, sensitivity_db)), first, count,
+                               want_f32, want_i16)
 
     # ---- dynamics compressor and its gain-reduction curve (build-defined; include/melonix_amd.h).  params: fields of
     # compress_params_default() ----
     def compress(self, audio: Audio, sr: int, **params) -> Audio:
         """A new Audio: `audio` through the compressor at sr.  Asynchronous on the context's stream."""
-        return self._audio(audio.n, "mx_audio_compress", audio.handle, int(sr), _compress_params(params))
+        return self._audio(audio.n, "mx_audio_compress", audio.handle, int(sr), _params_arg("compress", params, True, (int(sr),)))
 
     def compress_dev(self, audio: Audio, sr: int, first: int, count: int, d_f32: int | None = None, d_i16: int | None = None, **params):
         """Outputs [first, first + count) of the compressed take stay in HBM: float32 at d_f32 and / or int16 at d_i16 (None: not
         wanted); asynchronous on the context's stream."""
-        _call("mx_compress_dev", self.handle, audio.handle, int(sr), _compress_params(params), first, count, _dev(d_f32), _dev(d_i16))
+        _call("mx_compress_dev", self.handle, audio.handle, int(sr), _params_arg("compress", params, True, (int(sr),)), first, count,
+              _dev(d_f32), _dev(d_i16))
 
     def compress_range(self, audio: Audio, sr: int, first: int = 0, count: int | None = None, want_f32: bool = True,
                        want_i16: bool = False, **params):
         """-> (float32 | None, int16 | None) outputs [first, first + count) of the compressed take (count None: to its end).  Blocks."""
-        count = audio.n - first if count is None else count
-        f, i = _pcm_pair(max(count, 0), want_f32, want_i16)
-        _call("mx_compress", self.handle, audio.handle, int(sr), _compress_params(params), first, count, _ptr(f), _ptr(i))
-        return f, i
+        return self._pcm_range("mx_compress", audio, (int(sr), _params_arg("compress", params, True, (int(sr),))), first, count,
+                               want_f32, want_i16)
 
     def compress_gain(self, audio: Audio, sr: int, first_step: int = 0, nsteps: int | None = None, **params):
         """-> the smoothed gain s_b of steps [first_step, first_step + nsteps) as int32 Q30 (nsteps None: to the last): the
         gain-reduction meter, 20 log10(s / 2^30) dB.  Blocks."""
         nsteps = compress_steps(audio.n, sr) - first_step if nsteps is None else nsteps
         out = np.empty(max(nsteps, 0), dtype=np.int32)
-        _call("mx_compress_gain", self.handle, audio.handle, int(sr), _compress_params(params), first_step, nsteps, _ptr(out))
+        _call("mx_compress_gain", self.handle, audio.handle, int(sr), _params_arg("compress", params, True, (int(sr),)), first_step, nsteps,
+              _ptr(out))
         return out
 
     def compress_gain_dev(self, audio: Audio, sr: int, first_step: int, nsteps: int, d_gain: int, **params):
         """The same curve stays in HBM at d_gain (int32); asynchronous on the context's stream."""
-        _call("mx_compress_gain_dev", self.handle, audio.handle, int(sr), _compress_params(params), first_step, nsteps, _dev(d_gain))
+        _call("mx_compress_gain_dev", self.handle, audio.handle, int(sr), _params_arg("compress", params, True, (int(sr),)), first_step, nsteps,
+              _dev(d_gain))
 
     def compress_peaks_dev(self, audio: Audio, sr: int, first_step: int, nsteps: int, d_peaks: int):
         """The peaks p_b of steps [first_step, first_step + nsteps) stay in HBM at d_peaks (float32); asynchronous on the
@@ -1359,6 +1369,27 @@ def normalize_gain_tp(measured: dict, true_peak: float, target_lufs: float = -23
 
 
 # ---- sample-rate conversion: the plan, the length and the tap table of a rate pair (host; build-defined) ----
+def resample_plan(in_rate: int, out_rate: int) -> dict:
+    """The plan of in_rate -> out_rate -> {L, M, taps, half}; equal rates: {1, 1, 0, 0}.  MxError for a refused pair."""
+    p = _capi.ResamplePlan()
+    _call("mx_resample_plan_for", int(in_rate), int(out_rate), C.byref(p))
+    return _fields(p)
+
+
+def resample_length(n: int, in_rate: int, out_rate: int) -> int:
+    """m = ceil(n L / M): the samples of a take of n converted from in_rate to out_rate."""
+    return _call("mx_resample_length", int(n), int(in_rate), int(out_rate))
+
+
+def resample_taps(in_rate: int, out_rate: int):
+    """The tap table -> float32[L, taps], a row per phase ([1, 0] for equal rates)."""
+    p = resample_plan(in_rate, out_rate)
+    out = np.empty((p["L"], p["taps"]), dtype=np.float32)
+    _call("mx_resample_taps", int(in_rate), int(out_rate), _ptr(out))
+    return out
+
+
+# ---- noise reduction: the print and parameter arguments, the frame count, the factors, a print of rows (host; build-defined) ----
 DENOISE_BINS = _capi.DENOISE_BINS
 
 
@@ -1399,58 +1430,23 @@ COMPRESS_CURVE = _capi.COMPRESS_CURVE
 
 def compress_params_default(sr: int = 48000) -> dict:
     """The compressor's defaults: -18 dB, 4 : 1, a 6 dB knee, 5 ms / 100 ms, no look-ahead, make-up 1."""
-    p = _capi.CompressParams()
-    _call("mx_compress_params_default", int(sr), C.byref(p))
-    return _fields(p)
-
-
-def _compress_struct(params: dict):
-    d = compress_params_default()
-    unknown = set(params) - set(d)
-    if unknown:
-        raise TypeError(f"unknown compress parameters {sorted(unknown)}")
-    d.update(params)
-    return _capi.CompressParams(*(float(d[k]) for k, _ in _capi.CompressParams._fields_))
-
-
-def _compress_params(params: dict):
-    return C.byref(_compress_struct(params))
+    return _params_default("compress", int(sr))
 
 
 def compress_plan(sr: int, **params) -> dict:
     """The plan of `params` at sr -> {D, K, c_att, c_rel, W, Gc}.  MxError for a refused rate or parameter."""
     q = _capi.CompressPlan()
-    _call("mx_compress_plan_for", int(sr), _compress_params(params), C.byref(q))
+    _call("mx_compress_plan_for", int(sr), _params_arg("compress", params, True, (int(sr),)), C.byref(q))
     return _fields(q)
 
 
 def compress_curve(**params):
     """-> the 2049 Q30 gain targets (int32) of `params`: what the device, the emulation and numpy look up."""
     out = np.empty(COMPRESS_CURVE, dtype=np.int32)
-    _call("mx_compress_curve", _compress_params(params), _ptr(out))
+    _call("mx_compress_curve", _params_arg("compress", params, True, (48000,)), _ptr(out))
     return out
 
 
 def compress_steps(n: int, sr: int) -> int:
     """B = ceil(n / D), D = (sr + 500) // 1000: the control steps of the compressor over a take of n samples."""
     return _call("mx_compress_steps", int(n), int(sr))
-
-
-def resample_plan(in_rate: int, out_rate: int) -> dict:
-    """The plan of in_rate -> out_rate -> {L, M, taps, half}; equal rates: {1, 1, 0, 0}.  MxError for a refused pair."""
-    p = _capi.ResamplePlan()
-    _call("mx_resample_plan_for", int(in_rate), int(out_rate), C.byref(p))
-    return _fields(p)
-
-
-def resample_length(n: int, in_rate: int, out_rate: int) -> int:
-    """m = ceil(n L / M): the samples of a take of n converted from in_rate to out_rate."""
-    return _call("mx_resample_length", int(n), int(in_rate), int(out_rate))
-
-
-def resample_taps(in_rate: int, out_rate: int):
-    """The tap table -> float32[L, taps], a row per phase ([1, 0] for equal rates)."""
-    p = resample_plan(in_rate, out_rate)
-    out = np.empty((p["L"], p["taps"]), dtype=np.float32)
-    _call("mx_resample_taps", int(in_rate), int(out_rate), _ptr(out))
-    return out

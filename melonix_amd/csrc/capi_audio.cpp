@@ -14,9 +14,15 @@ using namespace mx;
 
 namespace {
 
-// A new audio object of n samples at *out: zeroed pads, and the samples that `fill(dst) -> hipError_t` queues behind the two
-// clears (not called for an empty take).  Queued on the context's stream; nothing is left allocated where it fails.  `what` names
-// the call in a device error.
+// a device call's status as an entry point's: the error recorded the way every derived-audio call words it
+int hip_status(const char *what, hipError_t e) {
+  return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+
+// A new audio object of n samples at *out: zeroed pads, and the samples that `fill(dst) -> status` queues behind the two clears
+// (not called for an empty take); a fill that fails has recorded its error.  Queued on the context's stream.  The call owns the
+// buffer until the object does: on every other path out, a throw included, the stream is drained and the buffer freed.  `what`
+// names the call in a device error of the clears.
 template <class F>
 int derived_audio(mx_ctx *ctx, int64_t length, const char *what, F &&fill, mx_audio **out) {
   if (length > 0x7fffffffLL - 2 * MX_AUDIO_PAD)  // (mx_audio_upload's bound, before anything is allocated)
@@ -24,16 +30,15 @@ int derived_audio(mx_ctx *ctx, int64_t length, const char *what, F &&fill, mx_au
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mx_audio> b(new mx_audio());
   const size_t n = (size_t)length, pad = (size_t)MX_AUDIO_PAD;
-  hipError_t e = hipMalloc(&b->d_padded, (n + 2 * pad) * sizeof(float));
+  DeviceArray<float> d;
+  hipError_t e = d.alloc(ctx->stream, n + 2 * pad);
   if (e != hipSuccess) return fail(MX_ERR_NOMEM, "audio buffer: %s", hipGetErrorString(e));
-  e = hipMemsetAsync(b->d_padded, 0, pad * sizeof(float), ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(b->d_padded + pad + n, 0, pad * sizeof(float), ctx->stream);
-  if (e == hipSuccess && n > 0) e = fill(b->d_padded + pad);
-  if (e != hipSuccess) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(b->d_padded);
-    return fail(MX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
-  }
+  e = hipMemsetAsync(d.p, 0, pad * sizeof(float), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d.p + pad + n, 0, pad * sizeof(float), ctx->stream);
+  if (const int rc = hip_status(what, e)) return rc;
+  if (n > 0)
+    if (const int rc = fill(d.p + pad)) return rc;
+  b->d_padded = d.release();
   b->n = length;
   b->owned = true;
   *out = b.release();
@@ -61,8 +66,9 @@ int derived_audio_host(mx_ctx *ctx, int64_t length, const char *what, const Devi
 // the samples a's (npts == 0) or a's through the gain of `d_pts`
 auto gain_fill(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *d_pts, int64_t npts) {
   return [=](float *dst) {
-    if (npts == 0) return hipMemcpyAsync(dst, a->d_padded + MX_AUDIO_PAD, (size_t)a->n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-    return launch_audio_gain(a->d_padded + MX_AUDIO_PAD, dst, a->n, d_pts, npts, ctx->stream);
+    const float *src = a->d_padded + MX_AUDIO_PAD;
+    return hip_status("audio gain", npts == 0 ? hipMemcpyAsync(dst, src, (size_t)a->n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream)
+                                              : launch_audio_gain(src, dst, a->n, d_pts, npts, ctx->stream));
   };
 }
 
@@ -73,7 +79,7 @@ mx_limit_params limit_defaults(int sr) {
 
 // what the two limiter entry points check of their arguments -> p, the parameters in force
 int limit_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_params *params, mx_audio **out, mx_limit_params &p) {
-  if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+  if (const int rc = handles_out_check(ctx, a, out)) return rc;
   if (const int rc = step_rate_check(sampleRate)) return rc;
   p = params_or(params, limit_defaults(sampleRate));
   if (!std::isnormal(p.ceiling_amp) || !(p.ceiling_amp > 0.f && p.ceiling_amp <= 1.f))
@@ -94,7 +100,7 @@ auto limit_fill(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limit_p
     g.lookahead = p.lookahead;
     g.dst = dst;
     g.pcm16 = d_pcm16;
-    return launch_audio_limit(g, ctx->stream);
+    return hip_status("audio limit", launch_audio_limit(g, ctx->stream));
   };
 }
 
@@ -125,7 +131,7 @@ int mx_audio_gain(mx_ctx *ctx, const mx_audio *a, const mx_gain_point *points, i
 
 int mx_audio_download(mx_ctx *ctx, const mx_audio *a, int64_t first, int64_t count, float *host_out) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (count < 0 || first < -(int64_t)MX_AUDIO_PAD || first > a->n + MX_AUDIO_PAD || count > a->n + MX_AUDIO_PAD - first)
       return fail(MX_ERR_INVALID, "samples [%lld, %lld) outside the padded audio", (long long)first, (long long)(first + count));
     if (count > 0 && !host_out) return fail(MX_ERR_INVALID, "null output");
@@ -170,49 +176,39 @@ int mx_audio_limit(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_limi
 
 int mx_audio_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, mx_audio **out) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+    if (const int rc = handles_out_check(ctx, a, out)) return rc;
     mx_resample_plan p;
     if (const int rc = resample_plan_check(inRate, outRate, p)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const float *d_table = nullptr;
     if (const int rc = resample_table_dev(ctx, p, &d_table)) return rc;
     const int64_t m = rs::out_length(a->n, p);
-    return derived_audio(ctx, m, "audio resample", [=](float *dst) { return resample_enqueue(ctx, a, p, d_table, 0, m, dst); }, out);
+    return derived_audio(ctx, m, "audio resample", [=](float *dst) {
+      return hip_status("audio resample", resample_enqueue(ctx, a, p, d_table, 0, m, dst));
+    }, out);
   });
 }
 
 int mx_audio_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, mx_audio **out) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+    if (const int rc = handles_out_check(ctx, a, out)) return rc;
     float floor = 0.f, sens = 0.f;
     if (const int rc = denoise_check(print, params, &floor, &sens)) return rc;
-    int status = MX_OK;  // (denoise_enqueue records its own message; derived_audio words the device error it is told of)
-    mx_audio *made = nullptr;
-    const int rc = derived_audio(ctx, a->n, "audio denoise", [&](float *dst) {
-      status = denoise_enqueue(ctx, a, print, floor, sens, 0, a->n, dst, nullptr);
-      return status == MX_OK ? hipSuccess : hipErrorUnknown;
-    }, &made);
-    if (rc) return status ? status : rc;
-    *out = made;
-    return MX_OK;
+    return derived_audio(ctx, a->n, "audio denoise", [&](float *dst) {
+      return denoise_enqueue(ctx, a, print, floor, sens, 0, a->n, dst, nullptr);
+    }, out);
   });
 }
 
 int mx_audio_compress(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, mx_audio **out) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+    if (const int rc = handles_out_check(ctx, a, out)) return rc;
     mx_compress_params p;
     mx_compress_plan plan;
     if (const int rc = compress_check(sampleRate, params, p, plan)) return rc;
-    int status = MX_OK;  // (compress_enqueue records its own message; derived_audio words the device error it is told of)
-    mx_audio *made = nullptr;
-    const int rc = derived_audio(ctx, a->n, "audio compress", [&](float *dst) {
-      status = compress_enqueue(ctx, a, p, plan, 0, a->n, dst, nullptr);
-      return status == MX_OK ? hipSuccess : hipErrorUnknown;
-    }, &made);
-    if (rc) return status ? status : rc;
-    *out = made;
-    return MX_OK;
+    return derived_audio(ctx, a->n, "audio compress", [&](float *dst) {
+      return compress_enqueue(ctx, a, p, plan, 0, a->n, dst, nullptr);
+    }, out);
   });
 }
 

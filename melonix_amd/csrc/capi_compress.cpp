@@ -63,7 +63,7 @@ int curve_enqueue(Hold<kCompressSlots> &w, mx_ctx *ctx, const mx_audio *a, const
 // what the two curve forms check of their arguments
 int gain_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first_step, int64_t nsteps,
                const void *out, mx_compress_params &p, mx_compress_plan &plan) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = handles_check(ctx, a)) return rc;
   if (const int rc = compress_check(sampleRate, params, p, plan)) return rc;
   return unit_span("steps", first_step, nsteps, cp::steps_of(a->n, plan.D), out);
 }
@@ -73,14 +73,6 @@ int gain_enqueue(mx_ctx *ctx, const mx_audio *a, const mx_compress_params &p, co
   Hold w(ctx, ctx->compress);
   return curve_enqueue(w, ctx, a, p, plan, first_step, first_step + nsteps - 1, d_gain, first_step, first_step + nsteps, nullptr,
                        nullptr);
-}
-
-// what the two range forms check of their arguments
-int range_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first, int64_t count,
-                const void *f32, const void *i16, mx_compress_params &p, mx_compress_plan &plan) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-  if (const int rc = compress_check(sampleRate, params, p, plan)) return rc;
-  return unit_span("outputs", first, count, a->n, f32 ? f32 : i16);
 }
 
 }  // namespace
@@ -117,6 +109,22 @@ int compress_enqueue(mx_ctx *ctx, const mx_audio *a, const mx_compress_params &p
 }
 
 }  // namespace mx
+
+namespace {
+
+// the two range forms: the unit's own checks -> the parameters in force and their plan, then the tail
+int range_call(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first, int64_t count,
+               float *f32, int16_t *i16, bool device) {
+  if (const int rc = handles_check(ctx, a)) return rc;
+  mx_compress_params p;
+  mx_compress_plan plan;
+  if (const int rc = compress_check(sampleRate, params, p, plan)) return rc;
+  return pcm_range(ctx, device, false, first, count, a->n, f32, i16, [&](float *d_f32, int16_t *d_i16) {
+    return compress_enqueue(ctx, a, p, plan, first, count, d_f32, d_i16);
+  });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -160,11 +168,11 @@ int64_t mx_compress_steps(int64_t n, int sampleRate) {
 
 int mx_compress_peaks_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_step, int64_t nsteps, float *d_peaks) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (const int rc = step_rate_check(sampleRate)) return rc;
     const int D = cp::step_samples(sampleRate);
     if (const int rc = unit_span("steps", first_step, nsteps, cp::steps_of(a->n, D), d_peaks)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_peaks) % 4) return fail(MX_ERR_INVALID, "device peaks must be 4-byte aligned");
+    if (const int rc = align_check(d_peaks, 4, "device peaks")) return rc;
     if (nsteps == 0) return MX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     CompressPeaksArgs k{};
@@ -185,7 +193,7 @@ int mx_compress_gain_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const m
     mx_compress_params p;
     mx_compress_plan plan;
     if (const int rc = gain_parse(ctx, a, sampleRate, params, first_step, nsteps, d_gain, p, plan)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_gain) % 4) return fail(MX_ERR_INVALID, "a device gain curve must be 4-byte aligned");
+    if (const int rc = align_check(d_gain, 4, "a device gain curve")) return rc;
     if (nsteps == 0) return MX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     return gain_enqueue(ctx, a, p, plan, first_step, nsteps, d_gain);
@@ -199,42 +207,19 @@ int mx_compress_gain(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_co
     mx_compress_plan plan;
     if (const int rc = gain_parse(ctx, a, sampleRate, params, first_step, nsteps, gain, p, plan)) return rc;
     if (nsteps == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeviceArray<int32_t> d;
-    hipError_t e = d.alloc(ctx->stream, (size_t)nsteps);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device gain curve: %s", hipGetErrorString(e));
-    if (const int rc = gain_enqueue(ctx, a, p, plan, first_step, nsteps, d.p)) return rc;
-    e = d.download(gain);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "gain curve download: %s", hipGetErrorString(e));
+    return array_to_host(ctx, nsteps, gain, "device gain curve", "gain curve download",
+                         [&](int32_t *d_gain) { return gain_enqueue(ctx, a, p, plan, first_step, nsteps, d_gain); });
   });
 }
 
 int mx_compress_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first, int64_t count,
                     float *d_f32, int16_t *d_i16) {
-  return mx_guard([&]() -> int {
-    mx_compress_params p;
-    mx_compress_plan plan;
-    if (const int rc = range_parse(ctx, a, sampleRate, params, first, count, d_f32, d_i16, p, plan)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_f32) % 4 || reinterpret_cast<uintptr_t>(d_i16) % 2)
-      return fail(MX_ERR_INVALID, "device samples must be 4-byte (f32) and 2-byte (int16) aligned");
-    if (count == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return compress_enqueue(ctx, a, p, plan, first, count, d_f32, d_i16);
-  });
+  return mx_guard([&]() -> int { return range_call(ctx, a, sampleRate, params, first, count, d_f32, d_i16, true); });
 }
 
 int mx_compress(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_compress_params *params, int64_t first, int64_t count,
                 float *f32_out, int16_t *i16_out) {
-  return mx_guard([&]() -> int {
-    mx_compress_params p;
-    mx_compress_plan plan;
-    if (const int rc = range_parse(ctx, a, sampleRate, params, first, count, f32_out, i16_out, p, plan)) return rc;
-    if (count == 0) return MX_OK;
-    return pcm_to_host(ctx, count, f32_out, i16_out, [&](float *d_f32, int16_t *d_i16) {
-      return compress_enqueue(ctx, a, p, plan, first, count, d_f32, d_i16);
-    });
-  });
+  return mx_guard([&]() -> int { return range_call(ctx, a, sampleRate, params, first, count, f32_out, i16_out, false); });
 }
 
 }  // extern "C"

@@ -92,7 +92,7 @@ int get_wtab(mx_ctx *ctx, int N, int hop, const NTables &nt, const float **out) 
 }
 
 int check_common(mx_ctx *ctx, const mx_audio *a, int N, int64_t count, int &kmin, int &kmax) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = handles_check(ctx, a)) return rc;
   if (N != 4096 && N != 16384 && N != 32768)
     return fail(MX_ERR_INVALID, "unsupported FFT size %d (supported: 4096, 16384, 32768)", N);
   if (count < 0) return fail(MX_ERR_INVALID, "negative frame count");
@@ -104,7 +104,7 @@ int check_common(mx_ctx *ctx, const mx_audio *a, int N, int64_t count, int &kmin
 }
 
 int file_frames(const mx_ctx *ctx, const mx_audio *a, int hop, int64_t &frames) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = handles_check(ctx, a)) return rc;
   if (const int rc = hop_check(hop)) return rc;
   frames = (a->n + hop - 1) / hop;
   return MX_OK;
@@ -330,8 +330,7 @@ int mx_audio_wrap_device(mx_ctx *ctx, const float *d_padded, int64_t n, mx_audio
     if (!ctx || !out || !d_padded || n < 0) return fail(MX_ERR_INVALID, "bad argument");
     if (n > 0x7fffffffLL - 2 * MX_AUDIO_PAD)  // (mx_audio_upload's bound: the kernels index the padded image in int32)
       return fail(MX_ERR_INVALID, "audio longer than the reference's int sample indices allow");
-    if (reinterpret_cast<uintptr_t>(d_padded) & 15)  // the kernels use 8- and 16-byte loads of the samples
-      return fail(MX_ERR_INVALID, "device audio buffer must be 16-byte aligned");
+    if (const int rc = align_check(d_padded, 16, "device audio buffer")) return rc;  // the kernels use 8- and 16-byte loads of the samples
     mx_audio *a = new (std::nothrow) mx_audio();
     if (!a) return fail(MX_ERR_NOMEM, "out of host memory");
     a->d_padded = const_cast<float *>(d_padded);

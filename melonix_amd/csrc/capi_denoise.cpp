@@ -47,12 +47,15 @@ int denoise_enqueue(mx_ctx *ctx, const mx_audio *a, const float *print, float fl
 
 namespace {
 
-// what the range forms check of their arguments -> the two factors
-int range_parse(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, int64_t first, int64_t count,
-                const void *f32, const void *i16, float *floor, float *sens) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
-  if (const int rc = denoise_check(print, params, floor, sens)) return rc;
-  return unit_span("outputs", first, count, a->n, f32 ? f32 : i16);
+// the two range forms: the unit's own checks -> the two factors, then the tail
+int range_call(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, int64_t first, int64_t count,
+               float *f32, int16_t *i16, bool device) {
+  if (const int rc = handles_check(ctx, a)) return rc;
+  float floor = 0.f, sens = 0.f;
+  if (const int rc = denoise_check(print, params, &floor, &sens)) return rc;
+  return pcm_range(ctx, device, false, first, count, a->n, f32, i16, [&](float *d_f32, int16_t *d_i16) {
+    return denoise_enqueue(ctx, a, print, floor, sens, first, count, d_f32, d_i16);
+  });
 }
 
 int rows_launch(mx_ctx *ctx, const mx_audio *a, int64_t first_frame, int64_t count, float *d_rows) {
@@ -71,7 +74,7 @@ int rows_launch(mx_ctx *ctx, const mx_audio *a, int64_t first_frame, int64_t cou
 
 // the region's frames, or its refusal
 int region_parse(mx_ctx *ctx, const mx_audio *a, int64_t begin, int64_t end, const void *out, int64_t *first_frame, int64_t *count) {
-  if (!ctx || !a || !out) return fail(MX_ERR_INVALID, "null context, audio handle or output");
+  if (const int rc = handles_out_check(ctx, a, out)) return rc;
   if (!noise_region_frames(a->n, begin, end, first_frame, count))
     return fail(MX_ERR_INVALID, "samples [%lld, %lld): a region inside the take's %lld samples with 1 to %d whole frames of %d", (long long)begin,
                 (long long)end, (long long)a->n, dn::kMaxPrintFrames, dn::kN);
@@ -80,7 +83,7 @@ int region_parse(mx_ctx *ctx, const mx_audio *a, int64_t begin, int64_t end, con
 
 // the device form: the rows into the context's work memory, their print to d_print
 int print_launch(mx_ctx *ctx, const mx_audio *a, int64_t first_frame, int64_t count, float *d_print) {
-  if (reinterpret_cast<uintptr_t>(d_print) % 4) return fail(MX_ERR_INVALID, "a device print must be 4-byte aligned");
+  if (const int rc = align_check(d_print, 4, "a device print")) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   Hold w(ctx, ctx->denoise);
   float *d_rows = nullptr;
@@ -114,9 +117,9 @@ int mx_denoise_factors(const mx_denoise_params *params, float *out) {
 
 int mx_noise_rows_dev(mx_ctx *ctx, const mx_audio *a, int64_t first_frame, int64_t count, float *d_rows) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (const int rc = unit_span("frames", first_frame, count, dn::frames_of(a->n), d_rows)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_rows) % 4) return fail(MX_ERR_INVALID, "device rows must be 4-byte aligned");
+    if (const int rc = align_check(d_rows, 4, "device rows")) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     return rows_launch(ctx, a, first_frame, count, d_rows);
   });
@@ -143,40 +146,19 @@ int mx_noise_print(mx_ctx *ctx, const mx_audio *a, int64_t begin, int64_t end, f
   return mx_guard([&]() -> int {
     int64_t f0 = 0, count = 0;
     if (const int rc = region_parse(ctx, a, begin, end, print, &f0, &count)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeviceArray<float> d;
-    hipError_t e = d.alloc(ctx->stream, (size_t)dn::kBins);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device print: %s", hipGetErrorString(e));
-    if (const int rc = print_launch(ctx, a, f0, count, d.p)) return rc;
-    e = d.download(print);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "print download: %s", hipGetErrorString(e));
+    return array_to_host(ctx, dn::kBins, print, "device print", "print download",
+                         [&](float *d_print) { return print_launch(ctx, a, f0, count, d_print); });
   });
 }
 
 int mx_denoise_dev(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, int64_t first,
                    int64_t count, float *d_f32, int16_t *d_i16) {
-  return mx_guard([&]() -> int {
-    float floor = 0.f, sens = 0.f;
-    if (const int rc = range_parse(ctx, a, print, params, first, count, d_f32, d_i16, &floor, &sens)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_f32) % 4 || reinterpret_cast<uintptr_t>(d_i16) % 2)
-      return fail(MX_ERR_INVALID, "device samples must be 4-byte (f32) and 2-byte (int16) aligned");
-    if (count == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return denoise_enqueue(ctx, a, print, floor, sens, first, count, d_f32, d_i16);
-  });
+  return mx_guard([&]() -> int { return range_call(ctx, a, print, params, first, count, d_f32, d_i16, true); });
 }
 
 int mx_denoise(mx_ctx *ctx, const mx_audio *a, const float *print, const mx_denoise_params *params, int64_t first, int64_t count,
                float *f32_out, int16_t *i16_out) {
-  return mx_guard([&]() -> int {
-    float floor = 0.f, sens = 0.f;
-    if (const int rc = range_parse(ctx, a, print, params, first, count, f32_out, i16_out, &floor, &sens)) return rc;
-    if (count == 0) return MX_OK;
-    return pcm_to_host(ctx, count, f32_out, i16_out, [&](float *d_f32, int16_t *d_i16) {
-      return denoise_enqueue(ctx, a, print, floor, sens, first, count, d_f32, d_i16);
-    });
-  });
+  return mx_guard([&]() -> int { return range_call(ctx, a, print, params, first, count, f32_out, i16_out, false); });
 }
 
 }  // extern "C"

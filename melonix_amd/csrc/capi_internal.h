@@ -1,10 +1,12 @@
 // capi_internal.h — what the units of the C-ABI implementation (capi_*.cpp) share: the context and audio handle types, the error
 // slot behind mx_last_error, the per-N table cache, and the sequences written once: the owners of device memory (DeviceArray for a
 // call; WorkMem, a locked set of GrowBufs, for a context), the chunked host-staged loop (staged_batch), the host form of a job-list
-// call (job_pass), the PCM download (pcm_to_host), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING
+// call (job_pass), the host form of a device form that writes one array (array_to_host) or PCM in two formats (pcm_to_host), the
+// tail of a PCM range entry point (pcm_range), the arrays handed out for mx_free (HandOver, hand_over), the MELONIX_TIMING
 // phase clock (PhaseClock); for the per-frame tracks (f0, onset strength, sibilant features, chroma): the frame-span check
 // (frame_span), the staged host form (staged_records), a call's common head, its parse and its one-record host form (TrackCall,
-// track_parse, staged_track), the small argument checks (hop_check, rate_check, frames_i32, notes_check); for the step records
+// track_parse, staged_track), the small argument checks (handles_check, handles_out_check, align_check, hop_check, rate_check,
+// frames_i32, notes_check); for the step records
 // (loudness, true peak): their rate check, span check, head and parse (step_rate_check, unit_span, StepsCall, steps_parse); a whole
 // take's records reduced on the host (whole_take); the parameters in force and their defaults (params_or, params_default), the
 // device tables built on the host (upload_table).
@@ -25,6 +27,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/melonix_amd.h"
@@ -113,6 +116,7 @@ struct DeviceArray {
     hipFree(p);
     p = nullptr;
   }
+  T *release() { return std::exchange(p, nullptr); }  // (the buffer goes on living: its new owner frees it)
   hipError_t alloc(hipStream_t s, size_t count) {  // (count 0: no buffer)
     reset();
     stream = s;
@@ -455,6 +459,20 @@ int pcm_to_host(mx_ctx *ctx, int64_t n, float *f_out, int16_t *i_out, F &&to_dev
   return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "PCM download: %s", hipGetErrorString(e));
 }
 
+// The host-pointer form of a device form that writes one array: `to_device(d) -> status` fills a device array of n elements of T,
+// which reach `host` only if it succeeded.  `device_what` names the array where it cannot be had, `download_what` its way back.
+template <class T, class F>
+int array_to_host(mx_ctx *ctx, int64_t n, T *host, const char *device_what, const char *download_what, F &&to_device) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  DeviceArray<T> d;
+  hipError_t e = d.alloc(ctx->stream, (size_t)n);
+  if (e != hipSuccess) return fail(MX_ERR_NOMEM, "%s: %s", device_what, hipGetErrorString(e));
+  if (const int rc = to_device(d.p)) return rc;
+  e = d.download(host);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "%s: %s", download_what, hipGetErrorString(e));
+}
+
 // One kind of per-frame record of a staged call: the staging buffer it passes through, its bytes per frame (0: the call has no
 // such records, the device pointer is null), the caller's records to upload and the caller's room for the result, each or null.
 struct StagedSlot {
@@ -523,8 +541,20 @@ struct TrackCall {
   int sampleRate, hop;
   int64_t first_frame, count;
 };
-// The small argument checks, each refusal worded once: the hop range (file_frames' too), a positive sample rate, a frame count the
-// kernels index with int32, and of a note list — `finite`: every note number; `ordered`: none reversed, empty or overlapping.
+// The small argument checks, each refusal worded once: the handles every call needs (handles_check) and with them the handle a
+// call hands out (handles_out_check), a device pointer's alignment (`noun`: what the message calls the memory), the hop range
+// (file_frames' too), a positive sample rate, a frame count the kernels index with int32, and of a note list — `finite`: every note
+// number; `ordered`: none reversed, empty or overlapping.
+inline int handles_check(const mx_ctx *ctx, const mx_audio *a) {
+  return ctx && a ? MX_OK : fail(MX_ERR_INVALID, "null context or audio handle");
+}
+inline int handles_out_check(const mx_ctx *ctx, const mx_audio *a, const void *out) {
+  return ctx && a && out ? MX_OK : fail(MX_ERR_INVALID, "null context, audio handle or output");
+}
+inline bool misaligned(const void *p, unsigned k) { return reinterpret_cast<uintptr_t>(p) % k != 0; }
+inline int align_check(const void *p, unsigned k, const char *noun) {
+  return misaligned(p, k) ? fail(MX_ERR_INVALID, "%s must be %u-byte aligned", noun, k) : MX_OK;
+}
 inline int hop_check(int hop) { return hop >= 1 && hop <= 16384 ? MX_OK : fail(MX_ERR_INVALID, "hop %d outside [1, 16384]", hop); }
 inline int rate_check(int sampleRate) { return sampleRate > 0 ? MX_OK : fail(MX_ERR_INVALID, "sample rate %d", sampleRate); }
 inline int frames_i32(int64_t count) {
@@ -581,11 +611,32 @@ inline int unit_span(const char *unit, int64_t first, int64_t count, int64_t tot
 template <class Total>
 int steps_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, const char *unit, Total &&total, int64_t first, int64_t count,
                 const void *out, StepsCall &q) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = handles_check(ctx, a)) return rc;
   if (const int rc = step_rate_check(sampleRate)) return rc;
   if (const int rc = unit_span(unit, first, count, total(a->n, sampleRate), out)) return rc;
   q = StepsCall{ctx, a, sampleRate, first, count, count};
   return MX_OK;
+}
+
+// The tail of a PCM range entry point (resample, denoise, compress), after the unit's own check of its parameters: outputs [first,
+// first + count) inside the unit's `total`, in the formats the caller gave room for — `f32_only`: the call has no int16 form —; of
+// the device form the pointers' alignment; nothing to do for an empty range; then `enqueue(d_f32, d_i16) -> status`, the unit's
+// launch on the context's stream, into the caller's device memory or through the host form.
+template <class F>
+int pcm_range(mx_ctx *ctx, bool device, bool f32_only, int64_t first, int64_t count, int64_t total, float *f32, int16_t *i16,
+              F &&enqueue) {
+  if (const int rc = unit_span("outputs", first, count, total, f32 ? (const void *)f32 : i16)) return rc;
+  if (device && f32_only) {
+    if (const int rc = align_check(f32, 4, "device samples")) return rc;
+  } else if (device && (misaligned(f32, 4) || misaligned(i16, 2))) {
+    return fail(MX_ERR_INVALID, "device samples must be 4-byte (f32) and 2-byte (int16) aligned");
+  }
+  if (count == 0) return MX_OK;
+  if (!device && f32_only)
+    return array_to_host(ctx, count, f32, "device samples", "sample download", [&](float *d) { return enqueue(d, nullptr); });
+  if (!device) return pcm_to_host(ctx, count, f32, i16, enqueue);
+  HIP_TRY(hipSetDevice(ctx->device));
+  return enqueue(f32, i16);
 }
 
 // A measure of a whole take: room for `count` records on the host (at least one), `parse(rec, q) -> status` the unit's parse of

@@ -23,7 +23,7 @@ int groups_parse(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t first_g
 
 int steps_launch(const StepsCall &q, mx_loud_step *d_steps) {
   if (q.count == 0) return MX_OK;
-  if (reinterpret_cast<uintptr_t>(d_steps) % 16) return fail(MX_ERR_INVALID, "device records must be 16-byte aligned");
+  if (const int rc = align_check(d_steps, 16, "device records")) return rc;
   HIP_TRY(hipSetDevice(q.ctx->device));
   const loud::Geometry geo = loud::geometry(q.a->n, q.sampleRate);
   LoudnessArgs g{};
@@ -108,7 +108,7 @@ int mx_loudness_integrated(const mx_loud_step *steps, int64_t nsteps, int sample
 int mx_loudness_measure(mx_ctx *ctx, const mx_audio *a, int sampleRate, mx_loudness *out) {
   return mx_guard([&]() -> int {
     if (!out) return fail(MX_ERR_INVALID, "null output");
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (const int rc = step_rate_check(sampleRate)) return rc;
     const loud::Geometry geo = loud::geometry(a->n, sampleRate);
     return whole_take<StepsCall, mx_loud_step>(

@@ -52,7 +52,7 @@ int psola_plan_out(const PsolaCall &c, Rec **grains, int64_t *ngrains, int64_t *
 bool no_output(int64_t nsamples, const float *f, const int16_t *i) { return nsamples == 0 || (!f && !i); }
 
 int psola_parse(mx_ctx *ctx, const mx_audio *a, const void *grains, int64_t ngrains, int64_t nsamples) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = handles_check(ctx, a)) return rc;
   if (ngrains < 0 || nsamples < 0 || nsamples > INT32_MAX) return fail(MX_ERR_INVALID, "grain or sample count out of range");
   if (ngrains > 0 && !grains) return fail(MX_ERR_INVALID, "null grain records");
   return MX_OK;
@@ -134,7 +134,7 @@ int psola_render_as(mx_ctx *ctx, const mx_audio *a, const PsolaCall &c, float *p
 
 // ... for the record kind the call asks for (c.n: filled in here, once the handles are known to be there)
 int psola_render(mx_ctx *ctx, const mx_audio *a, PsolaCall c, float *pcm_f32, int16_t *pcm_i16, bool to_host) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+  if (const int rc = handles_check(ctx, a)) return rc;
   c.n = a->n;
   return c.npoints == 0 ? psola_render_as<mx_psola_grain>(ctx, a, c, pcm_f32, pcm_i16, to_host)
                         : psola_render_as<mx_psola_fgrain>(ctx, a, c, pcm_f32, pcm_i16, to_host);

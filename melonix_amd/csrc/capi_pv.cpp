@@ -274,7 +274,7 @@ extern "C" {
 
 int mx_pv_pitch_shift_dev(mx_ctx *ctx, const mx_audio *a, double semitones, float *d_pcm_f32, int16_t *d_pcm_i16) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (!(semitones >= -48.0 && semitones <= 48.0)) return fail(MX_ERR_INVALID, "semitones out of range [-48, 48]");
     if (a->n == 0 || (!d_pcm_f32 && !d_pcm_i16)) return MX_OK;
     std::lock_guard<std::mutex> plk(ctx->pv_mu);
@@ -293,7 +293,7 @@ int mx_pv_pitch_shift_dev(mx_ctx *ctx, const mx_audio *a, double semitones, floa
 
 int mx_pv_pitch_shift(mx_ctx *ctx, const mx_audio *a, double semitones, float *pcm_f32_out, int16_t *pcm_i16_out) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (a->n == 0 || (!pcm_f32_out && !pcm_i16_out)) return MX_OK;
     return pcm_to_host(ctx, a->n, pcm_f32_out, pcm_i16_out,
                        [&](float *d_f, int16_t *d_i) { return mx_pv_pitch_shift_dev(ctx, a, semitones, d_f, d_i); });
@@ -377,7 +377,7 @@ int mx_pv_render_dev(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_ma
 int mx_pv_render(mx_ctx *ctx, const mx_audio *a, int sampleRate, const mx_marker *markers, int nmarkers,
                  float *pcm_f32_out, int16_t *pcm_i16_out) {
   return mx_guard([&]() -> int {
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     const int64_t m = mx_pv_render_length(a->n, sampleRate, markers, nmarkers);
     if (m < 0) return (int)m;
     if (m == 0 || (!pcm_f32_out && !pcm_i16_out)) return MX_OK;

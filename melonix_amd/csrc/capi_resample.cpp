@@ -58,23 +58,18 @@ hipError_t resample_enqueue(mx_ctx *ctx, const mx_audio *a, const mx_resample_pl
 
 namespace {
 
-// what the two range forms check of their arguments -> the plan
-int range_parse(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, const float *out,
-                mx_resample_plan &p) {
-  if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+// the two range forms: the unit's own checks -> the plan, then the tail (an empty range asks nothing of a device pointer: it is
+// refused for its alignment only where something would be written through it)
+int range_call(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, float *out, bool device) {
+  if (const int rc = handles_check(ctx, a)) return rc;
+  mx_resample_plan p;
   if (const int rc = resample_plan_check(inRate, outRate, p)) return rc;
-  return unit_span("outputs", first_out, count, rs::out_length(a->n, p), out);
-}
-
-// the device form: outputs [first_out, first_out + count) queued on the context's stream
-int range_launch(mx_ctx *ctx, const mx_audio *a, const mx_resample_plan &p, int64_t first_out, int64_t count, float *d_out) {
-  if (count == 0) return MX_OK;
-  if (reinterpret_cast<uintptr_t>(d_out) % 4) return fail(MX_ERR_INVALID, "device samples must be 4-byte aligned");
-  HIP_TRY(hipSetDevice(ctx->device));
-  const float *d_table = nullptr;
-  if (const int rc = resample_table_dev(ctx, p, &d_table)) return rc;
-  HIP_TRY(resample_enqueue(ctx, a, p, d_table, first_out, count, d_out));
-  return MX_OK;
+  return pcm_range(ctx, device, true, first_out, count, rs::out_length(a->n, p), count ? out : nullptr, nullptr, [&](float *d_out, int16_t *) {
+    const float *d_table = nullptr;
+    if (const int rc = resample_table_dev(ctx, p, &d_table)) return rc;
+    HIP_TRY(resample_enqueue(ctx, a, p, d_table, first_out, count, d_out));
+    return (int)MX_OK;
+  });
 }
 
 }  // namespace
@@ -111,27 +106,11 @@ int mx_resample_taps(int inRate, int outRate, float *out) {
 }
 
 int mx_resample_dev(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, float *d_out) {
-  return mx_guard([&]() -> int {
-    mx_resample_plan p;
-    if (const int rc = range_parse(ctx, a, inRate, outRate, first_out, count, d_out, p)) return rc;
-    return range_launch(ctx, a, p, first_out, count, d_out);
-  });
+  return mx_guard([&]() -> int { return range_call(ctx, a, inRate, outRate, first_out, count, d_out, true); });
 }
 
 int mx_resample(mx_ctx *ctx, const mx_audio *a, int inRate, int outRate, int64_t first_out, int64_t count, float *out) {
-  return mx_guard([&]() -> int {
-    mx_resample_plan p;
-    if (const int rc = range_parse(ctx, a, inRate, outRate, first_out, count, out, p)) return rc;
-    if (count == 0) return MX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeviceArray<float> d;
-    hipError_t e = d.alloc(ctx->stream, (size_t)count);
-    if (e != hipSuccess) return fail(MX_ERR_NOMEM, "device samples: %s", hipGetErrorString(e));
-    if (const int rc = range_launch(ctx, a, p, first_out, count, d.p)) return rc;
-    e = d.download(out);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? MX_OK : fail(MX_ERR_DEVICE, "sample download: %s", hipGetErrorString(e));
-  });
+  return mx_guard([&]() -> int { return range_call(ctx, a, inRate, outRate, first_out, count, out, false); });
 }
 
 }  // extern "C"

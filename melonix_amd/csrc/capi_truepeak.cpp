@@ -11,7 +11,7 @@ namespace {
 
 int steps_launch(const StepsCall &q, mx_tp_step *d_steps) {
   if (q.count == 0) return MX_OK;
-  if (reinterpret_cast<uintptr_t>(d_steps) % 8) return fail(MX_ERR_INVALID, "device records must be 8-byte aligned");
+  if (const int rc = align_check(d_steps, 8, "device records")) return rc;
   HIP_TRY(hipSetDevice(q.ctx->device));
   TruePeakArgs g{};
   g.image = q.a->d_padded;
@@ -66,7 +66,7 @@ int mx_true_peak_steps(mx_ctx *ctx, const mx_audio *a, int sampleRate, int64_t f
 int mx_true_peak_measure(mx_ctx *ctx, const mx_audio *a, int sampleRate, float *true_peak, float *sample_peak) {
   return mx_guard([&]() -> int {
     if (!true_peak && !sample_peak) return fail(MX_ERR_INVALID, "null output");
-    if (!ctx || !a) return fail(MX_ERR_INVALID, "null context or audio handle");
+    if (const int rc = handles_check(ctx, a)) return rc;
     if (const int rc = step_rate_check(sampleRate)) return rc;
     const int64_t steps = tp::step_count(a->n, sampleRate);
     return whole_take<StepsCall, mx_tp_step>(

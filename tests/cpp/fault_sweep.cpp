@@ -14,7 +14,9 @@
 //                         library's own malloc() calls — the arrays it hands out for mx_free — instead of operator new
 //   fault_sweep device    ... and those that do (context, audio, STFT in all modes, kept rows, grain table, resynthesis,
 //                         export, phase vocoder incl. the three rank stages, pyramid, f0 and its decode, tempo, chroma and key,
-//                         pitch contour, the mastering chain): only allocations made FROM the
+//                         pitch contour, the mastering chain, the take processors — sample-rate conversion, noise reduction,
+//                         compressor: range forms, print, gain curve and derived audio, the last also on a context of their
+//                         own per call, first-use tables included): only allocations made FROM the
 //                         library's own code are faulted there (the HIP runtime beneath it is not the subject)
 #include <dlfcn.h>
 #include <unistd.h>
@@ -779,6 +781,23 @@ void device_entries() {
     return {rc, rc < 0 ? 0 : fnv(f0.data(), f0.size() * sizeof(mx_f0))};
   });
   analysis_entries(ctx, a, sr, hop, F);
+  // a derived audio object of `m` samples on context `c`: its handle is set only on success; its samples and both pads are the
+  // checksum
+  auto derived_on = [](mx_ctx *c, int64_t m, int rc, mx_audio *b, const std::vector<int16_t> *pcm) -> Result {
+    if (rc < 0) {
+      CHECK(b == nullptr, "derived audio: handle set on failure");
+      return {rc, 0};
+    }
+    std::vector<float> all((size_t)(m + 2 * MX_AUDIO_PAD));
+    rc = mx_audio_length(b) == m ? mx_audio_download(c, b, -(int64_t)MX_AUDIO_PAD, (int64_t)all.size(), all.data()) : -100;
+    mx_audio_free(c, b);
+    return {rc, rc < 0 ? 0 : fnv(all.data(), all.size() * 4, pcm ? fnv(pcm->data(), pcm->size() * 2) : 0)};
+  };
+  // the take processors' arguments: 48 kHz to 44.1 kHz, a flat print with {12, 6}, the compressor's defaults (the sweep peaks at
+  // 0.5, over their threshold)
+  const int out_sr = 44100;
+  const std::vector<float> print(MX_DENOISE_BINS, 1e-4f);
+  const mx_denoise_params dp{12.f, 6.f};
   // the mastering chain at the smallest sizes that take every branch: 2049 samples at 48 kHz (one limiter tile plus one sample, 5
   // steps, one group) and one sample
   for (const int64_t len : {(int64_t)2049, (int64_t)1}) {
@@ -816,17 +835,7 @@ void device_entries() {
       if (rc < 0) CHECK(v[0] == -7.f && v[1] == -7.f, "mx_true_peak_measure: outputs written on failure");
       return {rc, rc < 0 ? 0 : fnv(v, sizeof v)};
     });
-    // a derived audio object: its handle is set only on success; its samples and both pads are the checksum
-    auto derived = [&](int rc, mx_audio *b, const std::vector<int16_t> *pcm) -> Result {
-      if (rc < 0) {
-        CHECK(b == nullptr, "derived audio: handle set on failure");
-        return {rc, 0};
-      }
-      std::vector<float> all((size_t)(len + 2 * MX_AUDIO_PAD));
-      rc = mx_audio_length(b) == len ? mx_audio_download(ctx, b, -(int64_t)MX_AUDIO_PAD, (int64_t)all.size(), all.data()) : -100;
-      mx_audio_free(ctx, b);
-      return {rc, rc < 0 ? 0 : fnv(all.data(), all.size() * 4, pcm ? fnv(pcm->data(), pcm->size() * 2) : 0)};
-    };
+    auto derived = [&](int rc, mx_audio *b, const std::vector<int16_t> *pcm) -> Result { return derived_on(ctx, len, rc, b, pcm); };
     sweep(named("mx_audio_gain (0 points)"), [&]() -> Result {
       mx_audio *b = nullptr;
       const int rc = mx_audio_gain(ctx, s, nullptr, 0, &b);
@@ -855,8 +864,92 @@ void device_entries() {
       const int rc = mx_audio_download(ctx, s, -(int64_t)MX_AUDIO_PAD, (int64_t)all.size(), all.data());
       return {rc, rc < 0 ? 0 : fnv(all.data(), all.size() * 4)};
     });
+    // the take processors: a host form's outputs are pre-filled and must stand where it fails
+    auto host_form = [&](const char *what, int rc, const void *f32, size_t nf, const void *i16, size_t ni) -> Result {
+      const unsigned char *b = static_cast<const unsigned char *>(f32), *c = static_cast<const unsigned char *>(i16);
+      if (rc < 0) {
+        bool stands = true;
+        for (size_t k = 0; k < nf; ++k) stands = stands && b[k] == 0x5A;
+        for (size_t k = 0; k < ni; ++k) stands = stands && c[k] == 0x5A;
+        CHECK(stands, "%s: outputs written on failure", what);
+        return {rc, 0};
+      }
+      return {rc, fnv(i16, ni, fnv(f32, nf))};
+    };
+    const int64_t m = mx_resample_length(len, sr, out_sr), csteps = mx_compress_steps(len, sr);
+    sweep(named("mx_resample"), [&]() -> Result {
+      std::vector<float> out((size_t)m);
+      memset(out.data(), 0x5A, out.size() * 4);
+      return host_form("mx_resample", mx_resample(ctx, s, sr, out_sr, 0, m, out.data()), out.data(), out.size() * 4, nullptr, 0);
+    });
+    sweep(named("mx_audio_resample"), [&]() -> Result {
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_resample(ctx, s, sr, out_sr, &b);
+      return derived_on(ctx, m, rc, b, nullptr);
+    });
+    if (len == 2049)  // (one sample holds no frame of a print: the library refuses the region)
+      sweep(named("mx_noise_print"), [&]() -> Result {
+        std::vector<float> out(MX_DENOISE_BINS);
+        memset(out.data(), 0x5A, out.size() * 4);
+        return host_form("mx_noise_print", mx_noise_print(ctx, s, 0, 1024, out.data()), out.data(), out.size() * 4, nullptr, 0);
+      });
+    sweep(named("mx_denoise"), [&]() -> Result {
+      std::vector<float> f((size_t)len);
+      std::vector<int16_t> i((size_t)len);
+      memset(f.data(), 0x5A, f.size() * 4);
+      memset(i.data(), 0x5A, i.size() * 2);
+      const int rc = mx_denoise(ctx, s, print.data(), &dp, 0, len, f.data(), i.data());
+      return host_form("mx_denoise", rc, f.data(), f.size() * 4, i.data(), i.size() * 2);
+    });
+    sweep(named("mx_audio_denoise"), [&]() -> Result {
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_denoise(ctx, s, print.data(), &dp, &b);
+      return derived(rc, b, nullptr);
+    });
+    sweep(named("mx_compress"), [&]() -> Result {
+      std::vector<float> f((size_t)len);
+      std::vector<int16_t> i((size_t)len);
+      memset(f.data(), 0x5A, f.size() * 4);
+      memset(i.data(), 0x5A, i.size() * 2);
+      const int rc = mx_compress(ctx, s, sr, nullptr, 0, len, f.data(), i.data());
+      return host_form("mx_compress", rc, f.data(), f.size() * 4, i.data(), i.size() * 2);
+    });
+    sweep(named("mx_compress_gain"), [&]() -> Result {
+      std::vector<int32_t> g((size_t)csteps);
+      memset(g.data(), 0x5A, g.size() * 4);
+      return host_form("mx_compress_gain", mx_compress_gain(ctx, s, sr, nullptr, 0, csteps, g.data()), g.data(), g.size() * 4, nullptr, 0);
+    });
+    sweep(named("mx_audio_compress"), [&]() -> Result {
+      mx_audio *b = nullptr;
+      const int rc = mx_audio_compress(ctx, s, sr, nullptr, &b);
+      return derived(rc, b, nullptr);
+    });
     mx_audio_free(ctx, s);
   }
+  // ... and on a context of its own per call, so that the tables a context builds on first use (the 1024-point transform's
+  // twiddles, the resampler's taps) are built, and faulted, under the call that owns the new object's buffer
+  auto fresh = [&](int64_t m, const std::function<int(mx_ctx *, mx_audio *, mx_audio **)> &make) -> Result {
+    mx_ctx *c = nullptr;
+    mx_audio *s = nullptr, *b = nullptr;
+    int rc = mx_ctx_create(0, &c);
+    if (rc == MX_OK) rc = mx_audio_upload(c, w.data() + 1000, 2049, &s);
+    if (rc == MX_OK) rc = make(c, s, &b);
+    const Result r = rc == MX_OK ? derived_on(c, m, rc, b, nullptr) : Result{rc, 0};
+    if (rc < 0) CHECK(b == nullptr, "derived audio on a fresh context: handle set on failure");
+    const bool was = g_in_call;
+    g_in_call = false;
+    if (s) mx_audio_free(c, s);
+    if (c) mx_ctx_destroy(c);
+    g_in_call = was;
+    return r;
+  };
+  sweep("mx_audio_denoise (fresh context)", [&]() -> Result {
+    return fresh(2049, [&](mx_ctx *c, mx_audio *s, mx_audio **b) { return mx_audio_denoise(c, s, print.data(), &dp, b); });
+  });
+  sweep("mx_audio_resample (fresh context)", [&]() -> Result {
+    return fresh(mx_resample_length(2049, sr, out_sr),
+                 [&](mx_ctx *c, mx_audio *s, mx_audio **b) { return mx_audio_resample(c, s, sr, out_sr, b); });
+  });
   sweep("mx_ctx_release_scratch", [&]() -> Result { return {mx_ctx_release_scratch(ctx), 0}; });
   mx_free(steps);
   mx_free(gs);

@@ -22,6 +22,7 @@ ceil(n / hop) and the reads into the trailing pad are the same case.  (tests/tes
 CPU; tests/test_gpu_far_take.py holds every span-form entry point to "far == control, byte for byte".)"""
 import ctypes as C
 import functools
+import time
 
 import numpy as np
 import pytest
@@ -135,3 +136,14 @@ class FarTake:
         if self.buf is not None:
             self.buf.free()
             self.buf = None
+
+
+@pytest.fixture(scope="module")
+def far(gpu_ctx):
+    """The far take, held for the whole of the importing file and freed at its end."""
+    t0 = time.perf_counter()
+    ft = FarTake(gpu_ctx)
+    made = time.perf_counter() - t0
+    yield ft
+    print(f"far take: made in {made:.2f} s; peak device memory declared by this file {ft.peak / GIB:.2f} GiB")
+    ft.free()

@@ -1,6 +1,7 @@
 """tests/hip_timing.py — what the hour tools (tests/tools) and the suite's timed test share: the libraries under test on one device
-image of the samples, and the timed-launch loop: launches on the null stream between two HIP events, the candidates in turn
-(interleaved launch by launch, so that drift of the clocks hits all alike), warm-ups first."""
+image of the samples, the two ends of a long output for a comparison, and the timed-launch loop: launches on the null stream
+between two HIP events, the candidates in turn (interleaved launch by launch, so that drift of the clocks hits all alike), warm-ups
+first, a hook behind every launch for a tool whose launches make objects it has to free."""
 import ctypes as C
 import os
 
@@ -48,6 +49,23 @@ def same_bytes(libs, *names):
     return got[0]
 
 
+EDGE = 1 << 20  # elements compared at either end of an output
+
+
+def ends(buf, m, dtype=np.float32):
+    """The first and the last EDGE elements of the m that a DevBuf holds, as bytes."""
+    k = min(EDGE, m)
+    return buf.read(dtype, 0, k).tobytes() + buf.read(dtype, np.dtype(dtype).itemsize * (m - k), k).tobytes()
+
+
+def free_all(made):
+    """-> an `after` hook of EventTimer.timed: frees the objects the last launch appended to `made`."""
+    def after():
+        while made:
+            made.pop().free()
+    return after
+
+
 class EventTimer:
     def __init__(self, hip):
         """hip: the process's HIP runtime (conftest.loaded_hip())."""
@@ -68,12 +86,15 @@ class EventTimer:
         assert self.hip.hipEventElapsedTime(C.byref(ms), self.e0, self.e1) == 0
         return ms.value
 
-    def timed(self, calls, warm, runs):
-        """calls: name -> callable.  -> {name: median / min / max ms of `runs` launches after `warm`}, the calls in turn."""
+    def timed(self, calls, warm, runs, after=None):
+        """calls: name -> callable.  -> {name: median / min / max ms of `runs` launches after `warm`}, the calls in turn; after():
+        run behind every launch, outside its events."""
         ts = {k: [] for k in calls}
         for it in range(warm + runs):
             for k, call in calls.items():
                 t = self.once(call)
                 if it >= warm:
                     ts[k].append(t)
+                if after:
+                    after()
         return {k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()}

@@ -112,6 +112,14 @@ def test_allocation_fault_sweep_device_entry_points(mxlib, tmp_path):
                  "mx_tempo_from_flux (windows)", "mx_tempo_detect", "mx_chroma", "mx_chroma_sum", "mx_key_detect (windows)", "mx_f0_decode",
                  "mx_f0_track_decoded", "mx_contour_cents", "mx_contour_split", "mx_pitch_contour"):
         assert re.search(r"^\s+" + re.escape(name) + r"\s+\d+ allocation", r.stdout, flags=re.M), (name, tail)
+    # the take processors at both lengths (no print from one sample); the calls that make an audio object allocate its handle, and
+    # on a context of their own the context and its first-use tables too: those were actually faulted
+    for name, at_least in [(f"{what} (n = {n})", k) for n in (2049, 1) for what, k in
+                           (("mx_resample", 0), ("mx_audio_resample", 1), ("mx_denoise", 0), ("mx_audio_denoise", 1), ("mx_compress", 0),
+                            ("mx_compress_gain", 0), ("mx_audio_compress", 1))] + \
+            [("mx_noise_print (n = 2049)", 0), ("mx_audio_denoise (fresh context)", 3), ("mx_audio_resample (fresh context)", 3)]:
+        mm = re.search(r"^\s+" + re.escape(name) + r"\s+(\d+) allocation", r.stdout, flags=re.M)
+        assert mm and int(mm.group(1)) >= at_least, (name, tail)
     # ... and the library's own malloc() calls on the device paths (the grain table's arrays)
     exe_m = _build_sweep(tmp_path, ["-DSWEEP_MALLOC"])
     rm = subprocess.run([exe_m, "device-malloc"], capture_output=True, text=True, timeout=1500)

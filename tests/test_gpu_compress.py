@@ -12,7 +12,8 @@ import compress_ref as R
 import far_take as FT
 from conftest import DevBuf
 from test_compress_host import LENGTHS, SETTINGS, load_emu, take_of
-from test_gpu_truepeak import Guarded
+from far_take import far  # noqa: F401  (the module's far-take fixture)
+from guarded import Guarded, pcm_dev_range
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +26,19 @@ def emu(mxlib):
 
 
 def dev_range(ctx, audio, sr, p, first, count, shift=0, shift16=0, f32=True, i16=False):
-    """The range form into guarded buffers -> (f32 | None, int16 | None); the guards must stand.  The device is synchronised between
-    the buffers' fill and the launch: the fill is a hipMemset on the null stream and the launch goes to the context's non-blocking
-    stream, which nothing orders behind it."""
-    gf = Guarded(count * 4, shift) if f32 else None
-    gi = Guarded(count * 2, shift16) if i16 else None
-    assert (gf or gi).buf.hip.hipDeviceSynchronize() == 0
-    try:
-        ctx.compress_dev(audio, sr, first, count, gf.ptr if gf else None, gi.ptr if gi else None, **p)
-        ctx.synchronize()
-        return (np.frombuffer(gf.fetch().tobytes(), dtype=np.float32) if gf else None,
-                np.frombuffer(gi.fetch().tobytes(), dtype=np.int16) if gi else None)
-    finally:
-        for g in (gf, gi):
-            if g:
-                g.free()
+    """The range form into guarded buffers -> (f32 | None, int16 | None); the guards must stand."""
+    return pcm_dev_range(lambda f, i: (ctx.compress_dev(audio, sr, first, count, f, i, **p), ctx.synchronize()),
+                         count, shift, shift16, f32, i16)
 
 
 def dev_steps(ctx, audio, sr, p, first_step, nsteps, shift=4):
     """mx_compress_peaks_dev and mx_compress_gain_dev into guarded buffers -> (peaks f32, gain int32)"""
     gp, gg = Guarded(nsteps * 4, shift), Guarded(nsteps * 4, shift + 4)
-    assert gp.buf.hip.hipDeviceSynchronize() == 0
     try:
         ctx.compress_peaks_dev(audio, sr, first_step, nsteps, gp.ptr)
         ctx.compress_gain_dev(audio, sr, first_step, nsteps, gg.ptr, **p)
         ctx.synchronize()
-        return np.frombuffer(gp.fetch().tobytes(), dtype=np.float32), np.frombuffer(gg.fetch().tobytes(), dtype=np.int32)
+        return gp.take(np.float32), gg.take(np.int32)
     finally:
         gp.free()
         gg.free()
@@ -222,13 +210,6 @@ def test_refusals_happen_before_any_launch(mxlib, gpu_ctx):
     finally:
         buf.free()
         a.free()
-
-
-@pytest.fixture(scope="module")
-def far(gpu_ctx):
-    t = FT.FarTake(gpu_ctx)
-    yield t
-    t.free()
 
 
 @pytest.mark.parametrize("island", ("B2G", "B4G", "END"))

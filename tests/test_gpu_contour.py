@@ -9,32 +9,12 @@ import pytest
 
 import contour_ref as R
 from conftest import DevBuf
+from guarded import Guarded
 from test_contour_host import stage_a_track
 
 pytestmark = pytest.mark.gpu
 
 REC, STAT = R.REC_DTYPE.itemsize, R.STAT_DTYPE.itemsize
-GUARD = 64  # bytes either side of every device output
-
-
-class Guarded:
-    """A device output of `nbytes` with GUARD bytes of 0xA5 either side: .ptr is the output, .take(dtype) the output once the
-    guard bands are seen untouched."""
-
-    def __init__(self, nbytes):
-        self.nbytes, self.buf = nbytes, DevBuf(nbytes + 2 * GUARD, fill=0xA5)
-        self.ptr = self.buf.ptr + GUARD
-
-    def take(self, dtype):
-        raw = self.buf.read(np.uint8)
-        assert raw[:GUARD].tobytes() == b"\xa5" * GUARD and raw[GUARD + self.nbytes:].tobytes() == b"\xa5" * GUARD
-        return raw[GUARD:GUARD + self.nbytes].view(dtype).copy()
-
-    def untouched(self):
-        return self.buf.read(np.uint8).tobytes() == b"\xa5" * (self.nbytes + 2 * GUARD)
-
-    def free(self):
-        self.buf.free()
 
 
 def dev_cents(ctx, track, sr, threshold=0.15, rms_floor=1e-3):

@@ -13,7 +13,8 @@ import denoise_ref as D
 import emu_build
 import far_take as FT
 from conftest import DevBuf
-from test_gpu_truepeak import Guarded
+from far_take import far  # noqa: F401  (the module's far-take fixture)
+from guarded import Guarded, pcm_dev_range
 
 pytestmark = pytest.mark.gpu
 
@@ -22,21 +23,9 @@ SET = (24.0, 6.0)
 
 
 def dev_range(ctx, audio, P, setting, first, count, shift=0, shift16=0, f32=True, i16=False):
-    """The range form into guarded buffers -> (f32 | None, int16 | None); the guards must stand.  The device is synchronised between
-    the buffers' fill and the launch: the fill is a hipMemset on the null stream and the launch goes to the context's non-blocking
-    stream, which nothing orders behind it (tests/test_gpu_resample.py dev_range)."""
-    gf = Guarded(count * 4, shift) if f32 else None
-    gi = Guarded(count * 2, shift16) if i16 else None
-    assert (gf or gi).buf.hip.hipDeviceSynchronize() == 0
-    try:
-        ctx.denoise_dev(audio, P, setting[0], setting[1], first, count, gf.ptr if gf else None, gi.ptr if gi else None)
-        ctx.synchronize()
-        return (np.frombuffer(gf.fetch().tobytes(), dtype=np.float32) if gf else None,
-                np.frombuffer(gi.fetch().tobytes(), dtype=np.int16) if gi else None)
-    finally:
-        for g in (gf, gi):
-            if g:
-                g.free()
+    """The range form into guarded buffers -> (f32 | None, int16 | None); the guards must stand."""
+    return pcm_dev_range(lambda f, i: (ctx.denoise_dev(audio, P, setting[0], setting[1], first, count, f, i), ctx.synchronize()),
+                         count, shift, shift16, f32, i16)
 
 
 @pytest.fixture(scope="module")
@@ -145,13 +134,12 @@ def test_the_device_print(mxlib, gpu_ctx):
         for begin, end in ((0, 1024), (100, 100 + 1024 + 256 + 255), (0, 12000), (256, 256 + big)):
             f0, count = D.region_frames(len(x), begin, end)
             gr, gp = Guarded(count * D.BINS * 4, 4), Guarded(D.BINS * 4, 8)
-            assert gr.buf.hip.hipDeviceSynchronize() == 0
             try:
                 gpu_ctx.noise_rows_dev(a, f0, count, gr.ptr)
                 gpu_ctx.noise_print_dev(a, begin, end, gp.ptr)
                 gpu_ctx.synchronize()
-                rows = np.frombuffer(gr.fetch().tobytes(), dtype=np.float32).reshape(count, D.BINS)
-                dev = np.frombuffer(gp.fetch().tobytes(), dtype=np.float32)
+                rows = gr.take(np.float32).reshape(count, D.BINS)
+                dev = gp.take(np.float32)
             finally:
                 gr.free()
                 gp.free()
@@ -252,13 +240,6 @@ def test_refusals_happen_before_any_launch(mxlib, gpu_ctx):
         a.free()
 
 
-@pytest.fixture(scope="module")
-def far(gpu_ctx):
-    t = FT.FarTake(gpu_ctx)
-    yield t
-    t.free()
-
-
 @pytest.mark.parametrize("island", ("B2G", "B4G", "END"))
 def test_the_longest_take(gpu_ctx, far, island):
     """The range form over an island of the longest take the header admits equals the island uploaded as a take of its own, byte
@@ -296,12 +277,11 @@ def test_the_device_beside_the_emulation(mxlib, gpu_ctx, vowel):
     assert lib.emu_noise_rows(x.ctypes.data, n, 0, F, 1, emu_rows.ctypes.data) == 0
     a = gpu_ctx.upload(x)
     g = Guarded(F * D.BINS * 4)
-    assert g.buf.hip.hipDeviceSynchronize() == 0
     try:
         dev = gpu_ctx.denoise_range(a, P, *SET)[0]
         gpu_ctx.noise_rows_dev(a, 0, F, g.ptr)
         gpu_ctx.synchronize()
-        rows = np.frombuffer(g.fetch().tobytes(), dtype=np.float32).reshape(F, D.BINS)
+        rows = g.take(np.float32).reshape(F, D.BINS)
     finally:
         g.free()
         a.free()

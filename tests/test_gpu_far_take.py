@@ -14,7 +14,6 @@ reference — and its slots to the track's, field for field, as that module does
 import contextlib
 import ctypes as C
 import math
-import time
 
 import numpy as np
 import pytest
@@ -30,6 +29,7 @@ import sibilant_ref as S
 import truepeak_ref as T
 import yin_ref as Y
 from conftest import SR, DevBuf, mag_tol
+from far_take import far  # noqa: F401  (the module's far-take fixture)
 from test_gpu_onset import flux_tol
 from test_gpu_psola import _hand_plan
 from test_gpu_psola import check as psola_check
@@ -45,17 +45,6 @@ N_MAX = FT.N_MAX
 INT32_MAX = 2 ** 31 - 1
 ISLANDS = FT.SPAN_ISLANDS  # B2G, B4G, B6G, END
 ODD_HOP = 375
-
-
-@pytest.fixture(scope="module")
-def far(gpu_ctx):
-    """The far take, held for the whole file and freed at its end."""
-    t0 = time.perf_counter()
-    ft = FT.FarTake(gpu_ctx)
-    made = time.perf_counter() - t0
-    yield ft
-    print(f"far take: made in {made:.2f} s; peak device memory declared by this file {ft.peak / FT.GIB:.2f} GiB")
-    ft.free()
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ import loudness_ref as L
 import resample_ref as R
 import truepeak_ref as T
 from conftest import DevBuf
-from test_gpu_truepeak import Guarded
+from guarded import pcm_dev_range
 
 pytestmark = pytest.mark.gpu
 
@@ -35,17 +35,8 @@ def tables(mxlib):
 
 
 def dev_range(ctx, audio, pair, first, count, shift=0):
-    """The range form into a guarded buffer -> the outputs; the guards must stand.  The buffer's 0xA5 fill is a hipMemset on the
-    null stream and the launch goes to the context's non-blocking stream, which nothing orders behind it: without the device
-    synchronise in between the fill can land on top of the outputs (seen on the MI355X: 267 of 300 fills did)."""
-    g = Guarded(count * 4, shift)
-    assert g.buf.hip.hipDeviceSynchronize() == 0
-    try:
-        ctx.resample_dev(audio, pair[0], pair[1], first, count, g.ptr)
-        ctx.synchronize()
-        return np.frombuffer(g.fetch().tobytes(), dtype=np.float32)
-    finally:
-        g.free()
+    """The range form into a guarded buffer -> the outputs; the guards must stand."""
+    return pcm_dev_range(lambda d, _: (ctx.resample_dev(audio, pair[0], pair[1], first, count, d), ctx.synchronize()), count, shift)[0]
 
 
 @pytest.mark.parametrize("pair", R.PAIRS, ids=IDS)

@@ -13,6 +13,7 @@ import loudness_ref as L
 import pcm_extremes as PCM
 import truepeak_ref as T
 from conftest import DevBuf
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +21,6 @@ RATES = (48000, 44100, 8000, 96000, 192000)
 LENGTHS = (1, 5, 6, 7, 479, 480, 481, 4801, 10007)
 LOOKAHEADS = (1, 2, 63, 64, 65, 240, 1024)
 LIMIT_LENGTHS = (1, 7, 2047, 2048, 2049, 4097, 10007)
-GUARD = 64 * 1024  # bytes of 0xA5 either side of what a launch may write
 C1 = T.MINUS_1_DBTP
 
 
@@ -31,33 +31,13 @@ def taps(mxlib):
     return t
 
 
-class Guarded:
-    """`nbytes` of device memory `shift` bytes into a 0xA5 allocation with GUARD bytes either side (the pattern of
-    tests/test_gpu_guard.py): .ptr, .fetch() -> the payload, after checking that nothing around it was written."""
-
-    def __init__(self, nbytes, shift=0):
-        self.nbytes, self.shift = int(nbytes), int(shift)
-        self.buf = DevBuf(2 * GUARD + self.shift + self.nbytes, fill=0xA5)
-        self.ptr = self.buf.ptr + GUARD + self.shift
-
-    def fetch(self):
-        raw = self.buf.read(np.uint8)
-        lo, hi = GUARD + self.shift, GUARD + self.shift + self.nbytes
-        assert np.all(raw[:lo] == 0xA5), f"bytes written BEFORE the output (first at {int(np.argmax(raw[:lo] != 0xA5)) - lo})"
-        assert np.all(raw[hi:] == 0xA5), f"bytes written BEHIND the output (first at +{int(np.argmax(raw[hi:] != 0xA5))})"
-        return raw[lo:hi].copy()
-
-    def free(self):
-        self.buf.free()
-
-
 def dev_records(ctx, audio, sr, first_step, nsteps, shift=0):
     """The device form into a guarded buffer -> the records; the guards must stand."""
     g = Guarded(nsteps * 8, shift)
     try:
         ctx.true_peak_steps_dev(audio, sr, first_step, nsteps, g.ptr)
         ctx.synchronize()
-        return np.frombuffer(g.fetch().tobytes(), dtype=T.STEP_DTYPE)
+        return g.take(T.STEP_DTYPE)
     finally:
         g.free()
 
@@ -69,7 +49,7 @@ def dev_limit(ctx, audio, sr, c, A, pcm_shift=0):
     try:
         b = ctx.limit_dev(audio, sr, lookahead=A, d_pcm16=g.ptr, ceiling_amp=c)
         ctx.synchronize()
-        pcm = np.frombuffer(g.fetch().tobytes(), dtype=np.int16)
+        pcm = g.take(np.int16)
         pad = 4096
         return (ctx.audio_download(b), pcm, ctx.audio_download(b, -pad, pad), ctx.audio_download(b, audio.n, pad))
     finally:

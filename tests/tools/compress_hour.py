@@ -24,17 +24,10 @@ import numpy as np  # noqa: E402
 import melonix_amd as mx  # noqa: E402
 import denoise_ref as D  # noqa: E402
 from conftest import DevBuf, loaded_hip  # noqa: E402
-from hip_timing import EventTimer, device_image  # noqa: E402
+from hip_timing import EventTimer, device_image, ends, free_all  # noqa: E402
 
 WARM, RUNS = 3, 10
 SR = 48000
-EDGE = 1 << 20  # elements compared at either end of an output
-
-
-def ends(buf, m, dtype):
-    k = min(EDGE, m)
-    size = np.dtype(dtype).itemsize
-    return buf.read(dtype, 0, k).tobytes() + buf.read(dtype, size * (m - k), k).tobytes()
 
 
 def main():
@@ -66,15 +59,7 @@ def main():
     first = ends(d_f32, n, np.float32), ends(d_i16, n, np.int16)
     turned_down = int((ctx.compress_gain(a, SR, 0, min(steps, 100000)) < (1 << 30)).sum())
     timer = EventTimer(loaded_hip())
-    ts = {k: [] for k in calls}
-    for it in range(WARM + RUNS):
-        for k, call in calls.items():
-            t = timer.once(call)
-            if it >= WARM:
-                ts[k].append(t)
-            while made:
-                made.pop().free()
-    rows = {k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()}
+    rows = timer.timed(calls, WARM, RUNS, after=free_all(made))
     assert (ends(d_f32, n, np.float32), ends(d_i16, n, np.int16)) == first  # every launch wrote the same bytes
     med = {k: v["median"] for k, v in rows.items()}
     res = {"seconds": args.seconds, "samples": n, "steps": steps, "groups": -(-steps // 4096), "warmups": WARM, "launches": RUNS,

@@ -23,7 +23,7 @@ import numpy as np  # noqa: E402
 import melonix_amd as mx  # noqa: E402
 import loudness_ref as L  # noqa: E402
 from conftest import SR, DevBuf, loaded_hip  # noqa: E402
-from hip_timing import EventTimer, device_image  # noqa: E402
+from hip_timing import EventTimer, device_image, free_all  # noqa: E402
 
 HOP, WARM, RUNS = 256, 3, 10
 
@@ -65,15 +65,7 @@ def main():
     calls = {"loudness_steps": lambda: ctx.loudness_steps_dev(a, SR, 0, groups, rec.ptr),
              "audio_gain": lambda: made.append(ctx.audio_gain_dev(a, d_pts.ptr, len(pts))),
              "onset_flux": lambda: ctx.onset_flux_dev(a, SR, HOP, 0, frames, flux.ptr)}
-    ts = {k: [] for k in calls}
-    for it in range(WARM + RUNS):
-        for k, call in calls.items():
-            t = timer.once(call)
-            if it >= WARM:
-                ts[k].append(t)
-        while made:
-            made.pop().free()
-    rows = {k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()}
+    rows = timer.timed(calls, WARM, RUNS, after=free_all(made))
     assert rec.read(mx.LOUD_STEP_DTYPE).tobytes() == records.tobytes()  # every launch wrote the same bytes
     res = {"samples": n, "sr": SR, "steps": steps, "groups": groups, "frames": frames, "warmups": WARM, "launches": RUNS, "kernel_ms": rows,
            "loudness_over_onset_flux": rows["loudness_steps"]["median"] / rows["onset_flux"]["median"],

@@ -23,16 +23,10 @@ import numpy as np  # noqa: E402
 import melonix_amd as mx  # noqa: E402
 import loudness_ref as L  # noqa: E402
 from conftest import DevBuf, loaded_hip  # noqa: E402
-from hip_timing import EventTimer, device_image  # noqa: E402
+from hip_timing import EDGE, EventTimer, device_image, ends, free_all  # noqa: E402
 
 WARM, RUNS = 3, 10
 PAIRS = ((48000, 44100), (44100, 48000), (96000, 48000))
-EDGE = 1 << 20  # floats compared at either end of an output
-
-
-def ends(buf, m):
-    k = min(EDGE, m)
-    return buf.read(np.float32, 0, k).tobytes() + buf.read(np.float32, 4 * (m - k), k).tobytes()
 
 
 def main():
@@ -69,15 +63,7 @@ def main():
     calls["audio_gain"] = lambda: made.append(ctx.audio_gain_dev(a48, d_pts.ptr, 1))
     calls["audio_limit"] = lambda: made.append(ctx.limit_dev(a48, 48000))
     timer = EventTimer(loaded_hip())
-    ts = {k: [] for k in calls}
-    for it in range(WARM + RUNS):
-        for k, call in calls.items():
-            t = timer.once(call)
-            if it >= WARM:
-                ts[k].append(t)
-            while made:
-                made.pop().free()
-    rows = {k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()}
+    rows = timer.timed(calls, WARM, RUNS, after=free_all(made))
     for pair in PAIRS:
         assert ends(*outs[pair]) == first[pair], pair  # every launch wrote the same bytes
     res = {"seconds": args.seconds, "warmups": WARM, "launches": RUNS, "kernel_ms": rows,

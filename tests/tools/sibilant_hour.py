@@ -24,7 +24,7 @@ import numpy as np  # noqa: E402
 import melonix_amd as mx  # noqa: E402
 import sibilant_ref as S  # noqa: E402
 from conftest import SR, DevBuf, loaded_hip  # noqa: E402
-from hip_timing import EventTimer, device_image  # noqa: E402
+from hip_timing import EventTimer, device_image, free_all  # noqa: E402
 
 HOP, WARM, RUNS = 256, 3, 10
 
@@ -62,15 +62,8 @@ def main():
     def gain():
         made.append(ctx.audio_gain_dev(a, d_pts.ptr, len(pts)))
 
-    ts = {"gain": [], "granular": []}
-    for it in range(WARM + RUNS):
-        for k, call in (("gain", gain), ("granular", lambda: ctx.resynth_dev(a, d_steps.ptr, len(steps), total, d_pcm.ptr, None))):
-            t = timer.once(call)
-            if it >= WARM:
-                ts[k].append(t)
-        while made:
-            made.pop().free()
-    rows.update({k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()})
+    rows.update(timer.timed({"gain": gain, "granular": lambda: ctx.resynth_dev(a, d_steps.ptr, len(steps), total, d_pcm.ptr, None)},
+                            WARM, RUNS, after=free_all(made)))
     tiles = n // len(tile)
     res = {"samples": n, "sr": SR, "hop": HOP, "frames": frames, "warmups": WARM, "launches": RUNS, "kernel_ms": rows,
            "features_over_onset_flux": rows["features"]["median"] / rows["onset_flux"]["median"],

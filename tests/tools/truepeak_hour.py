@@ -21,7 +21,7 @@ import numpy as np  # noqa: E402
 import melonix_amd as mx  # noqa: E402
 import loudness_ref as L  # noqa: E402
 from conftest import SR, DevBuf, loaded_hip  # noqa: E402
-from hip_timing import EventTimer, device_image  # noqa: E402
+from hip_timing import EventTimer, device_image, free_all  # noqa: E402
 
 WARM, RUNS = 3, 10
 
@@ -59,15 +59,7 @@ def main():
              "audio_limit_pcm16": lambda: made.append(ctx.limit_dev(a, SR, lookahead=lookahead, d_pcm16=pcm.ptr)),
              "audio_gain": lambda: made.append(ctx.audio_gain_dev(a, d_pts.ptr, 1)),
              "loudness_steps": lambda: ctx.loudness_steps_dev(a, SR, 0, groups, loud.ptr)}
-    ts = {k: [] for k in calls}
-    for it in range(WARM + RUNS):
-        for k, call in calls.items():
-            t = timer.once(call)
-            if it >= WARM:
-                ts[k].append(t)
-            while made:
-                made.pop().free()
-    rows = {k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t))) for k, t in ts.items()}
+    rows = timer.timed(calls, WARM, RUNS, after=free_all(made))
     assert rec.read(mx.TP_STEP_DTYPE).tobytes() == records.tobytes()  # every launch wrote the same bytes
     assert pcm.read(np.int16, 0, 1 << 20).tobytes() == first_pcm.tobytes()
     ceiling = mx.limit_params_default(SR)["ceiling_amp"]
